@@ -12,7 +12,10 @@ NLL loss, backward, DDP gradient averaging over RCCL, Adadelta update.  W untime
 then exactly K steps bracketed by barrier + device synchronize on both sides; the reported
 time is the max over ranks; ``value`` is the whole-job images/s (N * B * K / t).
 
-With ``--full-run`` (default on) it then also measures the README's complete workload twice:
+A plain run does only that: set up, warm up, time the K steps, print the result line
+(``--dump-outputs DIR`` also writes what the last timed step left, as ``DIR/<name>.npy``).
+
+With ``--full`` it also measures the README's complete workload twice:
 
 * ``total_cost_time_s`` - the reference's own metric, measured the reference's way: rank 0 launches
   ``mnist_ddp.py --batch-size B --epochs 20 --synthetic`` as a child job at the same N (plain
@@ -191,7 +194,19 @@ def parse_args(argv=None):
     ap.add_argument("--batch-size", type=int, default=200, help="per-GPU batch (README config: 200)")
     ap.add_argument("--graph-steps", type=int, default=50, help="steps per captured hipGraph (0 = eager; 50 as the driver)")
     ap.add_argument("--single-bucket", action="store_true", help="one all-reduce per step (no overlap)")
-    ap.add_argument("--no-full-run", dest="full_run", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the README's complete workload: the mnist_ddp.py "
+                         "child job (total_cost_time_s) and the in-process 20 epochs with evaluation "
+                         "(wallclock_20ep_s, final_test_acc).  Off by default: a plain run sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--no-full-run", dest="full_run", action="store_false",
+                    help="no-op without --full, kept for existing command lines (it was the way to skip the "
+                         "20 epochs and the child job when they ran by default); --full --no-full-run is a "
+                         "plain run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left - the parameters, the "
+                         "gradient, the Adadelta state (flat fp32 layouts) and the timed steps' losses - as "
+                         "DIR/<name>.npy (rank 0; same arguments, same inputs: comparable between builds)")
     ap.add_argument("--epochs", type=int, default=EPOCHS, help="epochs for the full-run wallclock")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--force-comm", action="store_true",
@@ -222,7 +237,29 @@ def parse_args(argv=None):
                          "clocks ramp over ~10 ms of load: a 20-step window opened on a device that ran "
                          "only the warmup reads 67.8-68.3 us/step of device time, after 500 warm steps "
                          "65.7-65.9 (600 steps: 64.7); profiles/r5/ab/warm_replay_steps.txt")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full_run = args.full and args.full_run
+    return args
+
+
+def dump_outputs(path: str, tr, ms, warmup: int, steps: int) -> dict:
+    """``--dump-outputs``: what a caller of the timed path holds after its last step, as float32
+    ``.npy`` files - the flat parameter, gradient and Adadelta buffers (ModelState layouts, 4.8 MB
+    each) and the loss of every timed step still in the trainer's loss ring."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"param": ms.param, "grad": ms.grad, "square_avg": ms.square_avg, "acc_delta": ms.acc_delta}
+    ring = tr.loss_log.numel()
+    if ring and steps > 0:
+        kept = min(steps, ring)
+        at = torch.arange(warmup + steps - kept, warmup + steps, device=tr.loss_log.device) % ring
+        arrays["loss"] = tr.loss_log[at]
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 # ----------------------------------------------------------------------------- self-launch
@@ -371,7 +408,8 @@ def run_rank(args, world: int, rank: int, local: int, diag: Diag) -> dict | None
         torch.manual_seed(args.seed)
         net = Net()
         train = load_mnist(train=True, synthetic_data=True, verbose=False)
-        test = load_mnist(train=False, synthetic_data=True, verbose=False) if rank == 0 else None
+        # (the test split is only evaluated by the --full 20-epoch run)
+        test = load_mnist(train=False, synthetic_data=True, verbose=False) if rank == 0 and args.full_run else None
         sampler = DistributedIndexStream(len(train), world, rank, shuffle=True, seed=0)
         total = args.warmup + args.steps
         steps_per_epoch = math.ceil(len(sampler) / B)
@@ -437,6 +475,10 @@ def run_rank(args, world: int, rank: int, local: int, diag: Diag) -> dict | None
     elapsed = _max_over_ranks(elapsed)
     final_loss = float(tr.loss_log[(total - 1) % tr.loss_log.numel()].item()) if tr.loss_log.numel() else float("nan")
     img_s = world * B * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        diag.phase = "dump_outputs"
+        dumped = dump_outputs(args.dump_outputs, tr, ms, args.warmup, args.steps)
     # DDP correctness of the timed run: every rank must hold bitwise identical parameters
     diag.phase = "params_in_sync"
     in_sync = True
@@ -585,6 +627,7 @@ def run_rank(args, world: int, rank: int, local: int, diag: Diag) -> dict | None
             "vs_baseline_wallclock_inprocess": round(base / wall, 1) if (wall and base) else None,
             "final_test_acc": round(acc, 4) if acc is not None else None,
             "last_train_loss": round(final_loss, 4),
+            "dumped_outputs": {"dir": args.dump_outputs, "float32": dumped} if dumped else None,
             "setup_s": round(t0 - t_setup, 2),
             "timed_enqueue_ms": round(1000.0 * (t_enq - t0), 3),
             "timed_device_ms": round(ev0.elapsed_time(ev1), 3),

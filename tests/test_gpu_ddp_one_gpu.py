@@ -84,7 +84,7 @@ def test_bench_reports_correctness(gpu_box, tmp_path, W, launcher):
     """``bench.py --gpus W`` under torchrun, and (W = 8) launching its W ranks itself with no launcher
     (the driver's plain command): ONE JSON line with n_gpus W, params in sync, the transport, its
     validation and the per-phase setup seconds."""
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", str(W), "--steps", "20", "--warmup", "5", "--epochs", "2",
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", str(W), "--steps", "20", "--warmup", "5", "--full", "--epochs", "2",
             "--dist-backend", "gloo", "--allreduce", "xgmi"] + (["--no-script-run"] if W > 4 else [])
     # (W ranks + a W-rank child job would hold 2W processes on the one GPU; the box allows 16)
     if launcher == "torchrun":

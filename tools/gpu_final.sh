@@ -8,7 +8,7 @@ fatal() { case $1 in 124|134|137|139) echo "fatal exit $1 in $2: stopping"; exit
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1; rc=$?
 echo "TEST_EXIT $rc"; tail -2 $O/gpu_tests.log; fatal $rc tests
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; tail -1 $O/smoke.log; fatal $rc smoke
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_exact.log 2>&1; rc=$?; grep '^{' $O/bench_exact.log | cut -c1-300; fatal $rc bench
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_exact.log 2>&1; rc=$?; grep '^{' $O/bench_exact.log | cut -c1-300; fatal $rc bench
 timeout -k 10 200 python bench.py --steps 600 --warmup 50 --no-full-run > $O/bench_s600.log 2>&1; rc=$?; grep '^{' $O/bench_s600.log | cut -c1-200; fatal $rc bench600
 timeout -k 10 200 python bench.py --no-full-run --batch-size 8192 --steps 100 --warmup 10 > $O/bench_b8192.log 2>&1; rc=$?; grep '^{' $O/bench_b8192.log | cut -c1-200; fatal $rc bench8192
 cd /tmp && export TMPDIR=/tmp
