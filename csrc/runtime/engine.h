@@ -4,15 +4,18 @@
 // for the GPU: the dataset is HBM resident, every step is a fixed sequence of hand-written kernels
 // (no host work, no sync), and whole chunks of steps are captured once into hipGraphs and replayed.
 //
-// Schedules (set_schedule; C = compute stream, M = comm stream, [k] = device counter sync_[k]):
+// Schedules (set_schedule; C = compute stream, M = comm stream; +NAME / NAME>=NAME = device counters,
+// enum Counter in host_logic.h):
 //   SERIAL   (single GPU, fallback)  C: trunk, fc1, head, fc_bwd, wgrad, dgrad, reduce+update(all)
-//   OVERLAP  (single GPU, default)   C: trunk(hold [1]>=[0]), fc1, head, fc_bwd, wgrad(+[0]),
-//                                       dgrad(+[4]), conv1 reduce+update(hold [3]>=[4])
-//                                    M: (+[3] of the previous step) wait [0]: fc update (hold [4]>=[3]+1),
-//                                       conv2 reduce+update (+[1] at start); chunk end: +[3]
-//   RCCL     (DDP over RCCL)         C: trunk(hold [1]>=[0]), fc1, head, fc_bwd -ev_fc-> wgrad(+[0]),
-//                                       dgrad, conv reduce, (wait ev_done) all-reduce(conv), update(conv)
-//                                    M: (wait ev_fc) all-reduce(fc) -ev_done->, update(fc), +[1]
+//   OVERLAP  (single GPU, default)   C: trunk(hold FC_UPDATES>=WGRAD_STARTS), fc1, head, fc_bwd, wgrad(+WGRAD_STARTS),
+//                                       dgrad(+DGRAD_STARTS), conv1 reduce+update(hold CONV2_UPDATES>=DGRAD_STARTS)
+//                                    M: (+CONV2_UPDATES of the previous step) wait WGRAD_STARTS: fc update
+//                                       (hold DGRAD_STARTS>=CONV2_UPDATES+1), conv2 reduce+update
+//                                       (+FC_UPDATES at start); chunk end: +CONV2_UPDATES
+//   RCCL     (DDP over RCCL)         C: trunk(hold FC_UPDATES>=WGRAD_STARTS), fc1, head, fc_bwd -ev_fc->
+//                                       wgrad(+WGRAD_STARTS), dgrad, conv reduce, (wait ev_done) all-reduce(conv),
+//                                       update(conv)
+//                                    M: (wait ev_fc) all-reduce(fc) -ev_done->, update(fc), +FC_UPDATES
 //                                    one communicator, collectives issued and run in step order fc ->
 //                                    conv (graph edges); the fc update is ordered by the counters
 //                                    (set_rccl_handoff; off: update(fc) before ev_done): one graph per chunk
@@ -20,6 +23,7 @@
 //                                    M: fc all-reduce+update (xgmi_fc_fused), conv2 reduce+all-reduce+
 //                                    update; C: conv1 reduce+all-reduce+update (fuse off: separate
 //                                    all-reduce / update launches, conv bucket after dgrad on C)
+// Which stream runs which fc_bwd role, and what releases the comm chain: plan_step (host_logic.h).
 // OVERLAP and XGMI chunks are captured as two graphs (M chain, C chain) launched concurrently from two
 // host threads (capture_train_split); a chunk's first fork and last join are replay events.
 #pragma once
@@ -36,6 +40,7 @@
 #include <vector>
 
 #include "../include/kernels.h"
+#include "host_logic.h"
 #include "rccl_comm.h"
 #include "xgmi_comm.h"
 
@@ -76,7 +81,8 @@ class Engine {
          hipStream_t comm, int world_size, float rho, float eps, float weight_decay, bool fp32 = false);
   ~Engine();
 
-  enum Schedule : int { SERIAL = 0, OVERLAP = 1, RCCL = 2, XGMI = 3 };
+  using Schedule = mnist::Schedule;   // host_logic.h
+  static constexpr Schedule SERIAL = mnist::SERIAL, OVERLAP = mnist::OVERLAP, RCCL = mnist::RCCL, XGMI = mnist::XGMI;
   void attach_comm(std::shared_ptr<RcclComm> comm);   // RCCL schedule transport (+ parameter broadcast)
   // direct xGMI all-reduce (channels XGMI_CH_CONV / XGMI_CH_FC / XGMI_CH_CONV2 over x->in() -> x->out());
   // while attached the gradient producers write x->in() instead of buf.grad
@@ -85,20 +91,20 @@ class Engine {
   // xGMI: fold the Adadelta steps into the all-reduce kernels (fc: gather phase; conv2 on the comm
   // stream and conv1 on compute: slab reduce + one-shot + update in one launch each).  Off = separate
   // reduce / all-reduce / update launches (the A/B oracle of the fused kernels' bits).
-  void set_xgmi_fuse_update(bool on) { xgmi_fuse_update_ = on; }
-  void set_bucket_split(bool two_buckets) { two_buckets_ = two_buckets; }   // RCCL: 2 buckets or 1
+  void set_xgmi_fuse_update(bool on) { sw_.xgmi_fuse_update = on; }
+  void set_bucket_split(bool two_buckets) { sw_.two_buckets = two_buckets; }   // RCCL: 2 buckets or 1
   // RCCL two-bucket schedule: the fc update after the join, ordered by device-counter holds (needs
   // the compute / comm streams on distinct hardware queues: probe_stream_handoff); off = the update
   // before the join (graph edges only)
-  void set_rccl_handoff(bool on) { rccl_handoff_ = on; }
+  void set_rccl_handoff(bool on) { sw_.rccl_handoff = on; }
   // side schedules: fc_bwd's weight-gradient roles on the comm stream (default on): role A alone for
   // B > 1024 (lean kernel ahead of the split reduce), roles C + A for B <= 1024 in the chained OVERLAP /
   // XGMI schedules (released by fc_bwd's start)
-  void set_fc_dw1_side(bool on) { fc_dw1_side_ = on; }
-  bool fc_dw1_side() const { return fc_dw1_side_; }
+  void set_fc_dw1_side(bool on) { sw_.fc_dw1_side = on; }
+  bool fc_dw1_side() const { return sw_.fc_dw1_side; }
   // test hook: the second w1t copy (fc update beside fc_bwd role B); off reintroduces the race it fixes
-  void set_w1t_pingpong(bool on) { w1t_pingpong_ = on; }
-  bool w1t_pingpong() const { return w1t_pingpong_; }
+  void set_w1t_pingpong(bool on) { sw_.w1t_pingpong = on; }
+  bool w1t_pingpong() const { return sw_.w1t_pingpong; }
   // single-GPU OVERLAP step tail: conv1's reduce + update on 80 one-wave workgroups (1) or as the 20
   // conv1 parts of the 256-thread reduce launch (0); bitwise equal (A/B hook)
   void set_c1_lanes(bool on) { c1_lanes_ = on; }
@@ -153,13 +159,35 @@ class Engine {
   const EngineBuffers& buffers() const { return buf_; }
 
  private:
+  struct ChunkCursor {   // enqueue-time state that carries from step to step inside a chunk
+    bool side_pending = false;   // the previous step's fc update is not joined yet
+    bool side_forked = false;    // comm stream already ordered after this chunk's start
+    bool sig3_pending = false;   // chain: the last conv2 update's CONV2_UPDATES signal is owed
+    bool w2d_in_alt = false;     // the current w2d lives in w2d_alt_
+    bool w1t_in_alt = false;     // the current w1t lives in w1t_alt_
+    bool operator==(const ChunkCursor& o) const { return memcmp(this, &o, sizeof(o)) == 0; }   // five bools, no padding
+  };
+  struct EnqueuePass {   // which stream's launches enqueue_step issues (split capture: one pass per stream)
+    bool main = true, side = true;   // the compute stream's / the comm stream's
+    bool replay_join = false;        // the chunk-end join is an event at replay, not enqueued here
+  };
+  struct StepInput { const uint8_t* data; const int32_t* idx; int stride; const int32_t* labels; };   // a batch's rows
+  struct StepArgs;     // the kernel arguments every schedule tail shares (engine.cpp)
   void enqueue_step(int batch, bool last);
-  void enqueue_step_f32(int batch, bool last);
-  F32Step f32_args() const;
+  void tail_serial(StepArgs& a), tail_rccl(StepArgs& a), tail_chain(StepArgs& a);   // one per schedule
+  void enqueue_step_f32(int batch, bool last, const StepPlan& plan);
+  void fork_comm_once(), end_chunk();
+  StepInput train_input() const;
+  F32Step f32_args(const StepInput& in, StepState* state, float inv_batch) const;
+  AdadeltaArgs adadelta_args() const;
+  AdadeltaArgs held(AdadeltaArgs u, Counter a, Counter b, int delta) const;
+  int* ctr(int c) const { return sync_ + c; }   // device counter (enum Counter)
   bool side_schedule() const { return sched_ == OVERLAP || sched_ == XGMI; }
   bool probe_stream_pair(hipStream_t x, hipStream_t y, double timeout_s);
+  template <class F> hipGraph_t capture_on(hipStream_t s, F&& enqueue);
+  int add_graphs(hipGraph_t side, hipGraph_t main);
   int capture_train_split(int n, int batch);
-  void reset_host_state();
+  void reset_host_state() { cur_ = {}; pass_ = {}; }
   void side_worker(int k);
   void enqueue_eval(int n_total, int batch);
   void alloc_workspace();
@@ -170,27 +198,16 @@ class Engine {
   hipStream_t compute_, comm_stream_;
   int world_;
   float rho_, eps_, wd_;
-  bool two_buckets_ = true;
-  bool rccl_handoff_ = false;
-  bool fc_dw1_side_ = true;
-  bool w1t_pingpong_ = true;
+  StepSwitches sw_;                 // sw_.trace = profile_steps: roctx range + drain per phase
   bool c1_lanes_ = true;
   int idx_stride_ = 0;
   int sched_ = SERIAL;
   std::shared_ptr<RcclComm> comm_;
   std::shared_ptr<XgmiComm> xgmi_;
   float* grad_own_ = nullptr;       // buf_.grad as given (restored when the xGMI comm is detached)
-  bool xgmi_fuse_update_ = true;
-  bool side_pending_ = false;       // the previous step's fc update is not joined yet
-  bool side_forked_ = false;        // comm stream already ordered after this chunk's start
-  bool comm_sig3_pending_ = false;  // OVERLAP chain: the last conv2 update's [3] signal is owed
-  int* sync_ = nullptr;             // [0] wgrad starts (fc grads final), [1] fc updates done, [2] error,
-                                    // [3] conv2 updates done, [4] dgrad starts, [5] fc_bwd starts,
-                                    // [8..11] probe scratch,
-                                    // [12..15] fault-injection hold
-  // split capture: which stream's pass enqueue_step feeds (main = compute, side = comm)
-  bool enq_main_ = true, enq_side_ = true;
-  bool skip_join_ = false;                    // split capture: the chunk-end join is a replay event
+  ChunkCursor cur_;
+  EnqueuePass pass_;
+  int* sync_ = nullptr;             // device counters, read through ctr()
   std::vector<hipGraphExec_t> side_graphs_;   // per graph id: its side-chain graph (split capture) or null
   hipEvent_t ev_fork_ = nullptr;
   // side-graph launcher: the comm stream's graph on its own host thread, concurrently with the compute
@@ -208,15 +225,13 @@ class Engine {
   SideLauncher side_[1];
   void side_start(int k, hipGraphExec_t g, hipStream_t s);
   hipError_t side_wait(int k);
-  bool trace_ = false;              // profile_steps: roctx range + drain per phase
   void phase_begin(const char* name);
   void phase_end();
+  void phase_next(const char* name) { phase_end(), phase_begin(name); }
   float* c1red_ = nullptr;          // conv1 partial group sums (large batches)
   uint16_t* w2d_alt_ = nullptr;     // second dgrad-layout conv2 shadow (conv2 update on the comm stream)
-  bool w2d_in_alt_ = false;         // enqueue-time: the current w2d lives in w2d_alt_
   uint16_t* w1t_alt_ = nullptr;     // second transposed fc1 shadow (side fc weight gradients: the fc
                                     // update of step k runs beside fc_bwd role B, which reads w1t)
-  bool w1t_in_alt_ = false;         // enqueue-time: the current w1t lives in w1t_alt_
   hipEvent_t ev_fc_ = nullptr, ev_done_ = nullptr;
   // workspace
   int64_t ws_bytes_ = 0;

@@ -29,6 +29,70 @@ inline float ddp_head_inv_batch(int batch, int world) {
 }
 constexpr float kDdpEpilogueScale = 1.0f;
 
+// ---------------------------------------------------------------------------- step plan
+enum Schedule : int { SERIAL = 0, OVERLAP = 1, RCCL = 2, XGMI = 3 };   // values exported to Python
+
+// The engine's device counters (ints in the workspace's sync block).  The hand-off counters only
+// ever grow, in matched pairs inside a completed chunk; Engine::reset_counters zeroes them.
+enum Counter : int {
+  WGRAD_STARTS = 0,    // conv2 wgrad launches started: that step's fc gradients are final
+  FC_UPDATES = 1,      // fc updates done
+  HANDOFF_ERR = 2,     // a hand-off wait timed out (Engine::errors)
+  CONV2_UPDATES = 3,   // conv2 updates published
+  DGRAD_STARTS = 4,    // conv2 dgrad launches started: that step's wgrad is done
+  FCBWD_STARTS = 5,    // fc_bwd launches started: that step's head_train is done
+  HANDOFF_COUNTERS = 6,
+  PROBE_SCRATCH = 8,   // probe_stream_pair: a, b, zero, error
+  FAULT_HOLD = 12,     // fault_hold: released, zero, the hold's own timeout flag, spare
+};
+
+struct StepSwitches {   // the engine's set_* switches; trace = inside the profile window
+  bool two_buckets = true, rccl_handoff = false, fc_dw1_side = true, w1t_pingpong = true;
+  bool xgmi_fuse_update = true, trace = false;
+};
+
+// Every schedule decision of one training step; Engine::enqueue_step only reads it.
+struct StepPlan {
+  bool side = false;                 // OVERLAP / XGMI: part of the step runs on the comm stream
+  bool chain = false;                // ... with the hand-offs riding on its update kernels (untraced, fused)
+  bool xgmi_separate = false;        // XGMI with separate all-reduce / update launches (fuse off)
+  bool fc_reduce_side = false;       // B > 1024: the fc split partials are summed on the comm stream
+  bool dw1_side = false;             // ... and fc_bwd role A runs there ahead of that sum
+  bool fcw_side = false, w1t_pp = false;   // chain, B <= 1024: roles C + A there / writing the other w1t copy
+  bool c2r = false;                  // RCCL: conv2's slab reduce on the comm stream under dgrad
+  int roles = FCB_ROLES_ALL;         // fc_bwd roles left in the compute stream's launch
+  bool fc_bwd_reduces = true;        // that launch also sums the split partials
+  bool count_fc_bwd_start = false;   // it counts FCBWD_STARTS (wherever wgrad counts WGRAD_STARTS)
+  Counter release = WGRAD_STARTS;    // what releases the comm chain's first launch of a step
+  int dgrad_full_grid = 0, wt = 0;   // wt: write-through stores at small batches (store16)
+  bool f32_chained = false;          // fp32: the two-stream chained step (else one stream, in order)
+};
+
+inline StepPlan plan_step(Schedule sched, int B, bool fp32, const StepSwitches& sw) {
+  StepPlan p;
+  const bool xg = sched == XGMI, rccl2 = sched == RCCL && sw.two_buckets;
+  p.side = sched == OVERLAP || xg;
+  if (fp32) {   // (the fp32 step reads nothing else)
+    p.f32_chained = p.side || (rccl2 && sw.rccl_handoff && !sw.trace);
+    return p;
+  }
+  // not in the traced profiling window, whose phase syncs would deadlock a hold
+  p.chain = p.side && !sw.trace && (!xg || sw.xgmi_fuse_update);
+  p.xgmi_separate = xg && !sw.xgmi_fuse_update;
+  p.fc_reduce_side = fc_bwd_splits(B) > 1 && (p.side || rccl2);
+  p.dw1_side = p.fc_reduce_side && sw.fc_dw1_side;
+  p.fcw_side = p.chain && fc_bwd_splits(B) == 1 && sw.fc_dw1_side;
+  p.w1t_pp = p.fcw_side && sw.w1t_pingpong;
+  p.c2r = rccl2 && sw.rccl_handoff && !sw.trace;
+  p.roles = p.fcw_side ? FCB_ROLE_B : p.dw1_side ? (FCB_ROLE_C | FCB_ROLE_B) : FCB_ROLES_ALL;
+  p.fc_bwd_reduces = !p.fc_reduce_side;
+  p.count_fc_bwd_start = p.side || rccl2;
+  p.release = p.fcw_side ? FCBWD_STARTS : WGRAD_STARTS;
+  p.dgrad_full_grid = sched == OVERLAP || sched == SERIAL ? 0 : 1;
+  p.wt = B <= WT_MAX_B;
+  return p;
+}
+
 // ---------------------------------------------------------------------------- engine workspace
 struct WorkspaceLayout {
   int64_t a1, p, pmask, z1part, loss_rows, dz1, h_bf, dl_bf, dyc, c1part, w2part, fcpart, sync, w2d_alt, c1red,

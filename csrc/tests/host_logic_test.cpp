@@ -5,7 +5,9 @@
 //     256-B aligned, disjoint, inside the allocation, and large enough for their contents;
 //   * the xGMI record decoder: round trip, and rejection of truncated / oversized / mismatched /
 //     unterminated records, plus random byte soup (must throw, never read out of bounds);
-//   * the residency planner's grid fitting.
+//   * the residency planner's grid fitting;
+//   * the engine's step plan (plan_step) for every schedule, batch class and switch, and the values
+//     of the named device counters.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -142,6 +144,87 @@ static void test_ddp_scale() {
   CHECK(threw);
 }
 
+// plan_step: every schedule decision of the engine's step, against literal expectations
+static void test_plan_step() {
+  const int CB = FCB_ROLE_C | FCB_ROLE_B, ALL = FCB_ROLES_ALL, Bo = FCB_ROLE_B;
+  const int small[] = {200, 1024}, large[] = {1025, 8192}, any[] = {200, 1024, 1025, 8192};
+  const StepSwitches def;
+  auto nothing_on_comm = [](const StepPlan& p) {
+    return !p.fc_reduce_side && !p.dw1_side && !p.fcw_side && !p.chain && !p.c2r && !p.w1t_pp;
+  };
+  StepSwitches one_bucket, one_bucket_handoff, handoff, no_dw1, no_pp, traced, no_fuse, handoff_traced;
+  one_bucket.two_buckets = one_bucket_handoff.two_buckets = false;
+  one_bucket_handoff.rccl_handoff = true;
+  handoff.rccl_handoff = true;
+  no_dw1.fc_dw1_side = false;
+  no_pp.w1t_pingpong = false;
+  traced.trace = true;
+  no_fuse.xgmi_fuse_update = false;
+  handoff_traced.rccl_handoff = handoff_traced.trace = true;
+  for (int B : any) {
+    StepPlan p = plan_step(SERIAL, B, false, def);
+    CHECK(p.roles == ALL && p.fc_bwd_reduces && nothing_on_comm(p) && !p.count_fc_bwd_start && p.dgrad_full_grid == 0);
+    CHECK(!p.side && !p.xgmi_separate);
+    for (const StepSwitches& sw : {one_bucket, one_bucket_handoff}) {
+      p = plan_step(RCCL, B, false, sw);
+      CHECK(nothing_on_comm(p) && p.roles == ALL && p.fc_bwd_reduces && !p.count_fc_bwd_start && !p.side);
+    }
+    CHECK(!plan_step(RCCL, B, false, def).c2r && !plan_step(RCCL, B, false, handoff_traced).c2r);
+    CHECK(plan_step(RCCL, B, false, handoff).c2r);
+    CHECK(plan_step(OVERLAP, B, false, def).wt == (B == 200 || B == 1024 ? 1 : 0));
+  }
+  for (Schedule s : {OVERLAP, XGMI}) {   // XGMI with the fused kernels plans as OVERLAP, on the full dgrad grid
+    const int full = s == XGMI ? 1 : 0;
+    for (int B : small) {
+      StepPlan p = plan_step(s, B, false, def);
+      CHECK(p.side && p.fcw_side && p.roles == Bo && p.w1t_pp && p.chain && p.release == FCBWD_STARTS);
+      CHECK(!p.fc_reduce_side && !p.dw1_side && p.fc_bwd_reduces && p.count_fc_bwd_start && !p.c2r && !p.xgmi_separate);
+      CHECK(p.dgrad_full_grid == full);
+      p = plan_step(s, B, false, no_dw1);
+      CHECK(p.roles == ALL && !p.fcw_side && p.chain && !p.w1t_pp && p.release == WGRAD_STARTS);
+      p = plan_step(s, B, false, no_pp);
+      CHECK(p.fcw_side && !p.w1t_pp && p.roles == Bo);
+      p = plan_step(s, B, false, traced);
+      CHECK(!p.fcw_side && !p.chain && p.roles == ALL && !p.w1t_pp);
+    }
+    for (int B : large) {
+      StepPlan p = plan_step(s, B, false, def);
+      CHECK(p.fc_reduce_side && p.dw1_side && p.roles == CB && !p.fc_bwd_reduces && !p.fcw_side && !p.w1t_pp);
+      CHECK(p.chain && p.release == WGRAD_STARTS && p.dgrad_full_grid == full && p.wt == 0);
+      p = plan_step(s, B, false, no_dw1);
+      CHECK(p.fc_reduce_side && !p.dw1_side && p.roles == ALL && !p.fc_bwd_reduces);
+      p = plan_step(s, B, false, traced);
+      CHECK(p.dw1_side && !p.chain && p.roles == CB);
+    }
+  }
+  StepPlan p = plan_step(XGMI, 200, false, no_fuse);
+  CHECK(!p.fcw_side && !p.chain && p.roles == ALL && p.xgmi_separate && p.side && p.dgrad_full_grid == 1);
+  p = plan_step(XGMI, 1025, false, no_fuse);
+  CHECK(p.dw1_side && p.roles == CB && !p.chain && p.xgmi_separate);
+  for (int B : small) {
+    p = plan_step(RCCL, B, false, handoff);
+    CHECK(p.roles == ALL && p.c2r && p.count_fc_bwd_start && p.dgrad_full_grid == 1 && p.fc_bwd_reduces && !p.side);
+    CHECK(!p.chain && !p.fcw_side && !p.fc_reduce_side && p.release == WGRAD_STARTS);
+  }
+  for (int B : large) {
+    p = plan_step(RCCL, B, false, handoff);
+    CHECK(p.fc_reduce_side && p.dw1_side && p.roles == CB && p.c2r && !p.fc_bwd_reduces && p.count_fc_bwd_start);
+  }
+  for (int B : any) {   // fp32: which schedules run the chained two-stream step
+    CHECK(plan_step(OVERLAP, B, true, def).f32_chained && plan_step(XGMI, B, true, def).f32_chained);
+    CHECK(plan_step(OVERLAP, B, true, traced).f32_chained && plan_step(XGMI, B, true, no_fuse).f32_chained);
+    CHECK(plan_step(RCCL, B, true, handoff).f32_chained);
+    CHECK(!plan_step(RCCL, B, true, def).f32_chained && !plan_step(RCCL, B, true, handoff_traced).f32_chained);
+    CHECK(!plan_step(RCCL, B, true, one_bucket_handoff).f32_chained && !plan_step(SERIAL, B, true, def).f32_chained);
+    CHECK(!plan_step(OVERLAP, B, false, def).f32_chained);
+  }
+  // the counter block: the values the kernels' arguments were built from before the counters had names
+  CHECK(WGRAD_STARTS == 0 && FC_UPDATES == 1 && HANDOFF_ERR == 2 && CONV2_UPDATES == 3 && DGRAD_STARTS == 4);
+  CHECK(FCBWD_STARTS == 5 && HANDOFF_COUNTERS == 6 && PROBE_SCRATCH == 8 && FAULT_HOLD == 12);
+  CHECK((FAULT_HOLD + 4) * (int)sizeof(int) <= 256);   // inside the workspace's sync block (carve(256))
+  CHECK(SERIAL == 0 && OVERLAP == 1 && RCCL == 2 && XGMI == 3);
+}
+
 static void test_fit() {
   int a = 145, b = 309;
   double l = fit_grid_pair(&a, 8, 1024, &b, 39, 1024, 1, 0.5);
@@ -166,6 +249,7 @@ int main() {
   test_records();
   test_fit();
   test_ddp_scale();
+  test_plan_step();
   if (failures) {
     fprintf(stderr, "HOST_LOGIC_TEST FAILED (%d)\n", failures);
     return 1;

@@ -128,6 +128,27 @@ def test_one_wave_conv1_tail_bitwise_equals_reduce_parts(cuda_device, B):
     assert torch.equal(ta.loss_log, tb.loss_log)
 
 
+@pytest.mark.parametrize("B", [200, 1100])
+def test_fc_dw1_side_off_bitwise_equals_default(cuda_device, B):
+    """OVERLAP with hook fc_dw1_side=0 (fc_bwd keeps every role on the compute stream; B <= 1024: the
+    plain lean fc update instead of the one fused into the side weight gradients, no w1t ping-pong;
+    B > 1024: role A stays in fc_bwd's launch) == the default, bit for bit, shadows and gradients
+    included.  Three steps an epoch in chunks of two and one: with the default, the one-step chunk
+    ends on the alternate shadow copies and copies them back."""
+    n = 3 * B
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(17))
+    _, ms_a, ta = _trainer(cuda_device, graph_steps=2, n_train=n, B=B, overlap=True)
+    _, ms_b, tb = _trainer(cuda_device, graph_steps=2, n_train=n, B=B, overlap=True, hooks={"fc_dw1_side": 0})
+    assert ta.engine.fc_dw1_side and not tb.engine.fc_dw1_side
+    for ep in (1, 2):
+        assert ta.train_epoch(ep, idx).steps == 3
+        assert tb.train_epoch(ep, idx).steps == 3
+    torch.cuda.synchronize()
+    for name in ("param", "square_avg", "acc_delta", "grad", "w1", "w1t", "w2f", "w2d"):
+        assert torch.equal(getattr(ms_a, name), getattr(ms_b, name)), name
+    assert torch.equal(ta.loss_log, tb.loss_log)
+
+
 @pytest.mark.parametrize("graph_steps", [0, 2])
 def test_overlap_schedule_large_batch_bitwise_equals_serial(cuda_device, graph_steps):
     """B > 1024: fc_bwd's split partials are summed on the comm stream (ahead of the fc update) in
