@@ -231,6 +231,32 @@ PYBIND11_MODULE(_C, m) {
     check_launch();
   });
 
+  // ---------------- single-launch inference forward ----------------
+  m.attr("INFER_BANDS") = INFER_BANDS;
+  m.def("infer_plan", [](int B) {
+    const InferPlan p = infer_plan(B);
+    py::dict d;
+    d["images_per_wg"] = p.images_per_wg; d["groups"] = p.groups; d["bands"] = p.bands;
+    d["grid"] = py::make_tuple(p.grid_x, p.grid_y);            // (bands, groups)
+    d["workspace_bytes"] = p.workspace_bytes; d["ticket_count"] = p.ticket_count;
+    return d;
+  }, py::arg("B"), "launch geometry and buffer sizes of infer_fwd at batch B (pure; no GPU needed)");
+  m.def("infer_fwd", [](uintptr_t data_u8, uintptr_t idx, uintptr_t xin, uintptr_t labels, uintptr_t w1c,
+                        uintptr_t b1c, uintptr_t w2f, uintptr_t b2c, uintptr_t w1, uintptr_t b_fc1,
+                        uintptr_t w_fc2, uintptr_t b_fc2, uintptr_t z1part, uintptr_t tickets, uintptr_t logp,
+                        uintptr_t pred, uintptr_t loss_rows, uintptr_t correct, int B, uintptr_t stream) {
+    InferArgs a{P<const uint8_t>(data_u8), P<const int32_t>(idx), P<const float>(xin), P<const int32_t>(labels),
+                P<const float>(w1c), P<const float>(b1c), P<const uint16_t>(w2f), P<const float>(b2c),
+                P<const uint16_t>(w1), P<const float>(b_fc1), P<const float>(w_fc2), P<const float>(b_fc2),
+                P<float>(z1part), P<int>(tickets), P<float>(logp), P<int32_t>(pred), P<float>(loss_rows),
+                P<int32_t>(correct)};
+    launch_infer_fwd(a, B, S(stream));
+    check_launch();
+  }, py::arg("data_u8"), py::arg("idx"), py::arg("xin"), py::arg("labels"), py::arg("w1c"), py::arg("b1c"),
+     py::arg("w2f"), py::arg("b2c"), py::arg("w1"), py::arg("b_fc1"), py::arg("w_fc2"), py::arg("b_fc2"),
+     py::arg("z1part"), py::arg("tickets"), py::arg("logp"), py::arg("pred"), py::arg("loss_rows"),
+     py::arg("correct"), py::arg("B"), py::arg("stream"));
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {

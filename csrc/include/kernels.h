@@ -66,6 +66,44 @@ void launch_head_eval(const HeadArgs& a, int B, hipStream_t s);
 // module API forward: log-probs with (train) or without (eval) dropout-2
 void launch_head_fwd(const HeadArgs& a, int B, bool train, hipStream_t s);
 
+// ---------------- inference (infer_fwd.hip) ----------------
+// One launch: B images -> log-probs, argmax (+ per-row NLL / hit with labels).  Grid = (INFER_BANDS,
+// groups): workgroup (band, g) runs the conv trunk for pooled row `band` of the images
+// [g * ipw, min(B, (g + 1) * ipw)), multiplies its [ipw x 768] feature tile (LDS only) by the band's
+// 768 columns of the fc1 weight and writes z1part[band][b][128]; the workgroup of a group that draws
+// the last ticket sums the 12 partials in band order and runs the head.  Nobody waits for anybody.
+constexpr int INFER_BANDS = HP;           // 12 pooled rows = 12 split-K slices of 768 features
+constexpr int INFER_MAX_IPW = 16;         // images per workgroup: the M of one MFMA tile
+constexpr int INFER_FILL_GROUPS = 21;     // groups that fill the device: 21 x 12 bands = 252 workgroups
+constexpr int INFER_MAX_B = 1 << 18;      // 32-bit byte offsets into the partials
+// images per workgroup: 1 while B groups of one image still leave CUs idle, then growing so the grid
+// stays at about one workgroup per CU and the band's w1 slice is re-read once per group
+__host__ __device__ inline int infer_images_per_wg(int B) {
+  const int ipw = (B + INFER_FILL_GROUPS - 1) / INFER_FILL_GROUPS;
+  return ipw < 1 ? 1 : ipw > INFER_MAX_IPW ? INFER_MAX_IPW : ipw;
+}
+struct InferArgs {
+  const uint8_t* data_u8;     // [N][784] raw rows (row b, or row idx[b]), or null with xin
+  const int32_t* idx;         // optional [B] row index into data_u8 (and labels)
+  const float* xin;           // fp32 [B][784] already-normalised input; when set, data_u8 / idx are ignored
+  const int32_t* labels;      // optional: label of data row (idx given) or of batch row b
+  const float* w1c;           // conv1.weight fp32 [32][9]
+  const float* b1c;           // conv1.bias   fp32 [32]
+  const uint16_t* w2f;        // conv2 weight bf16 [64][9][32]
+  const float* b2c;           // conv2.bias   fp32 [64]
+  const uint16_t* w1;         // fc1 weight bf16 [128][9216]
+  const float* b_fc1;         // [128]
+  const float* w_fc2;         // [10][128] fp32
+  const float* b_fc2;         // [10]
+  float* z1part;              // workspace [INFER_BANDS][B][128] fp32: written, never accumulated
+  int* tickets;               // [groups] arrival counters: zero before and after every launch
+  float* logp;                // [B][10]
+  int32_t* pred;              // [B] argmax
+  float* loss_rows;           // optional [B] per-row NLL (needs labels)
+  int32_t* correct;           // optional [B] argmax == label (needs labels)
+};
+void launch_infer_fwd(const InferArgs& a, int B, hipStream_t s);
+
 // ---------------- backward ----------------
 // Compact gradient wrt the conv2 output (the max-pool backward input): one record per (image,
 // pooled position) = 64 bf16 pooled gradients (already dropout-scaled, ReLU-masked) followed by the

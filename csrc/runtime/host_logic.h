@@ -93,6 +93,30 @@ inline StepPlan plan_step(Schedule sched, int B, bool fp32, const StepSwitches& 
   return p;
 }
 
+// ---------------------------------------------------------------------------- inference plan
+// Launch geometry and buffer sizes of the single-launch inference forward (infer_fwd.hip) at batch
+// B: grid = (bands, groups), workgroup (band, g) serving images [g * images_per_wg, ...).  The
+// workspace holds z1part[bands][B][128] fp32, sized for B + 15 rows (>= groups * images_per_wg, and
+// growing with B: a buffer made for max_B serves every B <= max_B); one ticket per group.
+struct InferPlan {
+  int images_per_wg, groups, bands, grid_x, grid_y;
+  int64_t workspace_bytes;
+  int ticket_count;
+};
+
+inline InferPlan infer_plan(int B) {
+  if (B < 1 || B > INFER_MAX_B) throw std::runtime_error("infer_plan: batch size out of range");
+  InferPlan p{};
+  p.images_per_wg = infer_images_per_wg(B);
+  p.groups = (B + p.images_per_wg - 1) / p.images_per_wg;
+  p.bands = INFER_BANDS;
+  p.grid_x = p.bands;
+  p.grid_y = p.groups;
+  p.workspace_bytes = 4LL * INFER_BANDS * NH * ((int64_t)B + INFER_MAX_IPW - 1);
+  p.ticket_count = p.groups;
+  return p;
+}
+
 // ---------------------------------------------------------------------------- engine workspace
 struct WorkspaceLayout {
   int64_t a1, p, pmask, z1part, loss_rows, dz1, h_bf, dl_bf, dyc, c1part, w2part, fcpart, sync, w2d_alt, c1red,

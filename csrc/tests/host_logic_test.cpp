@@ -144,6 +144,30 @@ static void test_ddp_scale() {
   CHECK(threw);
 }
 
+// infer_plan: every image in exactly one group, buffers that cover the grid and grow with B
+static void test_infer_plan() {
+  int64_t last = 0;
+  for (int B = 1; B <= 10000; B = B < 700 ? B + 1 : B + 997) {
+    const InferPlan p = infer_plan(B);
+    CHECK(p.images_per_wg >= 1 && p.images_per_wg <= INFER_MAX_IPW && p.bands == INFER_BANDS);
+    CHECK((int64_t)p.groups * p.images_per_wg >= B && (int64_t)(p.groups - 1) * p.images_per_wg < B);
+    CHECK(p.grid_x == p.bands && p.grid_y == p.groups && p.grid_y <= 65535 && p.ticket_count >= p.groups);
+    CHECK(p.workspace_bytes >= 4LL * p.bands * p.groups * p.images_per_wg * NH && p.workspace_bytes >= last);
+    last = p.workspace_bytes;
+  }
+  CHECK(infer_plan(INFER_MAX_B).grid_y <= 65535);
+  CHECK(4LL * INFER_BANDS * INFER_MAX_B * NH < (1LL << 31));   // 32-bit byte offsets into the partials
+  for (int bad : {0, -1, INFER_MAX_B + 1}) {
+    bool threw = false;
+    try {
+      infer_plan(bad);
+    } catch (const std::runtime_error&) {
+      threw = true;
+    }
+    CHECK(threw);
+  }
+}
+
 // plan_step: every schedule decision of the engine's step, against literal expectations
 static void test_plan_step() {
   const int CB = FCB_ROLE_C | FCB_ROLE_B, ALL = FCB_ROLES_ALL, Bo = FCB_ROLE_B;
@@ -249,6 +273,7 @@ int main() {
   test_records();
   test_fit();
   test_ddp_scale();
+  test_infer_plan();
   test_plan_step();
   if (failures) {
     fprintf(stderr, "HOST_LOGIC_TEST FAILED (%d)\n", failures);

@@ -1,0 +1,179 @@
+"""Inference with a trained ``Net``: ``Predictor`` and the ``mnist_predict.py`` command line.
+
+``Predictor.from_checkpoint("mnist_cnn.pt")`` loads any of the three checkpoint variants the
+reference writes (``utils/checkpoint.py``; weights-only loading); ``Predictor(net)`` wraps a live
+``Net`` and follows its parameters (the bf16 shadows the kernels read are refreshed whenever a
+parameter's version counter moved, as ``Net.forward`` on the GPU does).
+
+Dispatch of one batch of B images:
+
+* GPU, ``dtype="bf16"``, B <= ``INFER_FUSED_MAX_B``: the single-launch fused forward
+  (``csrc/kernels/infer_fwd.hip`` through ``ops.functional.infer_forward``; the constant is 0 as
+  measured, see below);
+* GPU, ``dtype="bf16"``, larger B: the three-launch eval path (``trunk_fwd`` -> ``fc1_fwd`` ->
+  ``head_eval``), as the trainer's per-epoch eval runs it;
+* CPU, or ``dtype="fp32"``: ``Net.forward_reference`` (stock torch ops) in eval mode under ``no_grad``.
+
+There is no fallback between them: a GPU predictor without the native extension raises.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from types import SimpleNamespace
+
+import torch
+import torch.nn.functional as F
+
+from .data.datasets import load_mnist, normalize_u8
+from .models.net import Net
+from .utils.checkpoint import load_state_dict
+from .utils.logging import test_line
+
+# Largest batch the fused single-launch kernel serves; above it the three-launch path runs.  Taken
+# from tools/infer_bench.py's table (profiles/infer/infer_bench.txt, docs/PERF_NOTES.md): as measured,
+# the three-launch path is faster at every batch size, B = 1 included (16.9 against 21.1 us), so the
+# Predictor never dispatches to the fused kernel until that changes.
+INFER_FUSED_MAX_B = 0
+
+
+class Predictor:
+    def __init__(self, net: Net, dtype: str = "bf16"):
+        if dtype not in ("bf16", "fp32"):
+            raise ValueError(f"dtype must be 'bf16' or 'fp32', got {dtype!r}")
+        self.net = net
+        self.dtype = dtype
+        self.device = next(net.parameters()).device
+        self.native = self.device.type == "cuda" and dtype == "bf16"
+        self._infer_buf = None            # ops.functional.InferBuffers (fused path)
+        self._eval_buf = None             # activation set of the three-launch path, one batch size
+        if self.native:
+            from .ops.fused_net import fused_state
+            self._st = fused_state(net)   # owns the ModelState (flat parameters + bf16 shadows)
+
+    @classmethod
+    def from_checkpoint(cls, path: str, device=None, dtype: str = "bf16") -> "Predictor":
+        if device is None:
+            device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+        net = Net()
+        load_state_dict(net, path, map_location="cpu")
+        return cls(net.to(torch.device(device)), dtype=dtype)
+
+    # ------------------------------------------------------------------ public API
+    def log_probs(self, x: torch.Tensor) -> torch.Tensor:
+        """float32 [B, 10] log-probabilities of uint8 [B,28,28] / [B,784] images or float
+        [B,1,28,28] already-normalised input."""
+        return self._forward(x)[0]
+
+    def predict(self, x: torch.Tensor) -> torch.Tensor:
+        """int64 [B] predicted classes."""
+        return self._forward(x)[1]
+
+    def evaluate(self, images_u8: torch.Tensor, labels: torch.Tensor, batch_size: int = 1000):
+        """(loss_sum, correct, n) over uint8 images [N,28,28] / [N,784] and their labels."""
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("evaluate: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("evaluate: batch_size must be positive")
+        if not self.native:
+            loss_sum, correct = 0.0, 0
+            lab = labels.long().to(self.device)
+            for i in range(0, n, batch_size):
+                lp, pred = self._forward(images_u8[i:i + batch_size])
+                loss_sum += F.nll_loss(lp, lab[i:i + batch_size], reduction='sum').item()
+                correct += int((pred == lab[i:i + batch_size]).sum().item())
+            return loss_sum, correct, n
+        u8 = images_u8.reshape(n, 784).contiguous().to(self.device)
+        lab = labels.to(torch.int32).to(self.device)
+        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        hits = torch.zeros((), dtype=torch.int64, device=self.device)
+        for i in range(0, n, batch_size):
+            b = min(batch_size, n - i)
+            out = self._native(b, u8=u8[i:i + b], labels=lab[i:i + b])
+            loss += out.loss_rows[:b].double().sum()
+            hits += out.correct[:b].sum()
+        return float(loss.item()), int(hits.item()), n
+
+    # ------------------------------------------------------------------ dispatch
+    def _forward(self, x: torch.Tensor):
+        B = int(x.shape[0])
+        if x.numel() != B * 784 or B < 1:
+            raise ValueError(f"Predictor expects [B,28,28] / [B,784] / [B,1,28,28] input, got {tuple(x.shape)}")
+        if not self.native:
+            xf = normalize_u8(x.reshape(B, 28, 28)) if x.dtype == torch.uint8 else \
+                x.reshape(B, 1, 28, 28).to(torch.float32)
+            was_training = self.net.training
+            self.net.eval()
+            try:
+                with torch.no_grad():
+                    lp = self.net.forward_reference(xf.to(self.device))
+            finally:
+                self.net.train(was_training)
+            return lp, lp.argmax(dim=1)
+        if x.dtype == torch.uint8:
+            out = self._native(B, u8=x.reshape(B, 784).contiguous().to(self.device))
+        else:
+            out = self._native(B, x=x.reshape(B, 784).to(self.device, torch.float32).contiguous())
+        lp = out.logp[:B].clone()
+        pred = out.pred[:B].long() if out.pred is not None else lp.argmax(dim=1)
+        return lp, pred
+
+    def _native(self, B: int, u8=None, x=None, labels=None):
+        """One batch through the HIP kernels; returns the buffer set holding rows [0, B)."""
+        from .ops import functional as Fk
+        self._st.sync()
+        ms = self._st.ms
+        if B <= INFER_FUSED_MAX_B:
+            if self._infer_buf is None or self._infer_buf.max_B < B:
+                self._infer_buf = Fk.InferBuffers.allocate(max(B, INFER_FUSED_MAX_B), self.device)
+            Fk.infer_forward(ms, self._infer_buf, B, u8=u8, x=x, labels=labels)
+            return self._infer_buf
+        buf = self._eval_buf
+        if buf is None or buf.B != B:
+            z = dict(device=self.device)
+            buf = self._eval_buf = SimpleNamespace(
+                B=B, pred=None,
+                p=torch.zeros(Fk.round_up(B, 64), Fk.NFLAT, dtype=torch.bfloat16, **z),
+                z1part=torch.zeros(ms.C.FC1_KSPLIT, B, Fk.NH, dtype=torch.float32, **z),
+                loss_rows=torch.zeros(B, dtype=torch.float32, **z),
+                correct=torch.zeros(B, dtype=torch.int32, **z),
+                logp=torch.zeros(B, Fk.NCLS, dtype=torch.float32, **z))
+        p, o = Fk.native.ptr, ms.offsets
+        P = p(ms.param)
+        ms.C.trunk_fwd(p(u8), 0, 0, 0, P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], p(ms.w2f),
+                       P + 4 * o["conv2.bias"], 0, p(buf.p), 0, B, False, Fk.native.stream_handle(), xin=p(x))
+        Fk.fc1_fwd(ms, buf)
+        Fk.head_eval(ms, labels, None, buf)
+        return buf
+
+
+# ---------------------------------------------------------------------------- mnist_predict.py
+def build_predict_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Evaluate a saved MNIST checkpoint on the test split")
+    ap.add_argument('--checkpoint', default='mnist_cnn.pt', help='state_dict file written by --save-model')
+    ap.add_argument('--batch-size', type=int, default=1000, metavar='N',
+                    help='images per forward (default: 1000)')
+    ap.add_argument('--no-cuda', action='store_true', default=False, help='run on the CPU')
+    ap.add_argument('--json-log', default=None, help='append the result as one JSON line to this file')
+    ap.add_argument('--data-root', default='./data', help='MNIST root (torchvision layout)')
+    ap.add_argument('--synthetic', action='store_true', default=None,
+                    help='use deterministic synthetic 28x28 data (auto when MNIST files are absent)')
+    ap.add_argument('--synthetic-test-size', type=int, default=None)
+    return ap
+
+
+def predict_main(argv=None) -> int:
+    args = build_predict_parser().parse_args(argv)
+    use_cuda = not args.no_cuda and torch.cuda.is_available()
+    device = torch.device("cuda", 0) if use_cuda else torch.device("cpu")
+    predictor = Predictor.from_checkpoint(args.checkpoint, device=device)
+    data = load_mnist(args.data_root, False, args.synthetic, args.synthetic_test_size)
+    images = data.device_images(device) if use_cuda else data.images
+    loss_sum, correct, n = predictor.evaluate(images, data.targets, args.batch_size)
+    print(test_line(loss_sum / n, correct, n))
+    if args.json_log:
+        with open(args.json_log, "a") as f:
+            f.write(json.dumps({"checkpoint": args.checkpoint, "device": str(device), "source": data.source,
+                                "test_loss": loss_sum / n, "correct": correct, "n": n}) + "\n")
+    return 0

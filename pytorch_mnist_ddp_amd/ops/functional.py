@@ -172,3 +172,65 @@ def dense_dy(buf: StepBuffers) -> torch.Tensor:
         dense[:, :, q >> 1, :, q & 1, :] = torch.where(sel, g, torch.zeros_like(g))
     return dense.view(B, 24, 24, 64)
 
+
+
+# ---------------------------------------------------------------------------- single-launch inference
+@dataclass
+class InferBuffers:
+    """Workspace, tickets and outputs of ``infer_forward`` for any batch size up to ``max_B``.  The
+    tickets are zeroed here, once; every completed launch leaves them zero."""
+    max_B: int
+    z1part: torch.Tensor      # f32 workspace: [INFER_BANDS, B, 128] of the launch's B
+    tickets: torch.Tensor     # i32 [max_B] (a launch uses one per group)
+    logp: torch.Tensor        # f32 [max_B, 10]
+    pred: torch.Tensor        # i32 [max_B]
+    loss_rows: torch.Tensor   # f32 [max_B]
+    correct: torch.Tensor     # i32 [max_B]
+
+    @staticmethod
+    def allocate(max_B: int, device) -> "InferBuffers":
+        plan = _C().infer_plan(max_B)            # workspace_bytes grows with B: max_B's serves every B below
+        z = dict(device=device)
+        return InferBuffers(
+            max_B=max_B,
+            z1part=torch.zeros(plan["workspace_bytes"] // 4, dtype=torch.float32, **z),
+            tickets=torch.zeros(max(max_B, plan["ticket_count"]), dtype=torch.int32, **z),
+            logp=torch.zeros(max_B, NCLS, dtype=torch.float32, **z),
+            pred=torch.zeros(max_B, dtype=torch.int32, **z),
+            loss_rows=torch.zeros(max_B, dtype=torch.float32, **z),
+            correct=torch.zeros(max_B, dtype=torch.int32, **z),
+        )
+
+
+def infer_forward(ms, buf: InferBuffers, B: int, *, u8: torch.Tensor | None = None,
+                  idx: torch.Tensor | None = None, x: torch.Tensor | None = None,
+                  labels: torch.Tensor | None = None) -> None:
+    """Rows [0, B) of ``buf.logp`` / ``buf.pred`` (and ``loss_rows`` / ``correct`` with ``labels``) from
+    exactly one launch on the current stream.  Input: ``u8`` uint8 [N, 784] rows (row b, or row
+    ``idx[b]`` with an int32 ``idx``), or ``x`` float32 [B, 784] already normalised.  ``labels`` int32:
+    one per ``u8`` row when ``idx`` is given, else one per batch row."""
+    if (u8 is None) == (x is None):
+        raise ValueError("infer_forward: pass exactly one of u8 and x")
+    if not 1 <= B <= buf.max_B:
+        raise ValueError(f"infer_forward: B = {B} outside [1, {buf.max_B}]")
+    if x is not None:
+        if idx is not None:
+            raise ValueError("infer_forward: idx applies to u8 rows only")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < B * 784:
+            raise ValueError("infer_forward: x must be contiguous float32 with at least B rows of 784")
+    else:
+        if u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.numel() % 784:
+            raise ValueError("infer_forward: u8 must be contiguous uint8 rows of 784")
+        if idx is None and u8.numel() < B * 784:
+            raise ValueError("infer_forward: u8 has fewer than B rows")
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() < B):
+        raise ValueError("infer_forward: idx must be int32 with at least B entries")
+    if labels is not None and labels.dtype != torch.int32:
+        raise ValueError("infer_forward: labels must be int32")
+    p, o = native.ptr, ms.offsets
+    P = p(ms.param)
+    _C().infer_fwd(p(u8), p(idx), p(x), p(labels), P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], p(ms.w2f),
+                   P + 4 * o["conv2.bias"], p(ms.w1), P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"],
+                   P + 4 * o["fc2.bias"], p(buf.z1part), p(buf.tickets), p(buf.logp), p(buf.pred),
+                   p(buf.loss_rows) if labels is not None else 0, p(buf.correct) if labels is not None else 0,
+                   B, _s())
