@@ -257,6 +257,22 @@ PYBIND11_MODULE(_C, m) {
      py::arg("z1part"), py::arg("tickets"), py::arg("logp"), py::arg("pred"), py::arg("loss_rows"),
      py::arg("correct"), py::arg("B"), py::arg("stream"));
 
+  // ---------------- input gradient (module API / Predictor) ----------------
+  m.def("input_grad_plan", [](int B, int cus) {
+    const InputGradPlan p = input_grad_plan(B, cus);
+    if (p.grid < 1) throw std::runtime_error("input_grad_plan: B and cus must be positive");
+    py::dict d;
+    d["items"] = p.items; d["rounds"] = p.rounds; d["grid"] = p.grid;
+    return d;
+  }, py::arg("B"), py::arg("cus") = 256, "items, rounds and grid of input_grad at batch B (pure; no GPU needed)");
+  m.def("input_grad", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t dx, int B,
+                         uintptr_t stream) {
+    InputGradArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d), P<const float>(w1c),
+                    P<float>(dx)};
+    launch_input_grad(a, B, S(stream));
+    check_launch();
+  }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("dx"), py::arg("B"), py::arg("stream"));
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {
@@ -451,6 +467,7 @@ PYBIND11_MODULE(_C, m) {
     preload_comm();
     preload_xgmi();
     preload_f32();
+    preload_input_grad();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -554,6 +571,7 @@ PYBIND11_MODULE(_C, m) {
     preload_comm();
     preload_xgmi();
     preload_f32();
+    preload_input_grad();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

@@ -197,6 +197,36 @@ void launch_conv_grad_reduce(const ConvBwdArgs& a, int B, hipStream_t s);
 // reduce blocks [lo, hi) only (RED_W2_PARTS conv2 blocks, then the conv1 ones: see RED_ALL_PARTS)
 void launch_conv_grad_reduce_parts(const ConvBwdArgs& a, int B, int lo, int hi, hipStream_t s);
 
+// ---------------- input gradient (input_grad.hip; module API and Predictor only) ----------------
+// dx = d loss / d (normalised input) from what the conv backward reads: the compact dy records, the
+// stored conv1 activations and the two conv weights.  Items = (image, strip of IG_ROWS dx rows);
+// every element of dx [B][784] is written exactly once by a plain store (no pre-zeroing).
+constexpr int IG_ROWS = 7, IG_STRIPS = IMG / IG_ROWS;     // 4 strips of 7 dx rows
+static_assert(IG_ROWS * IG_STRIPS == IMG, "the strips tile the image");
+struct InputGradArgs {
+  const uint8_t* dyc;         // compact un-pooled gradient [B][144] records (see DYC_REC)
+  const uint16_t* a1;         // bf16 [B][26][26][32]
+  const uint16_t* w2d;        // bf16 [9][32][64]
+  const float* w1c;           // conv1.weight fp32 [32][9]
+  float* dx;                  // fp32 [B][784]
+};
+// Persistent grid: at most two workgroups per CU (LDS), each walking items g, g + grid, ...; the
+// item count is spread evenly over the fewest workgroups that keep the round count.
+struct InputGradPlan {
+  int items, rounds, grid;
+};
+inline InputGradPlan input_grad_plan(int B, int cus) {
+  InputGradPlan p{};
+  if (B < 1 || cus < 1) return p;
+  p.items = IG_STRIPS * B;
+  const int cap = 2 * cus;
+  p.rounds = (p.items + cap - 1) / cap;
+  p.grid = (p.items + p.rounds - 1) / p.rounds;
+  return p;
+}
+constexpr int INPUT_GRAD_MAX_B = 1 << 20;   // 32-bit item index
+void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -264,6 +294,7 @@ void preload_adadelta();
 void preload_comm();
 void preload_xgmi();
 void preload_f32();
+void preload_input_grad();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

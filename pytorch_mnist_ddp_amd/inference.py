@@ -14,6 +14,14 @@ Dispatch of one batch of B images:
   ``head_eval``), as the trainer's per-epoch eval runs it;
 * CPU, or ``dtype="fp32"``: ``Net.forward_reference`` (stock torch ops) in eval mode under ``no_grad``.
 
+``Predictor.input_gradient`` (saliency, adversarial examples) returns the gradient of the summed NLL
+wrt the normalised image, in the same inference semantics (no dropout):
+
+* GPU, ``dtype="bf16"``: the fused forward in its training form with dropout switched off by flag,
+  ``head_train`` + ``fc_bwd`` for the dy records, then one launch of ``csrc/kernels/input_grad.hip``
+  (``ops.fused_net.fused_input_gradient``); no conv weight gradient is computed;
+* CPU, or ``dtype="fp32"``: torch autograd over ``Net.forward_reference`` in eval mode.
+
 There is no fallback between them: a GPU predictor without the native extension raises.
 """
 from __future__ import annotations
@@ -95,11 +103,43 @@ class Predictor:
             hits += out.correct[:b].sum()
         return float(loss.item()), int(hits.item()), n
 
+    def input_gradient(self, x: torch.Tensor, labels: torch.Tensor | None = None):
+        """(grad, log_probs): float32 [B,1,28,28] gradient of the summed NLL wrt the NORMALISED input
+        and the float32 [B,10] log-probabilities, without dropout.  The loss is taken against ``labels``
+        ([B] integers), or against the predicted class when ``labels`` is None.  ``x``: uint8
+        [B,28,28] / [B,784] images (normalised first) or float [B,1,28,28] already-normalised input."""
+        B = self._check_input(x)
+        xf = normalize_u8(x.reshape(B, 28, 28)) if x.dtype == torch.uint8 else x.reshape(B, 1, 28, 28)
+        xf = xf.detach().to(self.device, torch.float32).reshape(B, 1, 28, 28)
+        if labels is not None:
+            if labels.numel() != B:
+                raise ValueError(f"input_gradient: {labels.numel()} labels for {B} images")
+            labels = labels.reshape(B).long().to(self.device)
+        if self.native:
+            from .ops.fused_net import fused_input_gradient
+            grad, lp = fused_input_gradient(self.net, xf.reshape(B, 784).contiguous(), labels)
+            return grad.reshape(B, 1, 28, 28), lp
+        xf = xf.clone().requires_grad_()
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.enable_grad():
+                lp = self.net.forward_reference(xf)
+                target = lp.detach().argmax(dim=1) if labels is None else labels
+                grad, = torch.autograd.grad(F.nll_loss(lp, target, reduction='sum'), xf)
+        finally:
+            self.net.train(was_training)
+        return grad, lp.detach()
+
     # ------------------------------------------------------------------ dispatch
-    def _forward(self, x: torch.Tensor):
+    def _check_input(self, x: torch.Tensor) -> int:
         B = int(x.shape[0])
         if x.numel() != B * 784 or B < 1:
             raise ValueError(f"Predictor expects [B,28,28] / [B,784] / [B,1,28,28] input, got {tuple(x.shape)}")
+        return B
+
+    def _forward(self, x: torch.Tensor):
+        B = self._check_input(x)
         if not self.native:
             xf = normalize_u8(x.reshape(B, 28, 28)) if x.dtype == torch.uint8 else \
                 x.reshape(B, 1, 28, 28).to(torch.float32)
@@ -160,6 +200,9 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--synthetic', action='store_true', default=None,
                     help='use deterministic synthetic 28x28 data (auto when MNIST files are absent)')
     ap.add_argument('--synthetic-test-size', type=int, default=None)
+    ap.add_argument('--saliency', default=None, metavar='OUT.npy',
+                    help='also write d NLL / d (normalised image) against the true labels for the evaluated '
+                         'split as a float32 [N,28,28] .npy file (default: off)')
     return ap
 
 
@@ -172,6 +215,14 @@ def predict_main(argv=None) -> int:
     images = data.device_images(device) if use_cuda else data.images
     loss_sum, correct, n = predictor.evaluate(images, data.targets, args.batch_size)
     print(test_line(loss_sum / n, correct, n))
+    if args.saliency:
+        import numpy as np
+        out = np.empty((n, 28, 28), dtype=np.float32)
+        for i in range(0, n, args.batch_size):
+            g, _ = predictor.input_gradient(images[i:i + args.batch_size], data.targets[i:i + args.batch_size])
+            out[i:i + g.shape[0]] = g.reshape(-1, 28, 28).cpu().numpy()
+        with open(args.saliency, "wb") as f:      # (np.save on a name would append ".npy")
+            np.save(f, out)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps({"checkpoint": args.checkpoint, "device": str(device), "source": data.source,

@@ -126,6 +126,21 @@ def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, gra
                   p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s())
 
 
+def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Gradient wrt the normalised input, float32 [B, 784], from one launch of ``input_grad.hip`` on
+    what the conv backward reads (``buf.dyc`` after ``fc_bwd``, ``buf.a1``, the conv weights).  Every
+    element of ``out`` is written; it needs no zeroing."""
+    B = buf.B
+    if out is None:
+        out = torch.empty(B, 784, dtype=torch.float32, device=buf.dyc.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 784 or \
+            out.device != buf.dyc.device:
+        raise ValueError("input_grad: out must be contiguous float32 [B, 784] on the buffers' device")
+    p, o = native.ptr, ms.offsets
+    _C().input_grad(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"], p(out), B, _s())
+    return out.view(B, 784)
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False) -> None:
     p = native.ptr
     _C().adadelta(p(ms.param), p(ms.grad), p(ms.square_avg), p(ms.acc_delta), p(ms.lr), ms.rho, ms.eps,

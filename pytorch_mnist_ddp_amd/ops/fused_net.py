@@ -2,13 +2,18 @@
 
 This is the reference's programming model (mnist_ddp.py:65-73: ``output = model(data);
 loss = F.nll_loss(output, target); loss.backward(); optimizer.step()``) on the hand-written
-kernels, with autograd.  One ``torch.autograd.Function`` covers the whole network:
+kernels, with first-order autograd: every parameter gradient, and - only when the input tensor itself
+requires a gradient - the gradient wrt the input (``x.grad``; saliency, adversarial examples).  No
+double backward.  Two ``torch.autograd.Function`` objects cover the whole network:
 
 forward  = TrunkFunction: trunk_fwd (conv1 -> conv2 MFMA -> ReLU -> max-pool -> dropout-1)
            HeadFunction:  fc1 split-K MFMA -> head_fwd (bias -> ReLU -> dropout-2 -> fc2 -> log_softmax)
 backward = HeadFunction:  head_train (generic log_softmax backward from dlogp) -> fc_bwd
            [fc params' AccumulateGrad -> DDP hooks -> bucket 0 all-reduce launched]
            TrunkFunction: conv_bwd  [conv params' hooks -> bucket 1]
+                          (+ input_grad, one more launch, iff ``x.requires_grad``: the conv backward
+                          never forms the 28x28 gradient; csrc/kernels/input_grad.hip does, from the
+                          same dy records and stored a1.  Without it nothing extra runs or is allocated.)
 Two Functions (not one) so that autograd finalises the fc gradients - and DDP's hooks launch their
 bucket's all-reduce on the comm stream - before conv_bwd is even enqueued (reference DDP overlap,
 mnist_ddp.py:72).
@@ -29,7 +34,7 @@ from __future__ import annotations
 import torch
 
 from . import native
-from .functional import StepBuffers, round_up
+from .functional import StepBuffers, input_grad, round_up
 
 _SEED_MIX = 0x9E3779B97F4A7C15
 
@@ -117,6 +122,7 @@ class TrunkFunction(torch.autograd.Function):
         C = native.load()
         ms = st.ms
         p, o = native.ptr, ms.offsets
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         x = x.reshape(x.shape[0], -1).to(torch.float32).contiguous()
         if x.shape[1] != 784:
             raise ValueError(f"Net expects [B,1,28,28] inputs, got {tuple(x.shape)}")
@@ -144,6 +150,13 @@ class TrunkFunction(torch.autograd.Function):
             raise RuntimeError("fused Net: the trunk backward ran without the head backward")
         p, o = native.ptr, ms.offsets
         P = p(ms.param)
+        dx = None
+        if ctx.needs_input_grad[0]:       # same stream, same inputs as conv_bwd (which writes none of them)
+            dx = input_grad(ms, buf).view(ctx.x_shape).to(ctx.x_dtype)
+        if not any(ctx.needs_input_grad[4:]):      # frozen conv parameters: only the input gradient is wanted
+            st.give(buf)
+            ctx.pas = None
+            return (dx, None, None, None, None, None, None, None)
         C.conv_bwd(p(buf.dyc), p(buf.a1), p(ms.w2d), P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"],
                    0, 0, 0, p(pas.state), p(buf.c1part), p(buf.w2part), p(pas.grad), 1.0, buf.B,
                    native.stream_handle(), xin=p(pas.x))
@@ -151,7 +164,7 @@ class TrunkFunction(torch.autograd.Function):
         grad = pas.grad
         ctx.pas = None
         views = [grad[o[n]:o[n] + t.numel()].view(t.shape) for n, t in _named(ms, _CONV)]
-        return (None, None, None, None, *views)
+        return (dx, None, None, None, *views)
 
 
 class HeadFunction(torch.autograd.Function):
@@ -228,3 +241,26 @@ def fused_net_forward(net, x: torch.Tensor) -> torch.Tensor:
     named = dict(net.named_parameters())
     feat = TrunkFunction.apply(x, st, net.training, flags, *(named[n] for n in _CONV))
     return HeadFunction.apply(feat, st, net.training, *(named[n] for n in _FC))
+
+
+def fused_input_gradient(net, x: torch.Tensor, labels: torch.Tensor | None = None):
+    """(d sum-NLL / d x, log-probs) of float32 ``x`` [B, 784] in inference semantics on the fused
+    kernels: the two Functions in their training form (so a1, pmask and the dy records exist) with
+    STEP_FLAG_NO_DROPOUT, on detached parameters (no parameter gradient is formed past what fc_bwd
+    writes anyway, and conv_bwd is not launched).  ``net.training``, its dropout modules and its dropout
+    counter stream are left as they were.  ``labels`` None: the predicted class."""
+    st = fused_state(net)
+    st.sync()
+    named = dict(net.named_parameters())
+    x = x.detach().requires_grad_()
+    offset = st.rng_offset
+    try:
+        with torch.enable_grad():
+            feat = TrunkFunction.apply(x, st, True, 1, *(named[n].detach() for n in _CONV))
+            logp = HeadFunction.apply(feat, st, True, *(named[n].detach() for n in _FC))
+            target = logp.detach().argmax(dim=1) if labels is None else labels
+            loss = torch.nn.functional.nll_loss(logp, target, reduction='sum')
+            grad, = torch.autograd.grad(loss, x)
+    finally:
+        st.rng_offset = offset            # no dropout was drawn: the training stream continues where it was
+    return grad, logp.detach()
