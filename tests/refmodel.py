@@ -3,10 +3,16 @@
 ``reference_step`` runs the reference forward/backward (mnist_ddp.py:49-72) with stock torch
 ops in fp32 on the CPU, optionally with given dropout masks, and returns loss, log-probs and
 per-parameter gradients.
+
+The second half is the stage-wise forward oracle: one float64 function per forward kernel stage on the
+operands that kernel reads, the comparators (``assert_rounded_bf16``, ``assert_within``,
+``assert_decisions``) and the per-kernel checks built from them, shared by
+tests/test_forward_oracle_cpu.py and tests/test_gpu_forward_stages.py.
 """
 from __future__ import annotations
 
 import copy
+import functools
 
 import torch
 import torch.nn.functional as F
@@ -118,3 +124,318 @@ def emulated_bf16_step(net, images_u8, labels, mask1=None, mask2=None):
     grads["conv1.weight"] = G.conv2d_weight(q(x), d["conv1.weight"].shape, q(da1))
     grads["conv1.bias"] = q(da1).sum((0, 2, 3))
     return loss, lp, grads
+
+
+def keep_mask(seed: int, offset: int, n: int, thr8: int) -> torch.Tensor:
+    """Kernel dropout rule for elements [0, n): one Philox block per 16 elements, byte k of it."""
+    out = torch.empty(n, dtype=torch.float32)
+    for blk in range((n + 15) // 16):
+        w = philox4x32((blk & 0xFFFFFFFF, blk >> 32, offset & 0xFFFFFFFF, offset >> 32),
+                       (seed & 0xFFFFFFFF, seed >> 32))
+        for k in range(min(16, n - 16 * blk)):
+            out[16 * blk + k] = float(((w[k >> 2] >> (8 * (k & 3))) & 0xFF) < thr8)
+    return out
+
+
+def _mulhilo(a: int, b: torch.Tensor):
+    """(hi, lo) 32-bit words of the constant a times the 32-bit values in the int64 tensor b."""
+    t, u = a * (b & 0xFFFF), a * (b >> 16)
+    lo = t + ((u & 0xFFFF) << 16)
+    return (u >> 16) + (lo >> 32), lo & MASK
+
+
+def keep_mask_at(seed: int, offset: int, elems: torch.Tensor, thr8: int, blocks: torch.Tensor | None = None):
+    """``keep_mask`` for the given global element indices (int64 tensor, any shape), vectorised.
+    ``blocks`` overrides the Philox counter block (default ``elems >> 4``) - the CPU test's mutations."""
+    elems = elems.long()
+    blk = elems >> 4 if blocks is None else blocks.long()
+    c0, c1 = blk & MASK, blk >> 32
+    c2, c3 = torch.full_like(blk, offset & MASK), torch.full_like(blk, (offset >> 32) & MASK)
+    k0, k1 = seed & MASK, (seed >> 32) & MASK
+    for _ in range(10):
+        hi0, lo0 = _mulhilo(M0, c0)
+        hi1, lo1 = _mulhilo(M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
+    w = torch.stack([c0, c1, c2, c3], -1)
+    k = elems & 15
+    byte = (w.gather(-1, (k >> 2).unsqueeze(-1)).squeeze(-1) >> (8 * (k & 3))) & 0xFF
+    return (byte < thr8).float()
+
+
+@functools.lru_cache(maxsize=None)
+def trained_net():
+    """The seed-1 ``Net`` after the 32 seeded CPU Adadelta steps of tests/test_gpu_infer.py: an untrained
+    net's rows are almost all near-ties of three classes, so an argmax check on it checks nothing."""
+    from pytorch_mnist_ddp_amd.data.synthetic import generate
+    from pytorch_mnist_ddp_amd.models.net import Net
+    torch.manual_seed(1)
+    net = Net()
+    imgs, labels = generate(1024, seed=11)
+    x, y = normalize_u8(imgs), labels.long()
+    opt = torch.optim.Adadelta(net.parameters(), lr=1.0)
+    net.train()
+    with torch.enable_grad():
+        for step in range(32):
+            i = (step * 64) % 1024
+            opt.zero_grad()
+            F.nll_loss(net.forward_reference(x[i:i + 64]), y[i:i + 64]).backward()
+            opt.step()
+    return net.eval()
+
+
+# ---------------------------------------------------------------- stage-wise forward oracle
+# One function per forward kernel stage, on the operands that stage's kernel reads.  dtype = float64
+# is the oracle; dtype = float32 is "torch's fp32 CPU op on the same operands", which sets each
+# stage's accumulation slack (stage_eps) and builds the CPU test's stand-in for the kernels.
+F64, F32 = torch.float64, torch.float32
+INV_KEEP1_F32 = float(torch.tensor(1.0, dtype=F32) / torch.tensor(0.75, dtype=F32))   # the kernel's 1.0f / KEEP1
+EPS_MARGIN = 8.0            # kernel and torch both accumulate in fp32, in different orders over the same K
+HEAD_ULPS = 16.0            # head outputs: a chain of about ten rounded fp32 operations incl. expf / logf
+CAP = 1e-3                  # largest share of a decision tensor that may sit below the margin
+CHECK_ROWS = (0, 1, 15, 16, 31, 32, 63, 64, 255, 256, 511, 512)
+
+
+def check_rows(B: int) -> list[int]:
+    """Rows the oracle is applied to: all up to B = 64, a fixed subset around the tile edges beyond."""
+    if B <= 64:
+        return list(range(B))
+    return sorted({r for r in CHECK_ROWS + (B - 2, B - 1) if 0 <= r < B})
+
+
+def bf16_round(t: torch.Tensor) -> torch.Tensor:
+    return t.to(F32).to(torch.bfloat16)
+
+
+def stage_conv1(x_norm, w, b, dtype=F64):
+    """relu(conv1) [R,32,26,26] before rounding, from the normalised fp32 input rows [R,784]."""
+    return F.relu(F.conv2d(x_norm.reshape(-1, 1, 28, 28).to(dtype), w.to(dtype), b.to(dtype)))
+
+
+def pool_windows(y):
+    """[R,64,24,24] -> [R,9216,4]: the 2x2 windows in window order 2*dy + dx, flatten order c*144 + y*12 + x."""
+    R = y.shape[0]
+    return y.view(R, 64, 12, 2, 12, 2).permute(0, 1, 2, 4, 3, 5).reshape(R, 9216, 4)
+
+
+def first_strict_max(x):
+    """(max, index) over the last axis with explicit > comparisons in order 0, 1, ...: first maximum wins."""
+    best, code = x[..., 0].clone(), torch.zeros(x.shape[:-1], dtype=torch.long)
+    for k in range(1, x.shape[-1]):
+        m = x[..., k] > best
+        best = torch.where(m, x[..., k], best)
+        code = torch.where(m, torch.full_like(code, k), code)
+    return best, code
+
+
+def stage_conv2_pool(a1_bf16, w2_bf16, b2, keep1=None, dtype=F64):
+    """conv2 on bf16 operands (a1 NCHW [R,32,26,26], w2 [64,32,3,3]) + fp32 bias, ReLU, 2x2 max-pool,
+    dropout-1.  All results [R,9216(,4)] in torch flatten order: ``windows`` (the four pre-ReLU values),
+    ``pooled`` (max of their ReLUs), ``code`` (2*dy + dx of the first strict maximum), ``gap`` (between the
+    two largest window values), ``p`` (pooled x keep x float32(1/0.75) with a keep mask, else unscaled)."""
+    win = pool_windows(F.conv2d(a1_bf16.to(dtype), w2_bf16.to(dtype), b2.to(dtype)))
+    pooled, code = first_strict_max(F.relu(win))
+    top = win.topk(2, -1).values
+    p = pooled if keep1 is None else pooled * keep1.reshape(pooled.shape).to(dtype) * INV_KEEP1_F32
+    return dict(windows=win, pooled=pooled, code=code, gap=top[..., 0] - top[..., 1], p=p)
+
+
+def stage_fc1_partials(p_bf16, w1_bf16, ksplit, dtype=F64):
+    """[ksplit, R, 128]: chunk s = flat features [s*9216/ksplit, (s+1)*9216/ksplit) of p [R,9216] . w1 [128,9216]^T."""
+    R, kc = p_bf16.shape[0], 9216 // ksplit
+    a = p_bf16.to(dtype).view(R, ksplit, kc).permute(1, 0, 2)
+    b = w1_bf16.to(dtype).view(128, ksplit, kc).permute(1, 2, 0)
+    return torch.bmm(a, b)
+
+
+def stage_head(z1part, b_fc1, w_fc2, b_fc2, labels=None, keep2=None, inv_batch=1.0, dtype=F64):
+    """The head on the fc1 partials [ksplit,R,128]: z1 = bias + sum over chunks (in chunk order), h, logits,
+    log-probs and, with labels, the per-row NLL, dl = (softmax - onehot) * inv_batch and dz1 = dh * keep2 * 2 *
+    (z1 > 0) (keep2 None: dropout off, no factor 2)."""
+    s = torch.zeros_like(z1part[0], dtype=dtype)
+    for c in range(z1part.shape[0]):
+        s = s + z1part[c].to(dtype)
+    z1 = b_fc1.to(dtype) + s
+    drop = torch.ones_like(z1) if keep2 is None else keep2.reshape(z1.shape).to(dtype) * 2.0
+    h = F.relu(z1) * drop
+    logits = h @ w_fc2.to(dtype).t() + b_fc2.to(dtype)
+    logp = F.log_softmax(logits, 1)
+    out = dict(z1=z1, h=h, logits=logits, logp=logp)
+    if labels is not None:
+        y = labels.long().view(-1, 1)
+        out["nll"] = -logp.gather(1, y).squeeze(1)
+        out["dl"] = (logp.exp() - F.one_hot(y.squeeze(1), 10).to(dtype)) * inv_batch
+        out["dz1"] = (out["dl"] @ w_fc2.to(dtype)) * drop * (z1 > 0)
+    return out
+
+
+def stage_eps(ref32, ref64, head=False) -> float:
+    """A stage's accumulation slack: EPS_MARGIN x max |torch fp32 CPU op - float64 oracle| on the same
+    operands; for head tensors not below HEAD_ULPS fp32 ulps of the reference's largest magnitude."""
+    eps = EPS_MARGIN * float((ref32.to(F64) - ref64).abs().max())
+    if head:
+        _, e = torch.frexp(ref64.abs().max())
+        eps = max(eps, HEAD_ULPS * 2.0 ** (int(e) - 24))
+    return eps
+
+
+def halfulp_bf16(x64):
+    """Half a bf16 ulp at x: 2^(e-9) with frexp(|x|) = (m in [0.5, 1), e); 0 at 0."""
+    _, e = torch.frexp(x64.abs())
+    return torch.where(x64 == 0, torch.zeros_like(x64), torch.ldexp(torch.ones_like(x64), e - 9))
+
+
+def assert_rounded_bf16(out_bf16, ref64, eps, what="") -> float:
+    """Every element: |out - ref| <= halfulp(ref) + eps - either bf16 neighbour only where ref is within eps
+    of their midpoint; truncation, a one-ulp slip, a NaN or anything larger fails.  No element is excluded.
+    Returns the largest |out - ref| - halfulp(ref) (<= eps; negative: no element needed the slack)."""
+    assert out_bf16.dtype == torch.bfloat16 and out_bf16.shape == ref64.shape, (what, out_bf16.dtype, out_bf16.shape)
+    over = (out_bf16.to(F64) - ref64).abs() - halfulp_bf16(ref64)
+    bad = ~(over <= eps)                      # NaN compares false: an unwritten sentinel fails
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.numel()} elements off the bf16 rounding of the "
+                           f"oracle by more than eps = {eps:.3g}; worst excess {float(over[bad].nan_to_num(1e30).max()):.3g}")
+    return float(over.max())
+
+
+def assert_within(out, ref64, eps, what="") -> float:
+    """Every element within eps absolute of the oracle (fp32 outputs); returns the largest deviation."""
+    assert out.shape == ref64.shape, (what, out.shape, ref64.shape)
+    dev = (out.to(F64) - ref64).abs()
+    bad = ~(dev <= eps)
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.numel()} elements further than eps = {eps:.3g} "
+                           f"from the oracle; worst {float(dev[bad].nan_to_num(1e30).max()):.3g}")
+    return float(dev.max())
+
+
+def assert_decisions(got, ref, margin64, tau, cap=CAP, what="") -> float:
+    """Discrete outputs: got == ref wherever the oracle's margin is >= tau; the share of elements below tau
+    must itself be <= cap (it fails otherwise: the exclusion cannot hide a failure).  Returns that share."""
+    assert got.shape == ref.shape == margin64.shape, (what, got.shape, ref.shape, margin64.shape)
+    firm = margin64 >= tau
+    share = 1.0 - float(firm.double().mean())
+    assert share <= cap, f"{what}: {share:.3g} of the elements have a margin below tau = {tau:.3g} (cap {cap:.3g})"
+    bad = firm & (got != ref)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.numel()} decisions differ at a margin >= tau = {tau:.3g}"
+    return share
+
+
+# ---- the per-kernel checks: the GPU test calls them on the kernels' outputs (copied back), the CPU test
+# on a stand-in built from torch fp32 ops and on its mutations.  Each returns {name: (deviation, eps)}.
+def check_trunk(x_norm, w1c, b1c, w2_bf16, b2, p, a1, pm=None, keep1=None, check_a1=True, name="trunk"):
+    """trunk_fwd on rows x_norm [R,784]: a1 bf16 NHWC [R,26,26,32], p bf16 [R,9216] and, in the train form, the
+    flags pm = pmask_flat [R,9216]; keep1 [R,9216] 0/1 is the oracle's dropout-1 mask (None: dropout off).
+    The eval form stores no a1: it is checked on the a1 that a train-form launch stored for the same images
+    (check_a1=False: that launch's own check covers it).  Rounding the oracle's conv1 instead and excluding
+    the windows that hold an a1 element within eps of a bf16 midpoint excludes 98 % of them (measured, B = 7
+    and 257: a window reads 512 a1 elements), so that form of the check decides nothing."""
+    stats = {}
+    c1 = stage_conv1(x_norm, w1c, b1c)
+    eps1 = stage_eps(stage_conv1(x_norm, w1c, b1c, F32), c1)
+    a1n = a1.permute(0, 3, 1, 2)
+    if check_a1:
+        stats["a1"] = (assert_rounded_bf16(a1n, c1, eps1, f"{name} a1"), eps1)
+    ref = stage_conv2_pool(a1n, w2_bf16, b2, keep1)
+    eps2 = stage_eps(stage_conv2_pool(a1n, w2_bf16, b2, keep1, F32)["windows"], ref["windows"])
+    eps_p = eps2 * (INV_KEEP1_F32 if keep1 is not None else 1.0)
+    if pm is not None:
+        pm = pm.long()
+        assert (pm >> 4 == 0).all(), f"{name}: pmask bits above bit 3"
+        want = torch.ones_like(pm) if keep1 is None else keep1.reshape(pm.shape).long()
+        assert torch.equal((pm >> 2) & 1, want), f"{name}: keep bits differ from Philox"
+    stats["p"] = (assert_rounded_bf16(p, ref["p"], eps_p, f"{name} p"), eps_p)
+    if keep1 is not None:
+        assert (p[keep1.reshape(p.shape) == 0].to(F32) == 0).all(), f"{name}: p is not 0 where dropout-1 drops"
+    if pm is not None:
+        tau = eps2
+        top = ref["windows"].amax(-1)
+        inf = torch.full_like(top, float("inf"))
+        # all four <= -tau: code 0 and bit 3 clear for certain; else the code holds while both the gap to
+        # the runner-up and the distance of the maximum from 0 (below it every ReLU is 0: code 0) are >= tau
+        m_code = torch.where(top <= -tau, inf, torch.minimum(ref["gap"], top.abs()))
+        stats["argmax_excluded"] = (assert_decisions(pm & 3, ref["code"], m_code, tau, CAP, f"{name} argmax code"), CAP)
+        stats["pos_excluded"] = (assert_decisions((pm >> 3) & 1, (ref["pooled"] > 0).long(), top.abs(), tau, CAP,
+                                                  f"{name} pooled > 0 bit"), CAP)
+    return stats
+
+
+def check_fc1(p, w1_bf16, z1part, ksplit, name="fc1"):
+    """fc1_fwd: z1part f32 [ksplit,R,128] from p bf16 [R,9216]."""
+    ref = stage_fc1_partials(p, w1_bf16, ksplit)
+    eps = stage_eps(stage_fc1_partials(p, w1_bf16, ksplit, F32), ref)
+    return {"z1part": (assert_within(z1part, ref, eps, f"{name} z1part"), eps)}
+
+
+def _head_refs(z1part, hp, labels, keep2, inv_batch):
+    args = (z1part, hp["fc1.bias"], hp["fc2.weight"], hp["fc2.bias"], labels, keep2, inv_batch)
+    return stage_head(*args), stage_head(*args, dtype=F32)
+
+
+def check_head_train(z1part, hp, labels, keep2, inv_batch, loss_rows, h_bf, dz1, dl_bf, name="head_train"):
+    """head_train rows: z1part [ksplit,R,128], hp the fp32 head parameters by name, labels [R]; outputs
+    loss_rows f32 [R], h_bf / dz1 bf16 [R,128], dl_bf bf16 [R,16].  Each tensor's eps comes from that tensor's
+    own fp32-vs-float64 deviation, so it carries the dropout factor 2 and inv_batch by itself."""
+    r64, r32 = _head_refs(z1part, hp, labels, keep2, inv_batch)
+    e = {k: stage_eps(r32[k], r64[k], head=True) for k in ("z1", "h", "nll", "dl", "dz1")}
+    stats = {"loss_rows": (assert_within(loss_rows, r64["nll"], e["nll"], f"{name} loss_rows"), e["nll"]),
+             "h_bf": (assert_rounded_bf16(h_bf, r64["h"], e["h"], f"{name} h_bf"), e["h"]),
+             "dz1": (assert_rounded_bf16(dz1, r64["dz1"], e["dz1"], f"{name} dz1"), e["dz1"]),
+             "dl_bf": (assert_rounded_bf16(dl_bf[:, :10], r64["dl"], e["dl"], f"{name} dl_bf"), e["dl"])}
+    assert (dl_bf[:, 10:].to(F32) == 0).all(), f"{name}: dl_bf columns 10..15 are not 0"
+    live = torch.ones_like(r64["z1"], dtype=torch.bool) if keep2 is None else keep2.reshape(r64["z1"].shape) > 0
+    assert (dz1[~live].to(F32) == 0).all() and (h_bf[~live].to(F32) == 0).all(), f"{name}: not 0 where dropout-2 drops"
+    # zero pattern of dz1 among the kept units: 0 <=> z1 <= 0, decided wherever |z1| >= tau
+    stats["dz1_zero_excluded"] = (assert_decisions((dz1.to(F32) == 0)[live], (r64["z1"] <= 0)[live],
+                                                   r64["z1"].abs()[live], e["z1"], CAP, f"{name} dz1 zero pattern"), CAP)
+    return stats
+
+
+def check_head_padding(B, dz1, h_bf, dl_bf, sentinel_bits, name="head_train"):
+    """Whole buffers [round_up(B,64), .]: rows [B, round_up(B,32)) exactly 0, rows above keep the sentinel."""
+    Bp = (B + 31) // 32 * 32
+    for t, nm in ((dz1, "dz1"), (h_bf, "h_bf"), (dl_bf, "dl_bf")):
+        bits = t.view(torch.int16)
+        assert (bits[B:Bp] == 0).all(), f"{name}: {nm} padding rows [{B}, {Bp}) are not 0"
+        assert (bits[Bp:] == sentinel_bits).all(), f"{name}: {nm} rows from {Bp} were written"
+
+
+def check_head_logp(z1part, hp, logp, keep2=None, labels=None, loss_rows=None, correct=None, name="head_eval"):
+    """head_eval / head_fwd rows: logp f32 [R,10] (+ loss_rows f32 [R], correct i32 [R] with labels)."""
+    r64, r32 = _head_refs(z1part, hp, labels, keep2, 1.0)
+    eps = stage_eps(r32["logp"], r64["logp"], head=True)
+    stats = {"logp": (assert_within(logp, r64["logp"], eps, f"{name} logp"), eps)}
+    top = r64["logp"].topk(2, 1).values
+    margin = top[:, 0] - top[:, 1]
+    _, am = first_strict_max(r64["logp"])
+    stats["argmax_excluded"] = (assert_decisions(first_strict_max(logp.to(F64))[1], am, margin, eps, CAP,
+                                                 f"{name} argmax"), CAP)
+    if labels is not None:
+        e_nll = stage_eps(r32["nll"], r64["nll"], head=True)
+        stats["loss_rows"] = (assert_within(loss_rows, r64["nll"], e_nll, f"{name} loss_rows"), e_nll)
+        assert_decisions(correct.long(), (am == labels.long()).long(), margin, eps, CAP, f"{name} correct")
+    return stats
+
+
+
+# ---- the inputs of the stage-wise forward tests (tests/test_forward_oracle_cpu.py, test_gpu_forward_stages.py)
+FWD_STEP, FWD_SEED, FWD_RNG_BASE = 3, 0x1234ABCD5678, 2 ** 33 + 1000   # both counter / key words non-trivial
+TRUNK_B, FC1_B, HEAD_B, EVAL_B = (1, 7, 33, 257, 1025), (1, 7, 33, 511, 512, 513, 1025), (1, 7, 33, 511, 512, 513), (7, 513)
+
+
+def fc1_ksplit(B: int) -> int:
+    return 4 if B >= 512 else 32
+
+
+@functools.lru_cache(maxsize=None)
+def forward_case(B: int, data_seed: int = 5):
+    """A dataset of 4B + 5 synthetic rows and a random permutation over it; with idx_stride = B, row b of
+    step s reads idx[s*B + b].  Returns (images u8 [N,28,28], labels i64 [N], idx i64 [N])."""
+    from pytorch_mnist_ddp_amd.data.synthetic import generate
+    imgs, labels = generate(4 * B + 5, seed=data_seed)
+    idx = torch.randperm(4 * B + 5, generator=torch.Generator().manual_seed(100 + B))
+    return imgs, labels, idx
+
+
+def keep_rows(offset: int, rows, width: int, thr8: int) -> torch.Tensor:
+    """The keep mask [len(rows), width] of batch rows ``rows`` (global element index row*width + i)."""
+    elems = torch.as_tensor(rows).long().view(-1, 1) * width + torch.arange(width)
+    return keep_mask_at(FWD_SEED, offset, elems, thr8)

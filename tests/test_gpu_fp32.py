@@ -20,7 +20,7 @@ from pytorch_mnist_ddp_amd.engine.state import ModelState
 from pytorch_mnist_ddp_amd.engine.trainer import FusedTrainer
 from pytorch_mnist_ddp_amd.models.net import Net
 
-from refmodel import philox4x32, reference_forward, reference_step, rel_err
+from refmodel import keep_mask as _keep_mask, reference_forward, reference_step, rel_err
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,17 +38,6 @@ def _trainer(dev, B, n_train, dropout, graph_steps=0, seed=1, n_test=0, overlap=
     assert t.fp32 and t.engine.fp32
     assert t.engine.schedule == (t.C.SCHED_OVERLAP if overlap else t.C.SCHED_SERIAL)
     return ref, ms, t, tr, te
-
-
-def _keep_mask(seed: int, offset: int, n: int, thr8: int) -> torch.Tensor:
-    """Kernel dropout rule for elements [0, n): one Philox block per 16 elements, byte k of it."""
-    out = torch.empty(n, dtype=torch.float32)
-    for blk in range((n + 15) // 16):
-        w = philox4x32((blk & 0xFFFFFFFF, blk >> 32, offset & 0xFFFFFFFF, offset >> 32),
-                       (seed & 0xFFFFFFFF, seed >> 32))
-        for k in range(min(16, n - 16 * blk)):
-            out[16 * blk + k] = float(((w[k >> 2] >> (8 * (k & 3))) & 0xFF) < thr8)
-    return out
 
 
 @pytest.mark.parametrize("B,dropout", [(64, False), (200, False), (1100, False), (32, True)])
