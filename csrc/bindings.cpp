@@ -197,6 +197,7 @@ PYBIND11_MODULE(_C, m) {
     else if (role == 4) launch_fc_bwd(a, B, Bp, S(stream), false, FCB_ROLE_C | FCB_ROLE_B);   // B > 1024
     else if (role == 5) launch_fc_bwd(a, B, Bp, S(stream), false, FCB_ROLE_C | FCB_ROLE_A);   // weight grads
     else if (role == 6) launch_fc_bwd(a, B, Bp, S(stream), false, FCB_ROLE_B);
+    else if (role == 7) launch_fc_grad_reduce(a, B, S(stream));                  // B > 1024: the partials' sum alone
     else launch_fc_bwd_role(a, B, Bp, role, S(stream));
     check_launch();
   }, py::arg("dz1"), py::arg("p"), py::arg("pmask"), py::arg("w1t"), py::arg("h_bf"), py::arg("dl_bf"),
@@ -208,18 +209,24 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_bwd", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t b1c,
                        uintptr_t data_u8, uintptr_t idx, int64_t idx_stride, uintptr_t state, uintptr_t c1part,
                        uintptr_t w2part, uintptr_t grad, float grad_scale, int B, uintptr_t stream,
-                       uintptr_t xin) {
+                       uintptr_t xin, int stages, uintptr_t c1red) {
     ConvBwdArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d),
                   P<const float>(w1c), P<const float>(b1c), P<const uint8_t>(data_u8), P<const int32_t>(idx),
                   idx_stride, P<const StepState>(state), P<float>(c1part), P<float>(w2part), P<float>(grad),
                   grad_scale, conv_wgrad_groups(B), P<const float>(xin)};
     a.c1_rows = conv_dgrad_c1_rows(B);
-    launch_conv_bwd(a, B, S(stream));
-    launch_conv_grad_reduce(a, B, S(stream));
+    a.c1red = P<float>(c1red);
+    // stages: 1 = dgrad (+ the conv1 pre-reduce with c1red), 2 = wgrad, 4 = reduce (reads c1red when given)
+    if (stages <= 0 || stages > 7) throw std::runtime_error("conv_bwd: bad stage mask");
+    if (stages & 1) launch_conv_dgrad(a, B, S(stream));
+    if (stages & 2) launch_conv_wgrad(a, B, S(stream));
+    if (stages & 4) launch_conv_grad_reduce(a, B, S(stream));
     check_launch();
   }, py::arg("dy"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("b1c"), py::arg("data_u8"), py::arg("idx"),
      py::arg("idx_stride"), py::arg("state"), py::arg("c1part"), py::arg("w2part"), py::arg("grad"),
-     py::arg("grad_scale"), py::arg("B"), py::arg("stream"), py::arg("xin") = 0);
+     py::arg("grad_scale"), py::arg("B"), py::arg("stream"), py::arg("xin") = 0, py::arg("stages") = 7,
+     py::arg("c1red") = 0);
+  m.attr("C1_PRE_SLABS") = C1_PRE_SLABS;
   m.def("adadelta", [](uintptr_t param, uintptr_t grad, uintptr_t sq, uintptr_t acc, uintptr_t lr, float rho,
                        float eps, float wd, uintptr_t w2f, uintptr_t w2d, uintptr_t w1, uintptr_t w1t,
                        uintptr_t state_inc, int region, bool update, uintptr_t stream) {

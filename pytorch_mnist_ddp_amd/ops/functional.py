@@ -110,20 +110,33 @@ def head_eval(ms, labels: torch.Tensor | None, idx: torch.Tensor | None, buf: St
                    p(buf.logp), buf.B, _s())
 
 
-def fc_bwd(ms, buf: StepBuffers, grad_scale: float = 1.0, loss_log: torch.Tensor | None = None) -> None:
+# fc_bwd launches other than the whole step's (role = -1): one workgroup role of the kernel, the lean
+# fc1 weight-gradient kernel, the role pairs the side schedules launch (B > 1024: split partials, no
+# reduce) and fc_grad_reduce alone
+FC_ROLE_C, FC_ROLE_A, FC_ROLE_B, FC_DW1, FC_ROLES_CB, FC_ROLES_CA, FC_ROLES_B, FC_REDUCE = range(8)
+CONV_DGRAD, CONV_WGRAD, CONV_REDUCE, CONV_ALL = 1, 2, 4, 7      # conv_bwd stage mask
+
+
+def fc_bwd(ms, buf: StepBuffers, grad_scale: float = 1.0, loss_log: torch.Tensor | None = None,
+           role: int = -1) -> None:
     p = native.ptr
     B = buf.B
     _C().fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), p(ms.w1t), p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
                 p(ms.state), p(ms.grad), p(buf.dyc), p(loss_log), grad_scale, 1.0 / B, B, round_up(B, 32), _s(),
-                part=p(buf.fcpart))
+                role=role, part=p(buf.fcpart))
 
 
 def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, grad_scale: float = 1.0,
-             idx_stride: int = 0) -> None:
+             idx_stride: int = 0, stages: int = CONV_ALL, xin: torch.Tensor | None = None,
+             c1red: torch.Tensor | None = None) -> None:
+    """conv2 dgrad (+ conv1 weight-gradient partials), conv2 wgrad and the partials' reduce; ``stages``
+    selects the launches.  ``xin`` (fp32 [B,784]) replaces the dataset rows; with ``c1red`` (f32
+    [C1_PRE_SLABS, 320]) the dgrad stage also pre-reduces the conv1 partials and the reduce reads those."""
     p, o = native.ptr, ms.offsets
     _C().conv_bwd(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"],
                   p(ms.param) + 4 * o["conv1.bias"], p(data_u8), p(idx), idx_stride, p(ms.state),
-                  p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s())
+                  p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s(), xin=p(xin), stages=stages,
+                  c1red=p(c1red))
 
 
 def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.Tensor:

@@ -7,7 +7,8 @@ per-parameter gradients.
 The second half is the stage-wise forward oracle: one float64 function per forward kernel stage on the
 operands that kernel reads, the comparators (``assert_rounded_bf16``, ``assert_within``,
 ``assert_decisions``) and the per-kernel checks built from them, shared by
-tests/test_forward_oracle_cpu.py and tests/test_gpu_forward_stages.py.
+tests/test_forward_oracle_cpu.py and tests/test_gpu_forward_stages.py.  The last part is the same for the
+backward kernels (tests/test_backward_oracle_cpu.py, tests/test_gpu_backward_stages.py).
 """
 from __future__ import annotations
 
@@ -439,3 +440,335 @@ def keep_rows(offset: int, rows, width: int, thr8: int) -> torch.Tensor:
     """The keep mask [len(rows), width] of batch rows ``rows`` (global element index row*width + i)."""
     elems = torch.as_tensor(rows).long().view(-1, 1) * width + torch.arange(width)
     return keep_mask_at(FWD_SEED, offset, elems, thr8)
+
+
+# ---------------------------------------------------------------- stage-wise backward oracle
+# One function per backward kernel stage on the operands that kernel reads (csrc/include/kernels.h
+# FcBwdArgs / ConvBwdArgs), dtype = F32 the torch-fp32 twin that sets stage_eps; layout helpers for the
+# compact dy records, the conv2 partial slabs and the conv1 partial rows; the per-kernel checks, shared by
+# tests/test_backward_oracle_cpu.py and tests/test_gpu_backward_stages.py.
+FC_SPLIT_ROWS = 1024                          # kernels.h FC_BWD_SPLIT_ROWS
+FC_NAMES = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+CONV_NAMES = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias")
+FCB_PART = {"fc1.weight": (0, (128, 9216)), "fc1.bias": (128 * 9216, (128,)),
+            "fc2.weight": (128 * 9216 + 128, (10, 128)), "fc2.bias": (128 * 9216 + 128 + 1280, (10,)),
+            "loss": (128 * 9216 + 128 + 1280 + 10, ())}        # kernels.h FCB_PART_*
+C1_PRE_SLABS = 256
+
+
+def fc_splits(B: int) -> int:
+    return (B + FC_SPLIT_ROWS - 1) // FC_SPLIT_ROWS
+
+
+def conv_wgrad_groups(B: int) -> int:
+    return min(256, (24 * B + 7) // 8)
+
+
+def stage_fc_wgrads(dz1_bf16, p_bf16, h_bf16, dl_bf16, grad_scale=1.0, loss_rows=None, dtype=F64):
+    """fc_bwd roles A and C (+ fc_grad_reduce) on rows [0, B) of dz1 / h [.,128], p [.,9216], dl [.,16]
+    (B = len(loss_rows) if given, else p's rows): the four fc gradients x grad_scale, ``loss`` = mean of
+    loss_rows, and ``parts``: per split s the unscaled sums over rows [1024 s, 1024 (s + 1)) and the split's
+    loss sum - the FCB_PART_* partials when B > 1024; the gradients are the parts added in split order."""
+    B = p_bf16.shape[0] if loss_rows is None else loss_rows.shape[0]
+    parts = []
+    for s in range(fc_splits(B)):
+        r = slice(FC_SPLIT_ROWS * s, min(B, FC_SPLIT_ROWS * (s + 1)))
+        z, d = dz1_bf16[r].to(dtype), dl_bf16[r, :10].to(dtype)
+        part = {"fc1.weight": z.t() @ p_bf16[r].to(dtype), "fc1.bias": z.sum(0),
+                "fc2.weight": d.t() @ h_bf16[r].to(dtype), "fc2.bias": d.sum(0)}
+        if loss_rows is not None:
+            part["loss"] = loss_rows[r].to(dtype).sum()
+        parts.append(part)
+    out = {"parts": parts}
+    sc = torch.tensor(grad_scale, dtype=F32).to(dtype)
+    for k in parts[0]:
+        t = parts[0][k]
+        for q in parts[1:]:
+            t = t + q[k]
+        out[k] = t * sc if k != "loss" else t / torch.tensor(float(B), dtype=dtype)
+    return out
+
+
+def stage_fc_dgrad(dz1_bf16, w1_bf16, pmask, no_dropout=False, dtype=F64):
+    """fc_bwd role B on rows dz1 [R,128], w1 [128,9216], pmask flags [R,9216] (torch flatten order):
+    ``g`` = the 64 x 144 pooled gradients per image before rounding, 0 unless (pm & 12) == 12 and scaled by
+    float32(1/0.75) unless no_dropout; ``code`` = pm & 3 (copied into the records); ``live``."""
+    pm = pmask.long()
+    live = (pm & 12) == 12
+    g = dz1_bf16.to(dtype) @ w1_bf16.to(dtype)
+    if not no_dropout:
+        g = g * torch.tensor(INV_KEEP1_F32, dtype=dtype)
+    return dict(g=torch.where(live, g, torch.zeros_like(g)), code=pm & 3, live=live)
+
+
+def route_planes(code):
+    """[..., 64] codes 0..3 -> [..., 16] uint8 bit planes (the inverse of functional.route_codes)."""
+    c = code.long().reshape(*code.shape[:-1], 8, 8)
+    w = 1 << torch.arange(8)
+    pl = torch.stack([((c & 1) * w).sum(-1), ((c >> 1) * w).sum(-1)], -1)
+    return pl.reshape(*code.shape[:-1], 16).to(torch.uint8)
+
+
+def dyc_pack(g_bf16, code):
+    """[R,9216] bf16 gradients + codes (flatten order c*144 + pos) -> the u8 records [R, 144*144]."""
+    n = g_bf16.shape[0]
+    gb = g_bf16.view(n, 64, 144).permute(0, 2, 1).contiguous().view(torch.uint8)        # [R,144,128]
+    pl = route_planes(code.view(n, 64, 144).permute(0, 2, 1))
+    return torch.cat([gb, pl], -1).reshape(n, 144 * 144)
+
+
+def dyc_unpack(rec):
+    """The inverse: (g bf16 [R,9216], code i64 [R,9216]) in flatten order."""
+    from pytorch_mnist_ddp_amd.ops.functional import route_codes
+    n = rec.shape[0]
+    rec = rec.view(n, 144, 144)
+    g = rec[..., :128].contiguous().view(torch.bfloat16)
+    return g.permute(0, 2, 1).reshape(n, 9216), route_codes(rec[..., 128:]).permute(0, 2, 1).reshape(n, 9216)
+
+
+def dense_dy(g_bf16, code):
+    """[R,64,24,24] bf16: dy[., c, 2 py + i, 2 px + j] = g where code == 2 i + j, else 0."""
+    n = g_bf16.shape[0]
+    g4, c4 = g_bf16.view(n, 64, 12, 12), code.view(n, 64, 12, 12)
+    d = torch.zeros(n, 64, 12, 2, 12, 2, dtype=torch.bfloat16)
+    for q in range(4):
+        d[:, :, :, q >> 1, :, q & 1] = torch.where(c4 == q, g4, torch.zeros_like(g4))
+    return d.view(n, 64, 24, 24)
+
+
+def stage_conv2_wgrad(a1_bf16, dy_bf16, G=None, taps_transposed=False, drop_last_row_of=None, dtype=F64):
+    """conv2_wgrad (either form) on a1 NCHW [B,32,26,26] and dense dy [B,64,24,24]: the per-group partials
+    ``w`` [G,64,32,3,3] and ``b`` [G,64] - group g owns the rows [g 24B / G, (g + 1) 24B / G) of the batch's 24B dy
+    rows (conv_bwd.hip r0 / r1 of both wgrad kernels) - and their sums ``conv2.weight`` / ``conv2.bias``.
+    The two keyword mutations are the CPU test's."""
+    B = dy_bf16.shape[0]
+    G = conv_wgrad_groups(B) if G is None else G
+    rows = 24 * B
+    w, b = torch.zeros(G, 64, 288, dtype=dtype), torch.zeros(G, 64, dtype=dtype)
+    for g in range(G):
+        r0, r1 = g * rows // G, (g + 1) * rows // G
+        if drop_last_row_of == g:
+            r1 -= 1
+        if r1 <= r0:
+            continue
+        b0, b1 = r0 // 24, (r1 - 1) // 24 + 1
+        cols = F.unfold(a1_bf16[b0:b1].to(dtype), 3).permute(0, 2, 1).reshape(-1, 288)        # [px, ci*9 + tap]
+        d = dy_bf16[b0:b1].to(dtype).permute(0, 2, 3, 1).reshape(-1, 64)
+        px = slice((r0 - 24 * b0) * 24, (r1 - 24 * b0) * 24)
+        w[g], b[g] = d[px].t() @ cols[px], d[px].sum(0)
+    w = w.view(G, 64, 32, 3, 3)
+    if taps_transposed:
+        w = w.transpose(3, 4).contiguous()
+    return {"w": w, "b": b, "conv2.weight": w.sum(0), "conv2.bias": b.sum(0)}
+
+
+@functools.lru_cache(maxsize=None)
+def _w2part_index():
+    """Flat conv2.weight index co*288 + ci*9 + tap of slab element e < 18432 (conv_grad_reduce.h)."""
+    e = torch.arange(18432)
+    tile, ln, r = e >> 8, (e >> 2) & 63, e & 3
+    mt, nt = tile // 18, tile % 18
+    return (16 * mt + 4 * (ln >> 4) + r) * 288 + (16 * (nt & 1) + (ln & 15)) * 9 + (nt >> 1)
+
+
+def w2part_unpack(slabs):
+    """[G,18496] slabs -> (w [G,64,32,3,3], b [G,64])."""
+    G = slabs.shape[0]
+    w = torch.empty(G, 18432, dtype=slabs.dtype)
+    w[:, _w2part_index()] = slabs[:, :18432]
+    return w.view(G, 64, 32, 3, 3), slabs[:, 18432:18496]
+
+
+def w2part_pack(w, b):
+    return torch.cat([w.reshape(w.shape[0], 18432)[:, _w2part_index()], b], 1).contiguous()
+
+
+def strip_rows(s: int):
+    """conv1-output rows of dgrad strip s: 7, 7, 7, 5."""
+    return 7 * s, min(26, 7 * s + 7)
+
+
+def _c1_strip_sums(xcols, d):
+    """[B,9,676] input taps, [B,32,676] per-pixel values -> [4B,320] rows (image, strip) x (ci*10 + tap | 9)."""
+    B = d.shape[0]
+    out = torch.zeros(B, 4, 32, 10, dtype=d.dtype)
+    for s in range(4):
+        y0, y1 = strip_rows(s)
+        px = slice(26 * y0, 26 * y1)
+        out[:, s, :, :9] = torch.einsum("bcp,btp->bct", d[:, :, px], xcols[:, :, px])
+        out[:, s, :, 9] = d[:, :, px].sum(-1)
+    return out.view(4 * B, 320)
+
+
+def stage_conv2_dgrad_conv1(dy_bf16, w2_bf16, x_norm, a1_bf16, relu_geq=False, dtype=F64):
+    """conv2_dgrad on dense dy [B,64,24,24], w2 [64,32,3,3], the normalised fp32 input rows [B,784] and the stored
+    a1 NCHW [B,32,26,26]: ``da1`` = the transposed convolution before masking and rounding, ``mask`` = the conv1
+    ReLU decision, and ``c1part`` [4B,320]: per (image, strip of 7 conv1 rows) the conv1 weight (ci*10 + tap) and
+    bias (ci*10 + 9) partial from bf16-rounded masked da1 and bf16-rounded x, as the kernel's second MFMA takes
+    them.  The kernel masks with the stored bf16 a1 > 0 (conv_bwd.hip dgrad_mask_load: no conv1 recompute), an
+    operand it reads - so the decision is exact and needs no margin."""
+    B = dy_bf16.shape[0]
+    da1 = F.conv_transpose2d(dy_bf16.to(dtype), w2_bf16.to(dtype))
+    mask = a1_bf16.to(F32) >= 0 if relu_geq else a1_bf16.to(F32) > 0
+    dq = bf16_round(da1 * mask).to(dtype).view(B, 32, 676)
+    xcols = F.unfold(bf16_round(x_norm).to(dtype).view(B, 1, 28, 28), 3)
+    return dict(da1=da1, mask=mask, c1part=_c1_strip_sums(xcols, dq))
+
+
+def c1red_rows(nslab: int) -> int:
+    return (nslab + C1_PRE_SLABS - 1) // C1_PRE_SLABS
+
+
+def stage_c1_prereduce(c1part, dtype=F64):
+    """c1_prereduce: [256,320], row j = sum of the partial rows [j R, min(4B, (j + 1) R)), R = ceil(4B / 256)."""
+    n, R_ = c1part.shape[0], c1red_rows(c1part.shape[0])
+    pad = torch.zeros(C1_PRE_SLABS * R_ - n, 320, dtype=dtype)
+    return torch.cat([c1part.to(dtype), pad]).view(C1_PRE_SLABS, R_, 320).sum(1)
+
+
+def stage_conv_reduce(w2w, w2b, c1part, grad_scale=1.0, dtype=F64):
+    """conv_grad_reduce on the partials (w2w [G,64,32,3,3], w2b [G,64], c1part or c1red rows [.,320]): the four
+    conv gradients x grad_scale."""
+    sc = torch.tensor(grad_scale, dtype=F32).to(dtype)
+    c1 = c1part.to(dtype).view(-1, 32, 10).sum(0)
+    return {"conv2.weight": w2w.to(dtype).sum(0) * sc, "conv2.bias": w2b.to(dtype).sum(0) * sc,
+            "conv1.weight": c1[:, :9].reshape(32, 1, 3, 3) * sc, "conv1.bias": c1[:, 9] * sc}
+
+
+# ---- the per-kernel checks of the backward stages; each returns {name: (deviation, eps)}
+def check_fc_wgrads(dz1, p, h_bf, dl_bf, grad_scale, grads, loss_rows=None, loss=None, parts=None, names=FC_NAMES,
+                    name="fc_bwd"):
+    """grads: {name: fp32 tensor} of the parameters in ``names``; loss: loss_log[step]; parts: per split a dict
+    as stage_fc_wgrads's (B > 1024).  dz1 / h_bf / dl_bf / p may carry padding rows: only rows < B are the oracle's
+    (B = len(loss_rows) if given, else p's rows)."""
+    args = (dz1, p, h_bf, dl_bf, grad_scale, loss_rows)
+    r64, r32 = stage_fc_wgrads(*args), stage_fc_wgrads(*args, dtype=F32)
+    stats = {}
+    for k in names:
+        eps = stage_eps(r32[k], r64[k])
+        stats[k] = (assert_within(grads[k], r64[k], eps, f"{name} {k}"), eps)
+    if loss is not None:
+        eps = stage_eps(r32["loss"], r64["loss"], head=True)
+        stats["loss"] = (assert_within(loss.reshape(()), r64["loss"], eps, f"{name} loss_log"), eps)
+    if parts is not None:
+        assert len(parts) == len(r64["parts"]), f"{name}: {len(parts)} splits"
+        for s, (got, w64, w32) in enumerate(zip(parts, r64["parts"], r32["parts"])):
+            for k in got:
+                eps = stage_eps(w32[k], w64[k], head=k == "loss")
+                dev = assert_within(got[k], w64[k], eps, f"{name} part {s} {k}")
+                old = stats.get(f"part {k}", (0.0, 0.0))
+                stats[f"part {k}"] = (max(old[0], dev), max(old[1], eps)) if dev / max(eps, 1e-300) >= \
+                    old[0] / max(old[1], 1e-300) else old
+    return stats
+
+
+def check_fc_dgrad(dz1_rows, w1_bf16, pm_rows, no_dropout, rec_rows, name="fc_bwd dyc"):
+    """Role B's records of the given rows: all 64 x 144 gradients against the bf16 rounding of the oracle, exactly
+    0 where the flags are not 12, the code planes bit for bit pm & 3."""
+    r64 = stage_fc_dgrad(dz1_rows, w1_bf16, pm_rows, no_dropout)
+    eps = stage_eps(stage_fc_dgrad(dz1_rows, w1_bf16, pm_rows, no_dropout, F32)["g"], r64["g"])
+    g, code = dyc_unpack(rec_rows)
+    stats = {"dyc g": (assert_rounded_bf16(g, r64["g"], eps, f"{name} g"), eps)}
+    assert (g.view(torch.int16)[~r64["live"]] & 0x7FFF == 0).all(), f"{name}: g is not 0 where the flags are not 12"
+    assert torch.equal(code, r64["code"]), f"{name}: code planes differ from pmask & 3"
+    return stats
+
+
+def check_conv2_wgrad(a1_nchw, dy, slabs, name="conv2_wgrad"):
+    """slabs f32 [G,18496]: every group's weight and bias partial, element by element."""
+    G = slabs.shape[0]
+    r64, r32 = stage_conv2_wgrad(a1_nchw, dy, G), stage_conv2_wgrad(a1_nchw, dy, G, dtype=F32)
+    w, b = w2part_unpack(slabs)
+    ew, eb = stage_eps(r32["w"], r64["w"]), stage_eps(r32["b"], r64["b"])
+    return {"w2part w": (assert_within(w, r64["w"], ew, f"{name} w2part weight"), ew),
+            "w2part b": (assert_within(b, r64["b"], eb, f"{name} w2part bias"), eb)}
+
+
+def check_conv2_dgrad(dy, w2_bf16, x_norm, a1_nchw, c1part, name="conv2_dgrad"):
+    """c1part f32 [4B,320] element by element.  A partial depends on the bf16 roundings of da1, which the oracle
+    can only decide up to the accumulation error of da1, so its eps is stage_eps over the whole chain dy -> partial
+    with both dtypes rounding da1 to bf16: the fp32 twin's midpoint flips are in the measured deviation.  On the
+    MI355X this alone held at every size (docs/COVERAGE.md 2.4: the kernel's deviations are 1e-9 to 2e-7, below
+    the chain eps throughout), so no explicit midpoint bound and no exclusion is needed."""
+    args = (dy, w2_bf16, x_norm, a1_nchw)
+    r64, r32 = stage_conv2_dgrad_conv1(*args), stage_conv2_dgrad_conv1(*args, dtype=F32)
+    eps = stage_eps(r32["c1part"], r64["c1part"])
+    return {"c1part": (assert_within(c1part, r64["c1part"], eps, f"{name} c1part"), eps)}
+
+
+def check_c1red(c1part, c1red, name="c1_prereduce"):
+    r64 = stage_c1_prereduce(c1part)
+    eps = stage_eps(stage_c1_prereduce(c1part, F32), r64)
+    return {"c1red": (assert_within(c1red, r64, eps, f"{name} c1red"), eps)}
+
+
+def check_conv_reduce(slabs, c1rows, grad_scale, grads, name="conv_grad_reduce"):
+    """grads {name: fp32} of the four conv parameters from slabs [G,18496] and the conv1 rows the reduce read
+    (c1part [4B,320], or c1red [256,320])."""
+    w, b = w2part_unpack(slabs)
+    r64, r32 = stage_conv_reduce(w, b, c1rows, grad_scale), stage_conv_reduce(w, b, c1rows, grad_scale, F32)
+    stats = {}
+    for k in CONV_NAMES:
+        eps = stage_eps(r32[k], r64[k])
+        stats[k] = (assert_within(grads[k], r64[k], eps, f"{name} {k}"), eps)
+    return stats
+
+
+# ---- hand-made operands of the backward tests (shared by the CPU and the GPU test)
+BWD_STEP = 3
+FC_REAL_B, FC_HAND_B = (1, 5, 31, 32, 33, 127, 128), (1024, 1025, 2047, 2048, 2049)
+CONV_B = (1, 2, 5, 85, 86, 128, 129, 341, 342)
+
+
+def fcb_mr(B: int) -> int:
+    return 8 if B >= 2048 else 2 if B >= 128 else 1
+
+
+def dyc_check_rows(B: int) -> list[int]:
+    """check_rows(B) and, beyond B = 64, the first and last row of every role-B workgroup's tile set."""
+    rows = set(check_rows(B))
+    if B > 64:
+        n = 16 * fcb_mr(B)
+        for r0 in range(0, B, n):
+            rows |= {r0, min(B, r0 + n) - 1}
+    return sorted(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def fc_hand_case(B: int):
+    """Random bf16 operands of fc_bwd at realistic scales: dz1 / h_bf [Bp64,128], dl_bf [Bp64,16] with rows >= B
+    and dl columns >= 10 zero (head_train's contract), p [Bp64,9216] with rows >= B NaN (they must be masked),
+    loss_rows [B], and flags pm [B,9216] with all 16 low-nibble patterns in the 16 rows of every tile at
+    every feature."""
+    g = torch.Generator().manual_seed(7000 + B)
+    Bp = (B + 63) // 64 * 64
+    rn = lambda *s: torch.randn(*s, generator=g)
+    keep = lambda *s: (torch.rand(*s, generator=g) < 0.5).float()
+    dz1, h, dl = torch.zeros(Bp, 128), torch.zeros(Bp, 128), torch.zeros(Bp, 16)
+    dz1[:B] = rn(B, 128) * keep(B, 128) * (0.05 / B)
+    h[:B] = rn(B, 128).relu() * 2.0
+    dl[:B, :10] = rn(B, 10) * (0.3 / B)
+    p = torch.full((Bp, 9216), float("nan"))
+    p[:B] = rn(B, 9216).relu() * INV_KEEP1_F32
+    pm = ((torch.arange(B).view(-1, 1) + 5 * torch.arange(9216).view(1, -1) + (torch.arange(9216) >> 6)) & 15)
+    return dict(dz1=bf16_round(dz1), h_bf=bf16_round(h), dl_bf=bf16_round(dl), p=bf16_round(p),
+                pm=pm.to(torch.uint8), loss_rows=rn(B).abs() + 0.5)
+
+
+def pmask_device(pm_flat):
+    """[B,9216] flags in torch flatten order -> the device layout [B][36][64][4] (inverse of pmask_flat)."""
+    B = pm_flat.shape[0]
+    return pm_flat.view(B, 64, 36, 4).permute(0, 2, 1, 3).reshape(B, 9216).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def conv_hand_case(B: int):
+    """Dense records (every gradient non-zero, every code in every 8-channel chunk), a1 NHWC bf16 about half
+    zeros, and the normalised input rows of forward_case(B)'s first B images."""
+    g = torch.Generator().manual_seed(9000 + B)
+    gr = bf16_round(torch.randn(B, 9216, generator=g) * (2e-3 / B))
+    c = torch.arange(64).view(1, 64, 1)
+    code = ((c + (c >> 3) + torch.arange(144).view(1, 1, 144) + torch.arange(B).view(B, 1, 1)) & 3).reshape(B, 9216)
+    a1 = bf16_round(torch.randn(B, 26, 26, 32, generator=g).relu())
+    imgs = forward_case(B)[0][:B]
+    return dict(g=gr, code=code, a1=a1, imgs=imgs, x=normalize_u8(imgs).reshape(B, 784))
