@@ -279,6 +279,18 @@ PYBIND11_MODULE(_C, m) {
     launch_input_grad(a, B, S(stream));
     check_launch();
   }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("dx"), py::arg("B"), py::arg("stream"));
+  m.def("input_grad_step", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t x, uintptr_t x0,
+                              uintptr_t x_next, float alpha, float eps, float lo, float hi, int B,
+                              uintptr_t stream, uintptr_t dx) {
+    InputGradStepArgs a{{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d), P<const float>(w1c),
+                         P<float>(dx)},
+                        P<const float>(x), P<const float>(x0), P<float>(x_next), alpha, eps, lo, hi};
+    launch_input_grad_step(a, B, S(stream));
+    check_launch();
+  }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("x"), py::arg("x0"), py::arg("x_next"),
+     py::arg("alpha"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
+     py::arg("dx") = 0,
+     "input_grad with the projected-step epilogue: x_next = clamp(clamp(x + alpha sgn(dx), x0 -+ eps), lo, hi)");
 
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
@@ -475,6 +487,7 @@ PYBIND11_MODULE(_C, m) {
     preload_xgmi();
     preload_f32();
     preload_input_grad();
+    preload_input_grad_step();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -579,6 +592,7 @@ PYBIND11_MODULE(_C, m) {
     preload_xgmi();
     preload_f32();
     preload_input_grad();
+    preload_input_grad_step();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

@@ -226,6 +226,19 @@ inline InputGradPlan input_grad_plan(int B, int cus) {
 }
 constexpr int INPUT_GRAD_MAX_B = 1 << 20;   // 32-bit item index
 void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s);
+// The same kernel body with a projected-step epilogue (L-inf FGSM / PGD on the normalised image): the
+// thread that owns dx element e = s writes, instead of s,
+//   t = x[e] + alpha * sgn(s);  t = min(max(t, x0[e] - eps), x0[e] + eps);  x_next[e] = min(max(t, lo), hi)
+// with sgn = torch.sign for finite s and NaN for a NaN s (which reaches x_next).  x_next may alias x;
+// g.dx is optional here (null: the gradient is not stored).  Same plan, same bits on any grid.
+struct InputGradStepArgs {
+  InputGradArgs g;            // as launch_input_grad; g.dx may be null
+  const float* x;             // fp32 [B][784] current iterate
+  const float* x0;            // fp32 [B][784] centre of the eps ball (the clean image)
+  float* x_next;              // fp32 [B][784]
+  float alpha, eps, lo, hi;   // step size, radius, valid range: all in normalised units
+};
+void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s);
 
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
@@ -295,6 +308,7 @@ void preload_comm();
 void preload_xgmi();
 void preload_f32();
 void preload_input_grad();
+void preload_input_grad_step();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

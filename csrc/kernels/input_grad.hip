@@ -18,6 +18,13 @@
 // da1 FORM: da1 stays fp32 from the MFMA accumulators to the last fma (it is NOT rounded to bf16).
 // Rows of da1 outside the image (strip 0: -2, -1; strip 3: 26, 27) are stored as zeros.
 // No atomics, no cross-workgroup traffic, no waits: any grid gives the same bits.
+//
+// EPILOGUE: what the thread that owns dx[b][Y][X] does with its sum s is a compile-time policy of the
+// one kernel body (template parameter).  IgStoreGrad stores s (launch_input_grad; instruction for
+// instruction the kernel as it was before the policy existed).  IgProjectedStep writes the next iterate of
+// an L-inf signed-gradient ascent (FGSM / PGD) instead, and s itself only when asked:
+//   t = x + alpha * sgn(s);  t = min(max(t, x0 - eps), x0 + eps);  x_next = min(max(t, lo), hi)
+// (launch_input_grad_step).  Its x / x0 loads are issued before stage 2 and land under the 288 fmas.
 #include "../include/device_utils.h"
 #include "../include/kernels.h"
 
@@ -60,7 +67,38 @@ __device__ __forceinline__ uint32_t ig_keep_pair(uint32_t g, uint32_t r16, int k
 }
 }  // namespace
 
-__global__ __launch_bounds__(IG_THREADS, 2) void input_grad_kernel(InputGradArgs a, int B) {
+// ---- epilogue policies: `load(e)` is issued before stage 2 for dx element e = b * 784 + Y * 28 + X,
+// `store(dx, e, s, v)` after its last fma, both by the one thread that owns e
+struct IgStoreGrad {
+  struct Loaded {};
+  __device__ __forceinline__ Loaded load(int64_t) const { return {}; }
+  __device__ __forceinline__ void store(float* dx, int64_t e, float s, Loaded) const { dx[e] = s; }
+};
+
+struct IgProjectedStep {
+  const float* x;
+  const float* x0;
+  float* x_next;              // may alias x: element e is read and written by its owner only
+  float alpha, eps, lo, hi;
+  struct Loaded { float x, x0; };
+  __device__ __forceinline__ Loaded load(int64_t e) const { return {x[e], x0[e]}; }
+  __device__ __forceinline__ void store(float* dx, int64_t e, float s, Loaded v) const {
+    if (dx) dx[e] = s;                                     // optional here
+    // torch.sign, except that a NaN gradient stays a NaN (every comparison below is false for it, so it
+    // passes both clamps): a broken gradient is not turned into "no step"
+    const float sg = s > 0.0f ? 1.0f : s < 0.0f ? -1.0f : s == s ? 0.0f : s;
+    float t = v.x + alpha * sg;                            // alpha * sg is exact: contraction cannot change it
+    const float el = v.x0 - eps, eh = v.x0 + eps;          // rounded to fp32 first, as the torch formula does
+    t = t < el ? el : t;
+    t = t > eh ? eh : t;
+    t = t < lo ? lo : t;
+    t = t > hi ? hi : t;
+    x_next[e] = t;
+  }
+};
+
+template <class Epilogue>
+__global__ __launch_bounds__(IG_THREADS, 2) void input_grad_kernel(InputGradArgs a, int B, Epilogue epi) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[IG_LDS];
   uint16_t* dys = reinterpret_cast<uint16_t*>(smem);
   float* das = reinterpret_cast<float*>(smem);             // aliases the dy tile (after the MFMA loop)
@@ -203,6 +241,7 @@ __global__ __launch_bounds__(IG_THREADS, 2) void input_grad_kernel(InputGradArgs
     // ---- stage 2: dx[Y][X] = sum over ci, ky, kx of da1[Y - ky][X - kx][ci] * w1c[ci][3 ky + kx]
     if (tid < IG_ROWS * IMG) {
       const int yl = tid / IMG, X = tid - yl * IMG;
+      const typename Epilogue::Loaded ev = epi.load((int64_t)b * (IMG * IMG) + (Y0 + yl) * IMG + X);
       const float* base = das + ((yl + 2) * IG_DA_COLS + X + 2) * IG_DA_LD;   // da1 (Y, X)
       // (four chains with 16-B weight reads measured slower, 28.2 against 26.4 us at B = 200: the
       // stage is bound by LDS bytes, not by instruction count or the fma chain)
@@ -214,12 +253,11 @@ __global__ __launch_bounds__(IG_THREADS, 2) void input_grad_kernel(InputGradArgs
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx)
             s = __builtin_fmaf(base[-(ky * IG_DA_COLS + kx) * IG_DA_LD + ci], w1s[ci * 9 + ky * 3 + kx], s);
-      a.dx[(int64_t)b * (IMG * IMG) + (Y0 + yl) * IMG + X] = s;
+      epi.store(a.dx, (int64_t)b * (IMG * IMG) + (Y0 + yl) * IMG + X, s, ev);
     }
     lds_barrier();                                         // the next dy store must not overtake these reads
   }
 }
-
 static int input_grad_cus() {
   static int cus = 0;
   if (!cus) {
@@ -234,12 +272,26 @@ void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s) {
   if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("input_grad: batch size out of range");
   if (!a.dyc || !a.a1 || !a.w2d || !a.w1c || !a.dx) throw std::runtime_error("input_grad: null argument");
   const InputGradPlan p = input_grad_plan(B, input_grad_cus());
-  hipLaunchKernelGGL(input_grad_kernel, dim3(p.grid), dim3(IG_THREADS), 0, s, a, B);
+  hipLaunchKernelGGL(input_grad_kernel<IgStoreGrad>, dim3(p.grid), dim3(IG_THREADS), 0, s, a, B, IgStoreGrad{});
+}
+
+void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s) {
+  if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("input_grad_step: batch size out of range");
+  if (!a.g.dyc || !a.g.a1 || !a.g.w2d || !a.g.w1c || !a.x || !a.x0 || !a.x_next)
+    throw std::runtime_error("input_grad_step: null argument");   // (g.dx is optional)
+  const InputGradPlan p = input_grad_plan(B, input_grad_cus());
+  hipLaunchKernelGGL(input_grad_kernel<IgProjectedStep>, dim3(p.grid), dim3(IG_THREADS), 0, s, a.g, B,
+                     IgProjectedStep{a.x, a.x0, a.x_next, a.alpha, a.eps, a.lo, a.hi});
 }
 
 void preload_input_grad() {
   hipFuncAttributes fa;
-  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&input_grad_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&input_grad_kernel<IgStoreGrad>));
+}
+
+void preload_input_grad_step() {
+  hipFuncAttributes fa;
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&input_grad_kernel<IgProjectedStep>));
 }
 
 }  // namespace mnist

@@ -22,6 +22,16 @@ wrt the normalised image, in the same inference semantics (no dropout):
   (``ops.fused_net.fused_input_gradient``); no conv weight gradient is computed;
 * CPU, or ``dtype="fp32"``: torch autograd over ``Net.forward_reference`` in eval mode.
 
+``Predictor.adversarial`` / ``Predictor.robust_evaluate`` (L-inf FGSM / PGD on that gradient; ``eps`` and
+``step_size`` in pixel units on the [0, 1] scale):
+
+* GPU, ``dtype="bf16"``: the native loop ``ops.attack.fused_adversarial`` - per step ``trunk_fwd`` ->
+  ``fc1_fwd`` -> ``head_train`` -> ``fc_bwd`` (role B only) -> ``input_grad`` in its step form, which
+  updates the iterate in place; no autograd, no per-step allocation, no host sync;
+* CPU, or ``dtype="fp32"``: the same formula in torch ops over autograd through
+  ``Net.forward_reference`` in eval mode;
+* the returned log-probabilities are the predictor's own forward (above) of the adversarial images.
+
 There is no fallback between them: a GPU predictor without the native extension raises.
 """
 from __future__ import annotations
@@ -33,10 +43,15 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
-from .data.datasets import load_mnist, normalize_u8
+from .data.datasets import MNIST_STD, load_mnist, normalize_u8
 from .models.net import Net
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
+
+# The 256 normalised pixel values, by normalize_u8's own arithmetic on the CPU (IEEE division: what the
+# kernels' in-register normalisation gives, bit for bit); entries 0 and 255 bound the valid range.
+_PIXEL_LUT = normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256)
+PIXEL_LO, PIXEL_HI = float(_PIXEL_LUT[0]), float(_PIXEL_LUT[255])
 
 # Largest batch the fused single-launch kernel serves; above it the three-launch path runs.  Taken
 # from tools/infer_bench.py's table (profiles/infer/infer_bench.txt, docs/PERF_NOTES.md): as measured,
@@ -131,6 +146,88 @@ class Predictor:
             self.net.train(was_training)
         return grad, lp.detach()
 
+    def adversarial(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1, steps: int = 1,
+                    step_size: float | None = None, random_start: bool = False, generator=None):
+        """(x_adv, log_probs): L-inf FGSM (``steps`` = 1) / PGD adversarial examples of ``x`` and the
+        predictor's float32 [B,10] log-probabilities of them.  ``x_adv`` is float32 [B,1,28,28] in
+        NORMALISED units, inside both the ``eps`` ball around ``x`` and the valid pixel range [0, 1].
+
+        ``eps``, ``step_size``: pixel units on the [0, 1] scale (0.1, 0.3 are usual for MNIST);
+        ``step_size`` None: ``eps`` for one step, ``2.5 * eps / steps`` otherwise.  The summed NLL against
+        ``labels`` ([B] integers) is ascended, or against the class predicted on the clean input when
+        ``labels`` is None.  ``random_start``: start from ``x + U(-eps, eps)`` (clamped to the valid
+        range), drawn with torch from ``generator``.  Inference semantics as ``input_gradient``: no
+        dropout, the net's mode, dropout modules and parameter gradients are untouched.  ``x``: uint8
+        [B,28,28] / [B,784] images or float [B,1,28,28] already-normalised input."""
+        B = self._check_input(x)
+        if not eps >= 0:
+            raise ValueError(f"adversarial: eps must be >= 0, got {eps}")
+        if steps != int(steps) or steps < 1:
+            raise ValueError(f"adversarial: steps must be a positive integer, got {steps}")
+        if step_size is None:
+            step_size = eps if steps == 1 else 2.5 * eps / steps
+        elif not step_size > 0:
+            raise ValueError(f"adversarial: step_size must be > 0, got {step_size}")
+        if x.dtype == torch.uint8:               # the kernels' normalisation, bit for bit, on any device
+            x0 = _PIXEL_LUT.to(x.device)[x.reshape(B, 784).long()]
+        else:
+            x0 = x.detach().reshape(B, 784)
+        x0 = x0.to(self.device, torch.float32).contiguous()
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            if labels.numel() != B:
+                raise ValueError(f"adversarial: {labels.numel()} labels for {B} images")
+            labels = labels.reshape(B).long().to(self.device)
+            if int(labels.min()) < 0 or int(labels.max()) > 9:
+                raise ValueError("adversarial: labels must be in [0, 10)")
+        eps_n, alpha_n, lo, hi = eps / MNIST_STD, step_size / MNIST_STD, PIXEL_LO, PIXEL_HI
+        x_init = None
+        if random_start:
+            u = torch.rand(B, 784, generator=generator, dtype=torch.float32,
+                           device=generator.device if generator is not None else self.device).to(self.device)
+            x_init = (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
+        if self.native:
+            from .ops.attack import fused_adversarial
+            x_adv = fused_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init)
+        else:
+            x_adv = x0 if x_init is None else x_init
+            was_training = self.net.training
+            self.net.eval()
+            try:
+                for _ in range(int(steps)):
+                    xg = x_adv.clone().requires_grad_()
+                    with torch.enable_grad():
+                        lp = self.net.forward_reference(xg.view(B, 1, 28, 28))
+                        loss = F.nll_loss(lp, labels, reduction='sum')
+                        g, = torch.autograd.grad(loss, xg)
+                    t = x_adv + alpha_n * g.sign()
+                    t = torch.min(torch.max(t, x0 - eps_n), x0 + eps_n)
+                    x_adv = t.clamp(lo, hi)
+            finally:
+                self.net.train(was_training)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        return x_adv, self._forward(x_adv)[0]
+
+    def robust_evaluate(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 1,
+                        step_size: float | None = None, batch_size: int = 1000):
+        """(loss_sum, correct, n) as ``evaluate``, of the images after an L-inf attack against their true
+        labels (``adversarial`` without a random start), ``batch_size`` images at a time."""
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("robust_evaluate: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("robust_evaluate: batch_size must be positive")
+        lab = labels.long().to(self.device)
+        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        hits = torch.zeros((), dtype=torch.int64, device=self.device)
+        for i in range(0, n, batch_size):
+            y = lab[i:i + batch_size]
+            _, lp = self.adversarial(images_u8[i:i + batch_size], y, eps, steps, step_size)
+            loss += F.nll_loss(lp, y, reduction='none').double().sum()
+            hits += (lp.argmax(dim=1) == y).sum()
+        return float(loss.item()), int(hits.item()), n
+
     # ------------------------------------------------------------------ dispatch
     def _check_input(self, x: torch.Tensor) -> int:
         B = int(x.shape[0])
@@ -203,7 +300,20 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--saliency', default=None, metavar='OUT.npy',
                     help='also write d NLL / d (normalised image) against the true labels for the evaluated '
                          'split as a float32 [N,28,28] .npy file (default: off)')
+    ap.add_argument('--attack-eps', type=float, default=None, metavar='E',
+                    help='also report loss and accuracy under an L-inf FGSM / PGD attack of radius E, in pixel '
+                         'units on the [0, 1] scale (default: off)')
+    ap.add_argument('--attack-steps', type=int, default=1, metavar='K',
+                    help='attack iterations: 1 = FGSM, more = PGD (default: 1)')
+    ap.add_argument('--attack-step-size', type=float, default=None, metavar='A',
+                    help='attack step in pixel units (default: E for one step, 2.5 * E / K otherwise)')
     return ap
+
+
+def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int) -> str:
+    """The ``Test set:`` line's figures (``utils.logging.test_line``) for the attacked split."""
+    figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
+    return f"Adversarial set (Linf eps={eps:g}, steps={steps}): {figures}"
 
 
 def predict_main(argv=None) -> int:
@@ -223,8 +333,15 @@ def predict_main(argv=None) -> int:
             out[i:i + g.shape[0]] = g.reshape(-1, 28, 28).cpu().numpy()
         with open(args.saliency, "wb") as f:      # (np.save on a name would append ".npy")
             np.save(f, out)
+    record = {"checkpoint": args.checkpoint, "device": str(device), "source": data.source,
+              "test_loss": loss_sum / n, "correct": correct, "n": n}
+    if args.attack_eps is not None:
+        adv_loss, adv_correct, _ = predictor.robust_evaluate(images, data.targets, args.attack_eps, args.attack_steps,
+                                                             args.attack_step_size, args.batch_size)
+        print(adversarial_line(args.attack_eps, args.attack_steps, adv_loss / n, adv_correct, n))
+        record.update(adv_eps=args.attack_eps, adv_steps=args.attack_steps, adv_loss=adv_loss / n,
+                      adv_correct=adv_correct)
     if args.json_log:
         with open(args.json_log, "a") as f:
-            f.write(json.dumps({"checkpoint": args.checkpoint, "device": str(device), "source": data.source,
-                                "test_loss": loss_sum / n, "correct": correct, "n": n}) + "\n")
+            f.write(json.dumps(record) + "\n")
     return 0

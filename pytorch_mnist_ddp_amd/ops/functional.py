@@ -81,13 +81,14 @@ def pmask_flat(pmask: torch.Tensor) -> torch.Tensor:
     return pmask.view(B, 36, 64, 4).permute(0, 2, 1, 3).reshape(B, 9216)
 
 
-def trunk_fwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, train: bool,
-              idx_stride: int = 0, state: torch.Tensor | None = None) -> None:
+def trunk_fwd(ms, data_u8: torch.Tensor | None, idx: torch.Tensor | None, buf: StepBuffers, train: bool,
+              idx_stride: int = 0, state: torch.Tensor | None = None, xin: torch.Tensor | None = None) -> None:
+    """``xin`` (float32 [B, 784], already normalised) replaces the dataset rows ``data_u8`` / ``idx``."""
     p, o = native.ptr, ms.offsets
     _C().trunk_fwd(p(data_u8), p(idx), idx_stride, p(state if state is not None else ms.state),
                    p(ms.param) + 4 * o["conv1.weight"], p(ms.param) + 4 * o["conv1.bias"], p(ms.w2f),
                    p(ms.param) + 4 * o["conv2.bias"], p(buf.a1) if train else 0, p(buf.p),
-                   p(buf.pmask) if train else 0, buf.B, train, _s())
+                   p(buf.pmask) if train else 0, buf.B, train, _s(), xin=p(xin))
 
 
 def fc1_fwd(ms, buf: StepBuffers) -> None:
@@ -95,11 +96,15 @@ def fc1_fwd(ms, buf: StepBuffers) -> None:
     _C().fc1_fwd(p(buf.p), p(ms.w1), p(buf.z1part), buf.B, _s())
 
 
-def head_train(ms, labels: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, idx_stride: int = 0) -> None:
+def head_train(ms, labels: torch.Tensor, idx: torch.Tensor | None, buf: StepBuffers, idx_stride: int = 0,
+               state: torch.Tensor | None = None, inv_batch: float | None = None) -> None:
+    """``idx`` None: ``labels`` holds one int32 label per batch row.  ``inv_batch``: the loss scale
+    (default 1 / B, the mean NLL; 1.0 gives the gradient of the summed NLL)."""
     p, o = native.ptr, ms.offsets
     B = buf.B
     _C().head_train(p(buf.z1part), p(ms.param) + 4 * o["fc1.bias"], p(ms.param) + 4 * o["fc2.weight"],
-                    p(ms.param) + 4 * o["fc2.bias"], p(labels), p(idx), idx_stride, p(ms.state), 1.0 / B,
+                    p(ms.param) + 4 * o["fc2.bias"], p(labels), p(idx), idx_stride,
+                    p(state if state is not None else ms.state), 1.0 / B if inv_batch is None else inv_batch,
                     p(buf.loss_rows), p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), B, round_up(B, 32), _s())
 
 
@@ -118,12 +123,12 @@ CONV_DGRAD, CONV_WGRAD, CONV_REDUCE, CONV_ALL = 1, 2, 4, 7      # conv_bwd stage
 
 
 def fc_bwd(ms, buf: StepBuffers, grad_scale: float = 1.0, loss_log: torch.Tensor | None = None,
-           role: int = -1) -> None:
+           role: int = -1, state: torch.Tensor | None = None) -> None:
     p = native.ptr
     B = buf.B
     _C().fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), p(ms.w1t), p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
-                p(ms.state), p(ms.grad), p(buf.dyc), p(loss_log), grad_scale, 1.0 / B, B, round_up(B, 32), _s(),
-                role=role, part=p(buf.fcpart))
+                p(state if state is not None else ms.state), p(ms.grad), p(buf.dyc), p(loss_log), grad_scale,
+                1.0 / B, B, round_up(B, 32), _s(), role=role, part=p(buf.fcpart))
 
 
 def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, grad_scale: float = 1.0,
@@ -151,6 +156,43 @@ def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.T
         raise ValueError("input_grad: out must be contiguous float32 [B, 784] on the buffers' device")
     p, o = native.ptr, ms.offsets
     _C().input_grad(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"], p(out), B, _s())
+    return out.view(B, 784)
+
+
+def _f32_rows(name: str, what: str, t: torch.Tensor, B: int, device) -> None:
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * 784 or t.device != device:
+        raise ValueError(f"{name}: {what} must be contiguous float32 [B, 784] on the buffers' device")
+
+
+def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
+                    lo: float, hi: float, out: torch.Tensor | None = None,
+                    dx: torch.Tensor | None = None) -> torch.Tensor:
+    """One projected signed-gradient step on the normalised image from one launch of ``input_grad.hip``
+    in its step form: with ``g`` what ``input_grad`` returns on the same buffers,
+
+        t = x + alpha * sign(g);  t = min(max(t, x0 - eps), x0 + eps);  out = min(max(t, lo), hi)
+
+    elementwise in float32 (a NaN in ``g`` reaches ``out``).  ``x``, ``x0``, ``out``: float32 [B, 784];
+    ``out`` may be ``x`` itself (in place) and is allocated when None.  ``dx`` (optional, float32
+    [B, 784], no overlap with the others) also receives ``g``."""
+    B, dev = buf.B, buf.dyc.device
+    _f32_rows("input_grad_step", "x", x, B, dev)
+    _f32_rows("input_grad_step", "x0", x0, B, dev)
+    if out is None:
+        out = torch.empty(B, 784, dtype=torch.float32, device=dev)
+    else:
+        _f32_rows("input_grad_step", "out", out, B, dev)
+    if out.data_ptr() == x0.data_ptr():
+        raise ValueError("input_grad_step: out must not be x0 (the centre of the eps ball is read, not written)")
+    if dx is not None:
+        _f32_rows("input_grad_step", "dx", dx, B, dev)
+        if dx.data_ptr() in (x.data_ptr(), x0.data_ptr(), out.data_ptr()):
+            raise ValueError("input_grad_step: dx must not alias x, x0 or out")
+    if not (eps >= 0 and alpha >= 0 and lo <= hi):
+        raise ValueError("input_grad_step: need eps >= 0, alpha >= 0 and lo <= hi")
+    p, o = native.ptr, ms.offsets
+    _C().input_grad_step(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"], p(x), p(x0),
+                         p(out), alpha, eps, lo, hi, B, _s(), dx=p(dx))
     return out.view(B, 784)
 
 
