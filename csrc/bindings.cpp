@@ -291,6 +291,15 @@ PYBIND11_MODULE(_C, m) {
      py::arg("alpha"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
      py::arg("dx") = 0,
      "input_grad with the projected-step epilogue: x_next = clamp(clamp(x + alpha sgn(dx), x0 -+ eps), lo, hi)");
+  m.attr("PGD_L2_TINY") = PGD_L2_TINY;
+  m.def("pgd_l2_step", [](uintptr_t dx, uintptr_t x, uintptr_t x0, uintptr_t x_next, float alpha, float eps,
+                          float lo, float hi, int B, uintptr_t stream) {
+    PgdL2StepArgs a{P<const float>(dx), P<const float>(x), P<const float>(x0), P<float>(x_next), alpha, eps, lo, hi};
+    launch_pgd_l2_step(a, B, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("x"), py::arg("x0"), py::arg("x_next"), py::arg("alpha"), py::arg("eps"),
+     py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
+     "L2 projected-gradient step per image: t = x + alpha dx / |dx|; x_next = clamp(x0 + proj_eps(t - x0), lo, hi)");
 
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
@@ -488,6 +497,7 @@ PYBIND11_MODULE(_C, m) {
     preload_f32();
     preload_input_grad();
     preload_input_grad_step();
+    preload_attack_step();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -593,6 +603,7 @@ PYBIND11_MODULE(_C, m) {
     preload_f32();
     preload_input_grad();
     preload_input_grad_step();
+    preload_attack_step();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

@@ -240,6 +240,22 @@ struct InputGradStepArgs {
 };
 void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s);
 
+// L2 projected-gradient step (attack_step.hip; L2 PGD on the normalised image), one workgroup per image:
+//   n = sqrt(sum dx^2);  t = x + (alpha / max(n, TINY)) * dx;  d = t - x0;  m = sqrt(sum d^2)
+//   x_next = min(max(x0 + d * min(1, eps / max(m, TINY)), lo), hi)
+// all fp32, both sums a fixed tree (the same bits on any stream and launch).  alpha < 0 descends (targeted);
+// a zero dx leaves t = x; a NaN in an image's dx makes that image's x_next NaN and no other's.  x_next may
+// alias x.  dx is what launch_input_grad wrote.  The arrays are 16-byte aligned (rows are 3136 B).
+constexpr float PGD_L2_TINY = 1e-12f;       // floor of both norms (ops/functional.py PGD_L2_TINY)
+struct PgdL2StepArgs {
+  const float* dx;            // fp32 [B][784] gradient wrt the normalised image
+  const float* x;             // fp32 [B][784] current iterate
+  const float* x0;            // fp32 [B][784] centre of the eps ball (the clean image), inside [lo, hi]
+  float* x_next;              // fp32 [B][784]
+  float alpha, eps, lo, hi;   // step length, radius (both L2), valid range: all in normalised units
+};
+void launch_pgd_l2_step(const PgdL2StepArgs& a, int B, hipStream_t s);   // B in [1, INPUT_GRAD_MAX_B], eps >= 0
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -309,6 +325,7 @@ void preload_xgmi();
 void preload_f32();
 void preload_input_grad();
 void preload_input_grad_step();
+void preload_attack_step();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

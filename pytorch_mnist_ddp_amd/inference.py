@@ -22,12 +22,14 @@ wrt the normalised image, in the same inference semantics (no dropout):
   (``ops.fused_net.fused_input_gradient``); no conv weight gradient is computed;
 * CPU, or ``dtype="fp32"``: torch autograd over ``Net.forward_reference`` in eval mode.
 
-``Predictor.adversarial`` / ``Predictor.robust_evaluate`` (L-inf FGSM / PGD on that gradient; ``eps`` and
-``step_size`` in pixel units on the [0, 1] scale):
+``Predictor.adversarial`` / ``Predictor.robust_evaluate`` (L-inf or L2 FGSM / PGD on that gradient,
+untargeted or targeted; ``eps`` and ``step_size`` in pixel units on the [0, 1] scale):
 
 * GPU, ``dtype="bf16"``: the native loop ``ops.attack.fused_adversarial`` - per step ``trunk_fwd`` ->
   ``fc1_fwd`` -> ``head_train`` -> ``fc_bwd`` (role B only) -> ``input_grad`` in its step form, which
-  updates the iterate in place; no autograd, no per-step allocation, no host sync;
+  updates the iterate in place (L2: ``input_grad`` in its plain form, then ``pgd_l2_step`` of
+  ``csrc/kernels/attack_step.hip``, one workgroup per image); no autograd, no per-step allocation, no
+  host sync;
 * CPU, or ``dtype="fp32"``: the same formula in torch ops over autograd through
   ``Net.forward_reference`` in eval mode;
 * the returned log-probabilities are the predictor's own forward (above) of the adversarial images.
@@ -45,6 +47,7 @@ import torch.nn.functional as F
 
 from .data.datasets import MNIST_STD, load_mnist, normalize_u8
 from .models.net import Net
+from .ops.functional import PGD_L2_TINY, pgd_l2_step_reference
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -147,19 +150,28 @@ class Predictor:
         return grad, lp.detach()
 
     def adversarial(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1, steps: int = 1,
-                    step_size: float | None = None, random_start: bool = False, generator=None):
-        """(x_adv, log_probs): L-inf FGSM (``steps`` = 1) / PGD adversarial examples of ``x`` and the
+                    step_size: float | None = None, random_start: bool = False, generator=None,
+                    norm: str = "linf", targeted: bool = False):
+        """(x_adv, log_probs): FGSM (``steps`` = 1) / PGD adversarial examples of ``x`` and the
         predictor's float32 [B,10] log-probabilities of them.  ``x_adv`` is float32 [B,1,28,28] in
         NORMALISED units, inside both the ``eps`` ball around ``x`` and the valid pixel range [0, 1].
 
-        ``eps``, ``step_size``: pixel units on the [0, 1] scale (0.1, 0.3 are usual for MNIST);
-        ``step_size`` None: ``eps`` for one step, ``2.5 * eps / steps`` otherwise.  The summed NLL against
-        ``labels`` ([B] integers) is ascended, or against the class predicted on the clean input when
-        ``labels`` is None.  ``random_start``: start from ``x + U(-eps, eps)`` (clamped to the valid
-        range), drawn with torch from ``generator``.  Inference semantics as ``input_gradient``: no
-        dropout, the net's mode, dropout modules and parameter gradients are untouched.  ``x``: uint8
-        [B,28,28] / [B,784] images or float [B,1,28,28] already-normalised input."""
+        ``norm``: ``"linf"`` (signed-gradient steps, the ball is a box) or ``"l2"`` (steps of length
+        ``step_size`` along the gradient, the ball is Euclidean per image).  ``eps``, ``step_size``: pixel
+        units on the [0, 1] scale (L-inf: 0.1, 0.3 are usual for MNIST; L2: 1.5 to 2.0); ``step_size``
+        None: ``eps`` for one step, ``2.5 * eps / steps`` otherwise.  The summed NLL against ``labels``
+        ([B] integers) is ascended, or against the class predicted on the clean input when ``labels`` is
+        None; ``targeted``: ``labels`` (required) are the classes to reach and their NLL is descended.
+        ``random_start``: start from a point drawn with torch from ``generator`` - L-inf: ``x + U(-eps,
+        eps)``; L2: uniform in the ball (a normal direction scaled to radius ``eps * u^(1/784)``) - clamped
+        to the valid range.  Inference semantics as ``input_gradient``: no dropout, the net's mode,
+        dropout modules and parameter gradients are untouched.  ``x``: uint8 [B,28,28] / [B,784] images
+        or float [B,1,28,28] already-normalised input."""
         B = self._check_input(x)
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"adversarial: norm must be 'linf' or 'l2', got {norm!r}")
+        if targeted and labels is None:
+            raise ValueError("adversarial: a targeted attack needs labels (the target classes)")
         if not eps >= 0:
             raise ValueError(f"adversarial: eps must be >= 0, got {eps}")
         if steps != int(steps) or steps < 1:
@@ -184,14 +196,24 @@ class Predictor:
         eps_n, alpha_n, lo, hi = eps / MNIST_STD, step_size / MNIST_STD, PIXEL_LO, PIXEL_HI
         x_init = None
         if random_start:
-            u = torch.rand(B, 784, generator=generator, dtype=torch.float32,
-                           device=generator.device if generator is not None else self.device).to(self.device)
-            x_init = (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
+            draw = dict(generator=generator, dtype=torch.float32,
+                        device=generator.device if generator is not None else self.device)
+            if norm == "linf":
+                u = torch.rand(B, 784, **draw).to(self.device)
+                x_init = (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
+            else:
+                g = torch.randn(B, 784, **draw).to(self.device)
+                u = torch.rand(B, 1, **draw).to(self.device)
+                radius = eps_n * u.pow(1.0 / 784.0)
+                x_init = (x0 + g * (radius / g.square().sum(dim=1, keepdim=True).sqrt().clamp_min(PGD_L2_TINY))
+                          ).clamp_(lo, hi)
         if self.native:
             from .ops.attack import fused_adversarial
-            x_adv = fused_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init)
+            x_adv = fused_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init,
+                                      norm=norm, targeted=targeted)
         else:
             x_adv = x0 if x_init is None else x_init
+            alpha_s = -alpha_n if targeted else alpha_n
             was_training = self.net.training
             self.net.eval()
             try:
@@ -201,18 +223,24 @@ class Predictor:
                         lp = self.net.forward_reference(xg.view(B, 1, 28, 28))
                         loss = F.nll_loss(lp, labels, reduction='sum')
                         g, = torch.autograd.grad(loss, xg)
-                    t = x_adv + alpha_n * g.sign()
-                    t = torch.min(torch.max(t, x0 - eps_n), x0 + eps_n)
-                    x_adv = t.clamp(lo, hi)
+                    if norm == "l2":
+                        x_adv = pgd_l2_step_reference(g, x_adv, x0, eps_n, alpha_s, lo, hi)
+                    else:
+                        t = x_adv + alpha_s * g.sign()
+                        t = torch.min(torch.max(t, x0 - eps_n), x0 + eps_n)
+                        x_adv = t.clamp(lo, hi)
             finally:
                 self.net.train(was_training)
         x_adv = x_adv.view(B, 1, 28, 28)
         return x_adv, self._forward(x_adv)[0]
 
     def robust_evaluate(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 1,
-                        step_size: float | None = None, batch_size: int = 1000):
-        """(loss_sum, correct, n) as ``evaluate``, of the images after an L-inf attack against their true
-        labels (``adversarial`` without a random start), ``batch_size`` images at a time."""
+                        step_size: float | None = None, batch_size: int = 1000, norm: str = "linf"):
+        """(loss_sum, correct, n) as ``evaluate``, of the images after an untargeted L-inf or L2 (``norm``)
+        attack against their true labels (``adversarial`` without a random start), ``batch_size`` images at
+        a time."""
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"robust_evaluate: norm must be 'linf' or 'l2', got {norm!r}")
         n = int(labels.shape[0])
         if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
             raise ValueError("robust_evaluate: images_u8 must be uint8 with one row per label")
@@ -223,7 +251,7 @@ class Predictor:
         hits = torch.zeros((), dtype=torch.int64, device=self.device)
         for i in range(0, n, batch_size):
             y = lab[i:i + batch_size]
-            _, lp = self.adversarial(images_u8[i:i + batch_size], y, eps, steps, step_size)
+            _, lp = self.adversarial(images_u8[i:i + batch_size], y, eps, steps, step_size, norm=norm)
             loss += F.nll_loss(lp, y, reduction='none').double().sum()
             hits += (lp.argmax(dim=1) == y).sum()
         return float(loss.item()), int(hits.item()), n
@@ -307,13 +335,15 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack iterations: 1 = FGSM, more = PGD (default: 1)')
     ap.add_argument('--attack-step-size', type=float, default=None, metavar='A',
                     help='attack step in pixel units (default: E for one step, 2.5 * E / K otherwise)')
+    ap.add_argument('--attack-norm', choices=('linf', 'l2'), default='linf',
+                    help='norm of the attack radius E and of its steps (default: linf)')
     return ap
 
 
-def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int) -> str:
+def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, norm: str = "linf") -> str:
     """The ``Test set:`` line's figures (``utils.logging.test_line``) for the attacked split."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
-    return f"Adversarial set (Linf eps={eps:g}, steps={steps}): {figures}"
+    return f"Adversarial set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}): {figures}"
 
 
 def predict_main(argv=None) -> int:
@@ -337,10 +367,11 @@ def predict_main(argv=None) -> int:
               "test_loss": loss_sum / n, "correct": correct, "n": n}
     if args.attack_eps is not None:
         adv_loss, adv_correct, _ = predictor.robust_evaluate(images, data.targets, args.attack_eps, args.attack_steps,
-                                                             args.attack_step_size, args.batch_size)
-        print(adversarial_line(args.attack_eps, args.attack_steps, adv_loss / n, adv_correct, n))
+                                                             args.attack_step_size, args.batch_size,
+                                                             norm=args.attack_norm)
+        print(adversarial_line(args.attack_eps, args.attack_steps, adv_loss / n, adv_correct, n, args.attack_norm))
         record.update(adv_eps=args.attack_eps, adv_steps=args.attack_steps, adv_loss=adv_loss / n,
-                      adv_correct=adv_correct)
+                      adv_correct=adv_correct, adv_norm=args.attack_norm)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

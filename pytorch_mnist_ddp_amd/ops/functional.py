@@ -196,6 +196,51 @@ def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps
     return out.view(B, 784)
 
 
+PGD_L2_TINY = 1e-12                 # floor of both norms of the L2 step (csrc/include/kernels.h PGD_L2_TINY)
+
+
+def pgd_l2_step_reference(dx: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
+                          lo: float, hi: float) -> torch.Tensor:
+    """The L2 step of ``pgd_l2_step`` in torch ops, on any device and dtype (the CPU / fp32 path of
+    ``Predictor.adversarial``; in float64 the oracle of the kernel's tests).  All [B, 784]."""
+    n = dx.square().sum(dim=1, keepdim=True).sqrt()
+    t = x + (alpha / n.clamp_min(PGD_L2_TINY)) * dx
+    d = t - x0
+    m = d.square().sum(dim=1, keepdim=True).sqrt()
+    d = d * (eps / m.clamp_min(PGD_L2_TINY)).clamp_max(1.0)
+    return (x0 + d).clamp(lo, hi)
+
+
+def pgd_l2_step(dx: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
+                lo: float, hi: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One L2 projected-gradient step on the normalised image from one launch of ``attack_step.hip``: per
+    image, with ``g`` = ``dx`` (what ``input_grad`` returns),
+
+        t = x + alpha * g / max(|g|, TINY);  d = t - x0;  out = min(max(x0 + d * min(1, eps / max(|d|, TINY)), lo), hi)
+
+    in float32 with both L2 norms a fixed-order sum (a NaN in an image's ``g`` makes that image's ``out``
+    NaN).  ``alpha`` < 0 descends.  ``dx``, ``x``, ``x0``, ``out``: float32 [B, 784] on the GPU; ``x0`` must
+    lie in [lo, hi] for ``out`` to stay in the eps ball; ``out`` may be ``x`` itself (in place) and is
+    allocated when None."""
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("pgd_l2_step: x must be a [B, 784] tensor on the GPU")
+    B, dev = x.shape[0], x.device
+    _f32_rows("pgd_l2_step", "x", x, B, dev)
+    _f32_rows("pgd_l2_step", "x0", x0, B, dev)
+    _f32_rows("pgd_l2_step", "dx", dx, B, dev)
+    if out is None:
+        out = torch.empty(B, 784, dtype=torch.float32, device=dev)
+    else:
+        _f32_rows("pgd_l2_step", "out", out, B, dev)
+    if out.data_ptr() in (x0.data_ptr(), dx.data_ptr()):
+        raise ValueError("pgd_l2_step: out must not be x0 or dx (both are read, not written)")
+    if not (eps >= 0 and lo <= hi and alpha == alpha):
+        raise ValueError("pgd_l2_step: need eps >= 0, lo <= hi and a step that is not NaN")
+    p = native.ptr
+    _C().pgd_l2_step(p(dx), p(x), p(x0), p(out), alpha, eps, lo, hi, B, _s())
+    return out.view(B, 784)
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False) -> None:
     p = native.ptr
     _C().adadelta(p(ms.param), p(ms.grad), p(ms.square_avg), p(ms.acc_delta), p(ms.lr), ms.rho, ms.eps,
