@@ -112,6 +112,31 @@ EngineBuffers buffers_from_dict(const py::dict& d) {
     throw std::runtime_error("engine buffers: missing model/optimizer pointer");
   return b;
 }
+
+// AdadeltaArgs of a stand-alone launch from ModelState.buffers() + the optimizer scalars.  The hold
+// pointers and signal_start stay null: the completion holds wait on another stream's counters and
+// belong to the engine.
+AdadeltaArgs ada_from_dict(const py::dict& d) {
+  auto ptr = [&](const char* k) -> uintptr_t { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; };
+  AdadeltaArgs a{};
+  a.param = P<float>(ptr("param"));
+  a.grad = P<const float>(ptr("grad"));
+  a.square_avg = P<float>(ptr("square_avg"));
+  a.acc_delta = P<float>(ptr("acc_delta"));
+  a.lr = P<const float>(ptr("lr"));
+  a.rho = d["rho"].cast<float>();
+  a.eps = d["eps"].cast<float>();
+  a.weight_decay = d["weight_decay"].cast<float>();
+  a.w2f = P<uint16_t>(ptr("w2f"));
+  a.w2d = P<uint16_t>(ptr("w2d"));
+  a.w1 = P<uint16_t>(ptr("w1"));
+  a.w1t = P<uint16_t>(ptr("w1t"));
+  a.state_inc = P<StepState>(ptr("state_inc"));
+  a.wt = d.contains("wt") && d["wt"].cast<bool>() ? 1 : 0;
+  if (!a.param || !a.grad || !a.square_avg || !a.acc_delta || !a.lr || !a.w2f || !a.w2d || !a.w1 || !a.w1t)
+    throw std::runtime_error("adadelta arguments: missing model/optimizer pointer");
+  return a;
+}
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -187,12 +212,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("fc_bwd", [](uintptr_t dz1, uintptr_t p, uintptr_t pmask, uintptr_t w1t, uintptr_t h_bf, uintptr_t dl_bf,
                      uintptr_t loss_rows, uintptr_t state, uintptr_t grad, uintptr_t dyc, uintptr_t loss_log,
                      float grad_scale, float inv_batch, int B, int Bp, uintptr_t stream, int role,
-                     uintptr_t part) {
+                     uintptr_t part, py::object ada) {
     FcBwdArgs a{P<const uint16_t>(dz1), P<const uint16_t>(p), P<const uint8_t>(pmask), P<const uint16_t>(w1t),
                 P<const uint16_t>(h_bf), P<const uint16_t>(dl_bf), P<const float>(loss_rows),
                 P<const StepState>(state), P<float>(grad), P<uint8_t>(dyc), P<float>(loss_log), grad_scale,
                 inv_batch, P<float>(part)};
-    if (role < 0) launch_fc_bwd(a, B, Bp, S(stream));
+    if (!ada.is_none()) {                        // roles C + A with the fc Adadelta step in the epilogue
+      if (role >= 0) throw std::runtime_error("fc_bwd: the fused update takes no role");
+      launch_fc_wgrad_update(a, ada_from_dict(ada.cast<py::dict>()), B, Bp, S(stream));
+    } else if (role < 0) launch_fc_bwd(a, B, Bp, S(stream));
     else if (role == 3) launch_fc_bwd_dw1(a, B, Bp, S(stream));                  // role A alone, lean kernel
     else if (role == 4) launch_fc_bwd(a, B, Bp, S(stream), false, FCB_ROLE_C | FCB_ROLE_B);   // B > 1024
     else if (role == 5) launch_fc_bwd(a, B, Bp, S(stream), false, FCB_ROLE_C | FCB_ROLE_A);   // weight grads
@@ -203,13 +231,14 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("dz1"), py::arg("p"), py::arg("pmask"), py::arg("w1t"), py::arg("h_bf"), py::arg("dl_bf"),
      py::arg("loss_rows"), py::arg("state"), py::arg("grad"), py::arg("dyc"), py::arg("loss_log"),
      py::arg("grad_scale"), py::arg("inv_batch"), py::arg("B"), py::arg("Bp"), py::arg("stream"),
-     py::arg("role") = -1, py::arg("part") = 0);
+     py::arg("role") = -1, py::arg("part") = 0, py::arg("ada") = py::none());
   m.def("fc_bwd_splits", &fc_bwd_splits);
   m.attr("FCB_PART_STRIDE") = FCB_PART_STRIDE;
   m.def("conv_bwd", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t b1c,
                        uintptr_t data_u8, uintptr_t idx, int64_t idx_stride, uintptr_t state, uintptr_t c1part,
                        uintptr_t w2part, uintptr_t grad, float grad_scale, int B, uintptr_t stream,
-                       uintptr_t xin, int stages, uintptr_t c1red) {
+                       uintptr_t xin, int stages, uintptr_t c1red, int update, int upd_lo, int upd_hi,
+                       py::object ada) {
     ConvBwdArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d),
                   P<const float>(w1c), P<const float>(b1c), P<const uint8_t>(data_u8), P<const int32_t>(idx),
                   idx_stride, P<const StepState>(state), P<float>(c1part), P<float>(w2part), P<float>(grad),
@@ -220,23 +249,44 @@ PYBIND11_MODULE(_C, m) {
     if (stages <= 0 || stages > 7) throw std::runtime_error("conv_bwd: bad stage mask");
     if (stages & 1) launch_conv_dgrad(a, B, S(stream));
     if (stages & 2) launch_conv_wgrad(a, B, S(stream));
-    if (stages & 4) launch_conv_grad_reduce(a, B, S(stream));
+    // update (with the reduce stage): 0 = conv_grad_reduce, else the reduce fused with the Adadelta step:
+    // 1 = the whole single launch, 2 = reduce parts [upd_lo, upd_hi) of the conv bucket, 3 = adadelta_c1
+    if (update < 0 || update > 3 || (update && (!(stages & 4) || ada.is_none())))
+      throw std::runtime_error("conv_bwd: bad update form");
+    if ((stages & 4) && update == 0) {
+      launch_conv_grad_reduce(a, B, S(stream));
+    } else if (stages & 4) {
+      const AdadeltaArgs u = ada_from_dict(ada.cast<py::dict>());
+      if (update == 1) launch_adadelta_reduce(u, a, B, S(stream));
+      else if (update == 2) launch_adadelta_reduce_parts(u, a, B, upd_lo, upd_hi, S(stream));
+      else launch_adadelta_c1(u, a, B, S(stream));
+    }
     check_launch();
   }, py::arg("dy"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("b1c"), py::arg("data_u8"), py::arg("idx"),
      py::arg("idx_stride"), py::arg("state"), py::arg("c1part"), py::arg("w2part"), py::arg("grad"),
      py::arg("grad_scale"), py::arg("B"), py::arg("stream"), py::arg("xin") = 0, py::arg("stages") = 7,
-     py::arg("c1red") = 0);
+     py::arg("c1red") = 0, py::arg("update") = 0, py::arg("upd_lo") = 0, py::arg("upd_hi") = 0,
+     py::arg("ada") = py::none());
   m.attr("C1_PRE_SLABS") = C1_PRE_SLABS;
+  m.attr("RED_W2_PARTS") = RED_W2_PARTS;
+  m.attr("RED_ALL_PARTS") = RED_ALL_PARTS;
+  m.attr("ADA_FC_LEAN_GRID") = ADA_FC_LEAN_GRID;
+  m.attr("WT_MAX_B") = WT_MAX_B;
   m.def("adadelta", [](uintptr_t param, uintptr_t grad, uintptr_t sq, uintptr_t acc, uintptr_t lr, float rho,
                        float eps, float wd, uintptr_t w2f, uintptr_t w2d, uintptr_t w1, uintptr_t w1t,
-                       uintptr_t state_inc, int region, bool update, uintptr_t stream) {
+                       uintptr_t state_inc, int region, bool update, uintptr_t stream, int grid, bool wt) {
     AdadeltaArgs a{P<float>(param), P<const float>(grad), P<float>(sq), P<float>(acc), P<const float>(lr), rho,
                    eps, wd, P<uint16_t>(w2f), P<uint16_t>(w2d), P<uint16_t>(w1), P<uint16_t>(w1t),
                    P<StepState>(state_inc)};
-    if (update) launch_adadelta(a, region, S(stream));
+    a.wt = wt ? 1 : 0;
+    if (grid < 0) throw std::runtime_error("adadelta: negative grid");
+    if (update) launch_adadelta(a, region, S(stream), grid);   // grid > 0: the fc region's grid-stride form
     else launch_refresh_shadows(a, S(stream));
     check_launch();
-  });
+  }, py::arg("param"), py::arg("grad"), py::arg("square_avg"), py::arg("acc_delta"), py::arg("lr"), py::arg("rho"),
+     py::arg("eps"), py::arg("weight_decay"), py::arg("w2f"), py::arg("w2d"), py::arg("w1"), py::arg("w1t"),
+     py::arg("state_inc"), py::arg("region"), py::arg("update"), py::arg("stream"), py::arg("grid") = 0,
+     py::arg("wt") = false);
 
   // ---------------- single-launch inference forward ----------------
   m.attr("INFER_BANDS") = INFER_BANDS;

@@ -122,26 +122,61 @@ FC_ROLE_C, FC_ROLE_A, FC_ROLE_B, FC_DW1, FC_ROLES_CB, FC_ROLES_CA, FC_ROLES_B, F
 CONV_DGRAD, CONV_WGRAD, CONV_REDUCE, CONV_ALL = 1, 2, 4, 7      # conv_bwd stage mask
 
 
+ADA_ALL, ADA_FC, ADA_CONV = 0, 1, 2                             # adadelta_step regions (kernels.h AdadeltaRegion)
+ADA_FC_TILES = 577                  # workgroups of the fc region's full grid; fewer walk the tiles grid-stride
+RED_W2_PARTS, RED_ALL_PARTS = 289, 309                          # conv reduce parts: conv2, then conv1 (kernels.h)
+# conv_bwd(update=...): the reduce stage fused with the Adadelta step (adadelta.hip)
+UPD_WHOLE, UPD_C1 = "whole", "c1"                               # or ("parts", lo, hi)
+
+
+def _ada_args(ms, wt: bool, advance_step: bool) -> dict:
+    """AdadeltaArgs of a stand-alone launch (completion holds and start signal null: the engine's)."""
+    d = ms.buffers()
+    d.pop("state")
+    d.update(rho=ms.rho, eps=ms.eps, weight_decay=ms.weight_decay, wt=bool(wt),
+             state_inc=native.ptr(ms.state) if advance_step else 0)
+    return d
+
+
 def fc_bwd(ms, buf: StepBuffers, grad_scale: float = 1.0, loss_log: torch.Tensor | None = None,
-           role: int = -1, state: torch.Tensor | None = None) -> None:
+           role: int = -1, state: torch.Tensor | None = None, update: bool = False, wt: bool = False) -> None:
+    """``update``: roles C + A with the fc Adadelta step in their epilogues (``fc_wgrad_update``, the
+    OVERLAP step at one split; ``wt``: write-through stores).  The launcher refuses more than one split,
+    a grad scale other than 1 and a foreign grad buffer."""
     p = native.ptr
     B = buf.B
     _C().fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), p(ms.w1t), p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
                 p(state if state is not None else ms.state), p(ms.grad), p(buf.dyc), p(loss_log), grad_scale,
-                1.0 / B, B, round_up(B, 32), _s(), role=role, part=p(buf.fcpart))
+                1.0 / B, B, round_up(B, 32), _s(), role=role, part=p(buf.fcpart),
+                ada=_ada_args(ms, wt, False) if update else None)
 
 
 def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, grad_scale: float = 1.0,
              idx_stride: int = 0, stages: int = CONV_ALL, xin: torch.Tensor | None = None,
-             c1red: torch.Tensor | None = None) -> None:
+             c1red: torch.Tensor | None = None, update=None, wt: bool = False,
+             advance_step: bool = False) -> None:
     """conv2 dgrad (+ conv1 weight-gradient partials), conv2 wgrad and the partials' reduce; ``stages``
     selects the launches.  ``xin`` (fp32 [B,784]) replaces the dataset rows; with ``c1red`` (f32
-    [C1_PRE_SLABS, 320]) the dgrad stage also pre-reduces the conv1 partials and the reduce reads those."""
+    [C1_PRE_SLABS, 320]) the dgrad stage also pre-reduces the conv1 partials and the reduce reads those.
+    ``update`` replaces the reduce launch by one fused with the Adadelta step: ``UPD_WHOLE`` (the serial
+    step's single launch, which also updates the fc region from ``ms.grad``), ``("parts", lo, hi)`` (reduce
+    parts [lo, hi) of the conv bucket only) or ``UPD_C1`` (the conv1 parts on one-wave workgroups)."""
     p, o = native.ptr, ms.offsets
+    form, lo, hi = 0, 0, 0
+    if update == UPD_WHOLE:
+        form = 1
+    elif update == UPD_C1:
+        form = 3
+    elif update is not None:
+        kind, lo, hi = update
+        if kind != "parts":
+            raise ValueError(f"conv_bwd: unknown update form {update!r}")
+        form = 2
     _C().conv_bwd(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"],
                   p(ms.param) + 4 * o["conv1.bias"], p(data_u8), p(idx), idx_stride, p(ms.state),
                   p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s(), xin=p(xin), stages=stages,
-                  c1red=p(c1red))
+                  c1red=p(c1red), update=form, upd_lo=lo, upd_hi=hi,
+                  ada=_ada_args(ms, wt, advance_step) if form else None)
 
 
 def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -241,11 +276,13 @@ def pgd_l2_step(dx: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, eps: float,
     return out.view(B, 784)
 
 
-def adadelta_step(ms, region: int = 0, advance_step: bool = False) -> None:
+def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
+    """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
+    grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
     p = native.ptr
     _C().adadelta(p(ms.param), p(ms.grad), p(ms.square_avg), p(ms.acc_delta), p(ms.lr), ms.rho, ms.eps,
                   ms.weight_decay, p(ms.w2f), p(ms.w2d), p(ms.w1), p(ms.w1t),
-                  p(ms.state) if advance_step else 0, region, True, _s())
+                  p(ms.state) if advance_step else 0, region, True, _s(), grid=grid, wt=wt)
 
 
 def train_step(ms, data_u8, labels, idx, buf: StepBuffers, idx_stride: int = 0, grad_scale: float = 1.0,

@@ -772,3 +772,276 @@ def conv_hand_case(B: int):
     a1 = bf16_round(torch.randn(B, 26, 26, 32, generator=g).relu())
     imgs = forward_case(B)[0][:B]
     return dict(g=gr, code=code, a1=a1, imgs=imgs, x=normalize_u8(imgs).reshape(B, 784))
+
+
+# ---------------------------------------------------------------- optimizer-stage oracle
+# One Adadelta update on the operands the kernels read (csrc/include/device_utils.h Ada::step), the bf16 shadow
+# layouts, a model of the flat parameter layout, and the comparators shared by tests/test_optimizer_oracle_cpu.py
+# and tests/test_gpu_optimizer_stages.py.
+import numpy as np
+
+ADA_OFFS = {"fc1.weight": 0, "fc1.bias": 1179648, "fc2.weight": 1179776, "fc2.bias": 1181056,
+            "conv1.weight": 1181120, "conv1.bias": 1181440, "conv2.weight": 1181504, "conv2.bias": 1199936}
+ADA_NUMEL = {"fc1.weight": 128 * 9216, "fc1.bias": 128, "fc2.weight": 1280, "fc2.bias": 10,
+             "conv1.weight": 288, "conv1.bias": 32, "conv2.weight": 18432, "conv2.bias": 64}
+PARAM_TOTAL, OFF_CONV = 1200000, 1181120          # mnist_common.h PARAM_TOTAL, OFF_CONV1_W (the bucket split)
+ADA_ALL, ADA_FC, ADA_CONV = 0, 1, 2
+ADA_RANGE = {ADA_ALL: (0, PARAM_TOTAL), ADA_FC: (0, OFF_CONV), ADA_CONV: (OFF_CONV, PARAM_TOTAL)}
+ADA_STATE = ("param", "square_avg", "acc_delta")
+ADA_SHADOWS = ("w1", "w1t", "w2f", "w2d")
+ADA_SHADOW_OWNER = {"w1": ADA_FC, "w1t": ADA_FC, "w2f": ADA_CONV, "w2d": ADA_CONV}
+ADA_RHO, ADA_EPS = 0.9, 1e-6
+ADA_CONFIGS = ((1.0, 0.0), (0.7, 0.0), (0.7, 0.01))           # (lr, weight_decay)
+ADA_LR_GAMMA = 0.7                                            # the lr rewritten on the device before step 3
+RED_W2_PARTS, RED_ALL_PARTS = 289, 309
+# what the tests put into param / square_avg / acc_delta where a launch must not write.  Finite on purpose: the
+# kernels read-modify-write, and an update of a NaN is the same NaN (the CPU proof's fc_touches_conv1 mutation
+# passes a NaN sentinel unseen)
+ADA_SENTINEL = 4.0 / 3.0
+
+
+def ada_padding() -> torch.Tensor:
+    """Flat indices that belong to no parameter (after fc2.bias, conv1.weight and conv1.bias)."""
+    used = torch.zeros(PARAM_TOTAL, dtype=torch.bool)
+    for k, o in ADA_OFFS.items():
+        used[o:o + ADA_NUMEL[k]] = True
+    return (~used).nonzero().squeeze(1)
+
+
+def _f32(v) -> np.float32:
+    return np.float32(v)
+
+
+def stage_adadelta(p, g, sq, acc, lr, rho, eps, wd, dtype=F64):
+    """One Adadelta update in torch's documented order on fp32 operands; returns (param, square_avg, acc_delta).
+    dtype = F64: the oracle, with the scalars first rounded to fp32 (the kernel receives them as float; its
+    1 - rho is float32(1) - float32(rho)).  dtype = F32: every operation individually rounded in numpy float32,
+    no fusion, denormals kept - the emulation of Ada::step."""
+    lr, rho, eps, wd = _f32(lr), _f32(rho), _f32(eps), _f32(wd)
+    c = _f32(1) - rho
+    if dtype == F64:
+        lr, rho, eps, wd, c = float(lr), float(rho), float(eps), float(wd), float(c)
+        p, g, sq, acc = p.to(F64), g.to(F64), sq.to(F64), acc.to(F64)
+        if wd != 0:
+            g = g + wd * p
+        sq = sq * rho + c * g * g
+        d = (acc + eps).sqrt() / (sq + eps).sqrt() * g
+        return p - lr * d, sq, acc * rho + c * d * d
+    assert dtype == F32
+    p, g, sq, acc = (t.detach().contiguous().numpy().astype(np.float32, copy=True) for t in (p, g, sq, acc))
+    with np.errstate(all="ignore"):
+        if wd != 0:
+            g = g + wd * p
+        sq = sq * rho + (c * g) * g
+        sd = np.sqrt(sq + eps)
+        d = np.sqrt(acc + eps)
+        d = (d / sd) * g
+        acc = acc * rho + (c * d) * d
+        p = p + (-lr) * d
+    assert p.dtype == sq.dtype == acc.dtype == np.float32
+    return torch.from_numpy(p), torch.from_numpy(sq), torch.from_numpy(acc)
+
+
+def torch_adadelta(p, g, sq, acc, lr, rho, eps, wd, foreach=None):
+    """One step of torch.optim.Adadelta on the CPU, loaded with the same fp32 state."""
+    par = torch.nn.Parameter(p.detach().clone())
+    opt = torch.optim.Adadelta([par], lr=float(_f32(lr)), rho=rho, eps=eps, weight_decay=wd, foreach=foreach)
+    opt.state[par] = {"step": torch.tensor(0.0), "square_avg": sq.detach().clone(), "acc_delta": acc.detach().clone()}
+    par.grad = g.detach().clone()
+    opt.step()
+    st = opt.state[par]
+    return par.detach(), st["square_avg"], st["acc_delta"]
+
+
+def _shadow_layouts(fc1, c2):
+    """fc1.weight [128,9216] and conv2.weight [64,32,3,3] (any dtype) in the four shadow layouts."""
+    return {"w1": fc1.contiguous(), "w1t": fc1.t().contiguous(),
+            "w2f": c2.permute(0, 2, 3, 1).reshape(64, 9, 32).contiguous(),      # [co][tap][ci]
+            "w2d": c2.permute(2, 3, 1, 0).reshape(9, 32, 64).contiguous()}      # [tap][ci][co]
+
+
+def stage_shadows(param):
+    """The expected bf16 shadows (round to nearest even, NaN kept) of a flat fp32 parameter vector."""
+    fc1 = param[:128 * 9216].view(128, 9216)
+    o = ADA_OFFS["conv2.weight"]
+    return {k: bf16_round(v) for k, v in _shadow_layouts(fc1, param[o:o + 18432].view(64, 32, 3, 3)).items()}
+
+
+@functools.lru_cache(maxsize=None)
+def shadow_sources():
+    """Per shadow, the flat parameter index that each of its elements is a copy of."""
+    e = torch.arange(PARAM_TOTAL)
+    o = ADA_OFFS["conv2.weight"]
+    return {k: v.reshape(-1) for k, v in
+            _shadow_layouts(e[:128 * 9216].view(128, 9216), e[o:o + 18432].view(64, 32, 3, 3)).items()}
+
+
+def bits(t):
+    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32) if t.dtype == F32 else t
+
+
+def same_bits(a, b) -> bool:
+    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+
+
+def assert_shadow(got, want, what=""):
+    """Bit for bit the expected bf16 value; where that is NaN, any NaN."""
+    assert got.dtype == want.dtype == torch.bfloat16 and got.numel() == want.numel(), (what, got.dtype, got.shape)
+    got, want = got.reshape(-1), want.reshape(-1)
+    nan = torch.isnan(want)
+    bad = torch.where(nan, ~torch.isnan(got), bits(got) != bits(want))
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.numel()} shadow elements differ; first at {int(bad.nonzero()[0])}"
+
+
+def ada_eps(ref64, *fp32_results):
+    """Per tensor EPS_MARGIN x the largest |fp32 CPU - float64| over the given fp32 CPU results."""
+    return [EPS_MARGIN * max(float((r[i].to(F64) - ref64[i]).abs().max()) for r in fp32_results) for i in range(3)]
+
+
+def own_mask(lo=0, hi=0, idx=None) -> torch.Tensor:
+    """Bool mask over the flat layout: the range [lo, hi) and / or the flat indices ``idx``."""
+    m = torch.zeros(PARAM_TOTAL, dtype=torch.bool)
+    m[lo:hi] = True
+    if idx is not None:
+        m[torch.as_tensor(idx, dtype=torch.long)] = True
+    return m
+
+
+def check_adadelta_update(before, after, own, lr, wd, rho=ADA_RHO, eps=ADA_EPS, grad=None, name="adadelta"):
+    """One update of the flat elements in the bool mask ``own``: ``before`` / ``after`` hold the flat fp32 ``param``,
+    ``square_avg``, ``acc_delta`` (CPU); the gradient is ``grad`` (default ``before['grad']``).  Each tensor is held to
+    the float64 oracle within its measured eps; a zero gradient (without weight decay) leaves ``param`` bit-unchanged
+    and makes ``square_avg`` and ``acc_delta`` exactly rho x themselves.  Returns {tensor: (deviation, eps)} and, under
+    ``mismatch <tensor>``, the number of elements whose bits differ from the fp32 emulation."""
+    g = (before["grad"] if grad is None else grad)[own]
+    ops = (before["param"][own], g, before["square_avg"][own], before["acc_delta"][own])
+    assert all(torch.isfinite(t).all() for t in ops), f"{name}: non-finite operands"
+    r64 = stage_adadelta(*ops, lr, rho, eps, wd)
+    emu = stage_adadelta(*ops, lr, rho, eps, wd, dtype=F32)
+    e = ada_eps(r64, emu, torch_adadelta(*ops, lr, rho, eps, wd))
+    stats = {}
+    for i, k in enumerate(ADA_STATE):
+        got = after[k][own]
+        stats[k] = (assert_within(got, r64[i], e[i], f"{name} {k}"), e[i])
+        stats[f"mismatch {k}"] = (float((bits(got) != bits(emu[i])).sum()), 0.0)
+    if wd == 0:
+        z = g == 0
+        assert torch.equal(bits(after["param"][own])[z], bits(ops[0])[z]), f"{name}: param moved at a zero gradient"
+        for k, old in (("square_avg", ops[2]), ("acc_delta", ops[3])):
+            want = torch.from_numpy(old.numpy() * _f32(rho))
+            assert torch.equal(bits(after[k][own])[z], bits(want)[z]), f"{name}: {k} is not rho x itself at a zero gradient"
+    return stats
+
+
+def check_ownership(before, after, own, shadows_owned, grad_own=None, name="adadelta"):
+    """Outside the mask ``own``, ``param``, ``square_avg`` and ``acc_delta`` keep their bits (the caller's sentinels);
+    ``grad`` keeps its bits outside ``grad_own`` (default: everywhere); the shadows named in ``shadows_owned`` are
+    exactly stage_shadows of the launch's own ``param`` and the others keep their bits."""
+    for k in ADA_STATE:
+        assert torch.equal(bits(after[k])[~own], bits(before[k])[~own]), f"{name}: {k} was written outside its region"
+    keep = torch.ones(PARAM_TOTAL, dtype=torch.bool) if grad_own is None else ~grad_own
+    assert torch.equal(bits(after["grad"])[keep], bits(before["grad"])[keep]), f"{name}: grad was written"
+    want = stage_shadows(after["param"])
+    for k in ADA_SHADOWS:
+        if k in shadows_owned:
+            assert_shadow(after[k], want[k], f"{name} {k}")
+        else:
+            assert same_bits(after[k].reshape(-1), before[k].reshape(-1)), f"{name}: shadow {k} was written"
+
+
+def check_isolation(clean, dirty, poisoned, emu_at, name="adadelta"):
+    """``dirty`` = the launch of ``clean`` with a non-finite gradient at the flat indices ``poisoned``: exactly those
+    elements of the three tensors take the emulation's non-finite values ``emu_at`` (param is NaN), exactly their
+    shadow positions become NaN, every other element keeps the clean run's bits."""
+    idx = torch.as_tensor(poisoned, dtype=torch.long)
+    hit = torch.zeros(PARAM_TOTAL, dtype=torch.bool)
+    hit[idx] = True
+    for i, k in enumerate(ADA_STATE):
+        got, want = dirty[k][idx], emu_at[i]
+        assert not torch.isfinite(want).any(), f"{name}: the emulation stays finite in {k}"
+        ok = torch.where(torch.isnan(want), torch.isnan(got), got == want)
+        assert ok.all(), f"{name}: {k} at the poisoned elements {idx[~ok].tolist()} is {got[~ok].tolist()}"
+        assert torch.equal(bits(dirty[k])[~hit], bits(clean[k])[~hit]), f"{name}: {k} changed next to a poisoned element"
+    assert torch.isnan(dirty["param"][idx]).all(), f"{name}: param survived a non-finite gradient"
+    for k, src in shadow_sources().items():
+        h = hit[src]
+        got = dirty[k].reshape(-1)
+        assert torch.isnan(got[h]).all(), f"{name}: shadow {k} is finite at a poisoned element"
+        assert torch.equal(bits(got)[~h], bits(clean[k].reshape(-1))[~h]), f"{name}: shadow {k} changed elsewhere"
+
+
+def conv_sink_elements(lo=0, hi=RED_ALL_PARTS) -> torch.Tensor:
+    """Flat parameter indices that reduce parts [lo, hi) own (conv_grad_reduce.h): the conv2 parts conv2.weight
+    and conv2.bias, the conv1 parts conv1.weight and conv1.bias."""
+    out = []
+    if lo < RED_W2_PARTS:
+        assert lo == 0 and hi >= RED_W2_PARTS, "the tests split the parts at the conv2 / conv1 boundary only"
+        out += [torch.arange(ADA_OFFS[k], ADA_OFFS[k] + ADA_NUMEL[k]) for k in ("conv2.weight", "conv2.bias")]
+    if hi > RED_W2_PARTS:
+        assert hi == RED_ALL_PARTS and lo <= RED_W2_PARTS
+        out += [torch.arange(ADA_OFFS[k], ADA_OFFS[k] + ADA_NUMEL[k]) for k in ("conv1.weight", "conv1.bias")]
+    return torch.cat(out).sort().values
+
+
+# ---- the inputs of the optimizer-stage tests
+# square_avg = acc_delta = 0, a first step: in fc1.weight, across fc1.weight | fc1.bias, in fc2.weight, across
+# conv1.weight | padding | conv1.bias, in conv2.weight - and at every padding element
+ADA_ZERO_STATE = ((5000, 9000), (1179000, 1179700), (1180000, 1180400), (1181300, 1181460), (1185000, 1186000))
+ADA_ZERO_GRAD = ((100000, 101000), (1181000, 1181300), (1190000, 1190100))
+# the isolation test's elements: fc1 tile corners, first / last of every other tensor, the first padding element
+ADA_POISON = tuple(sorted(
+    [o * 9216 + i for o, i in ((0, 0), (63, 31), (64, 32), (127, 9215))] +
+    [ADA_OFFS[k] + j for k in ("fc1.bias", "fc2.weight", "fc2.bias", "conv1.weight", "conv1.bias", "conv2.weight",
+                               "conv2.bias") for j in (0, ADA_NUMEL[k] - 1)] +
+    [ADA_OFFS["fc2.bias"] + ADA_NUMEL["fc2.bias"]]))
+
+
+def _log_uniform(n, lo, hi, gen):
+    return torch.pow(10.0, lo + (hi - lo) * torch.rand(n, generator=gen, dtype=F64)).to(F32)
+
+
+@functools.lru_cache(maxsize=None)
+def ada_case():
+    """The seeded flat state: ``param`` a seed-1 Net (padding 0), ``square_avg`` / ``acc_delta`` 1e-12 .. 1e2 with
+    the ADA_ZERO_STATE blocks exactly 0, and three gradients of both signs with magnitudes 1e-24 .. 1e3 (so that
+    g x g is normal, denormal or 0), exactly 0 in the ADA_ZERO_GRAD blocks and of magnitude 0.1 .. 10 at the padding
+    elements (whose state is 0: a skipped padding element is off by about 1e-3)."""
+    from pytorch_mnist_ddp_amd.models.net import Net
+    torch.manual_seed(1)
+    net = Net()
+    gen = torch.Generator().manual_seed(4242)
+    param = torch.zeros(PARAM_TOTAL)
+    for k, v in net.named_parameters():
+        param[ADA_OFFS[k]:ADA_OFFS[k] + v.numel()] = v.detach().reshape(-1)
+    sq, acc = _log_uniform(PARAM_TOTAL, -12, 2, gen), _log_uniform(PARAM_TOTAL, -12, 2, gen)
+    pad, grads = ada_padding(), []
+    for a, b in ADA_ZERO_STATE:
+        sq[a:b], acc[a:b] = 0.0, 0.0
+    sq[pad], acc[pad] = 0.0, 0.0
+    for _ in range(3):
+        g = _log_uniform(PARAM_TOTAL, -24, 3, gen) * (torch.randint(0, 2, (PARAM_TOTAL,), generator=gen) * 2 - 1)
+        for a, b in ADA_ZERO_GRAD:
+            g[a:b] = 0.0
+        g[pad] = _log_uniform(len(pad), -1, 1, gen) * (torch.randint(0, 2, (len(pad),), generator=gen) * 2 - 1)
+        grads.append(g)
+    return dict(param=param, square_avg=sq, acc_delta=acc, grads=tuple(grads))
+
+
+def shadow_specials() -> torch.Tensor:
+    """fp32 values whose bf16 rounding is a corner: ties to even both ways, +-0, denormals, the largest finite fp32
+    (rounds to inf), +-inf, NaN."""
+    b = [0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000,      # ties: down to even 0x3F80, up to even 0x3F82
+         0x3F808001, 0x3F817FFF,                              # just above / below a tie
+         0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x00008000, 0x00018000, 0x007FFFFF,   # +-0, denormals
+         0x7F7FFFFF, 0xFF7FFFFF, 0x7F800000, 0xFF800000, 0x7FC00000]
+    return torch.from_numpy(np.array(b, dtype=np.uint32).view(np.float32).copy())
+
+
+# their bf16 bits (the last is any NaN)
+SHADOW_SPECIAL_BITS = (0x3F80, 0x3F82, 0xBF80, 0xBF82, 0x3F81, 0x3F81, 0, 0x8000, 0, 0x8000, 0, 2, 0x80,
+                       0x7F80, 0xFF80, 0x7F80, 0xFF80, None)
+# where the refresh test places them: fc1.weight (o, i) at the corners of the 64 x 32 update tiles, and the first
+# elements of conv2.weight (flat offsets from the tensor's start)
+SHADOW_SPECIAL_AT = {"fc1.weight": [o * 9216 + i for o in (0, 63, 64, 127) for i in (0, 31, 32, 4607, 9215)][:18],
+                     "conv2.weight": [0, 1, 8, 9, 287, 288, 289, 4000, 4001, 9215, 9216, 12345, 18000, 18142, 18143,
+                                      18144, 18430, 18431]}
