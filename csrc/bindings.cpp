@@ -351,6 +351,22 @@ PYBIND11_MODULE(_C, m) {
      py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
      "L2 projected-gradient step per image: t = x + alpha dx / |dx|; x_next = clamp(x0 + proj_eps(t - x0), lo, hi)");
 
+  // ---------------- adversarial training ----------------
+  m.attr("ADV_PHILOX_DOMAIN") = ADV_PHILOX_DOMAIN;
+  m.def("adv_init", [](uintptr_t data_u8, uintptr_t idx, int64_t idx_stride, uintptr_t labels, uintptr_t state,
+                       uintptr_t x0, uintptr_t x, uintptr_t labels_out, float eps, float lo, float hi,
+                       bool random_start, int B, uintptr_t stream) {
+    AdvInitArgs a{P<const uint8_t>(data_u8), P<const int32_t>(idx), idx_stride, P<const int32_t>(labels),
+                  P<const StepState>(state), P<float>(x0), P<float>(x), P<int32_t>(labels_out), eps, lo, hi,
+                  random_start ? 1 : 0};
+    launch_adv_init(a, B, S(stream));
+    check_launch();
+  }, py::arg("data_u8"), py::arg("idx"), py::arg("idx_stride"), py::arg("labels"), py::arg("state"), py::arg("x0"),
+     py::arg("x"), py::arg("labels_out"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("random_start"),
+     py::arg("B"), py::arg("stream"),
+     "first launch of an adversarial training step: x0 = the step's batch normalised, x = x0 or its random "
+     "start clamp(x0 + (2u - 1) eps, lo, hi), labels_out = the batch's labels");
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {
@@ -493,6 +509,11 @@ PYBIND11_MODULE(_C, m) {
       .def("fault_release", [](Engine& e, uintptr_t stream) { e.fault_release(S(stream)); })
       .def("set_schedule", &Engine::set_schedule, py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("schedule", &Engine::schedule)
+      .def("set_adversarial", &Engine::set_adversarial, py::arg("eps"), py::arg("step_size"), py::arg("steps"),
+           py::arg("random_start"), py::arg("lo"), py::arg("hi"),
+           "adversarial training step form (normalised units; steps = 0: off); SERIAL, bf16, world 1 only")
+      .def_property_readonly("adversarial_steps", &Engine::adversarial_steps)
+      .def_property_readonly("adversarial_bytes", &Engine::adversarial_bytes)
       .def("reset_counters", &Engine::reset_counters, py::call_guard<py::gil_scoped_release>())
       .def("probe_stream_handoff", &Engine::probe_stream_handoff, py::arg("timeout_s") = 2.0,
            py::call_guard<py::gil_scoped_release>())
@@ -548,6 +569,7 @@ PYBIND11_MODULE(_C, m) {
     preload_input_grad();
     preload_input_grad_step();
     preload_attack_step();
+    preload_adv_train();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -654,6 +676,7 @@ PYBIND11_MODULE(_C, m) {
     preload_input_grad();
     preload_input_grad_step();
     preload_attack_step();
+    preload_adv_train();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

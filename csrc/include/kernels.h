@@ -256,6 +256,31 @@ struct PgdL2StepArgs {
 };
 void launch_pgd_l2_step(const PgdL2StepArgs& a, int B, hipStream_t s);   // B in [1, INPUT_GRAD_MAX_B], eps >= 0
 
+// ---------------- adversarial training (adv_train.hip) ----------------
+// adv_init, the first launch of an adversarial training step: per batch row b of the step (row r = step *
+// idx_step_stride + b; image and label idx[r] of the set, or r itself without an index vector: the
+// pre-gathered epoch rows - as trunk_fwd / head_train resolve them)
+//   x0[b] = the normalised image (bitwise trunk_fwd's in-register value);  labels_out[b] = its label
+//   x[b]  = x0[b], or with random_start  min(max(x0 + (2u - 1) * eps, lo), hi),  u = (w >> 8) * 2^-24, one
+//           Philox-4x32-10 word w per element keyed by (state->seed; state->step, element) in a counter
+//           domain no dropout stream uses (layout: adv_train.hip)
+// Rows past B are not written.  x0 / x 16-byte aligned, data_u8 4-byte aligned.
+constexpr uint32_t ADV_PHILOX_DOMAIN = 0x41445631u;   // Philox counter word 1 of adv_init ("ADV1"; dropout: 0)
+constexpr int ADV_INIT_MAX_B = 1 << 20;               // 32-bit Philox counter word 0 = b * 196 + float4
+struct AdvInitArgs {
+  const uint8_t* data_u8;     // [N][784] raw rows
+  const int32_t* idx;         // optional index vector
+  int64_t idx_step_stride;
+  const int32_t* labels;      // label of data row
+  const StepState* state;     // step (row offset, Philox counter) and seed (Philox key)
+  float* x0;                  // fp32 [B][784]
+  float* x;                   // fp32 [B][784]
+  int32_t* labels_out;        // [B]
+  float eps, lo, hi;          // random start: radius and valid range, normalised units
+  int random_start;
+};
+void launch_adv_init(const AdvInitArgs& a, int B, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -326,6 +351,7 @@ void preload_f32();
 void preload_input_grad();
 void preload_input_grad_step();
 void preload_attack_step();
+void preload_adv_train();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

@@ -51,6 +51,7 @@ Engine::~Engine() {
     if (e) hipEventDestroy(e);
   if (ws_) hipFree(ws_);
   if (ws32_) hipFree(ws32_);
+  if (adv_ws_) hipFree(adv_ws_);
 }
 
 void Engine::alloc_workspace() {
@@ -188,8 +189,51 @@ void Engine::set_schedule(int s) {
   } else {
     throw std::runtime_error("engine: unknown schedule " + std::to_string(s));
   }
+  if (adv_.steps > 0) check_adversarial_scope(s);
   sched_ = s;
   reset_counters();
+}
+
+// Adversarial steps run on the compute stream alone.  The side-stream schedules update the bf16 shadows
+// (w1, w1t, w2d) under the previous step's backward, ordered against the next step's readers by hand-off
+// holds that know nothing of the attack's launches; the fp32 step has no xin form.
+void Engine::check_adversarial_scope(int sched) const {
+  if (f32_) throw std::runtime_error("engine: adversarial training is limited to the bf16 step (fp32 is not supported)");
+  if (world_ != 1 || comm_ || xgmi_)
+    throw std::runtime_error("engine: adversarial training is limited to world size 1 (no RCCL / XGMI transport)");
+  if (sched != SERIAL) {
+    static const char* names[] = {"SERIAL", "OVERLAP", "RCCL", "XGMI"};
+    throw std::runtime_error(std::string("engine: adversarial training is limited to the SERIAL schedule (not ") +
+                             (sched >= 0 && sched < 4 ? names[sched] : "?") + ")");
+  }
+}
+
+void Engine::set_adversarial(float eps, float step_size, int steps, bool random_start, float lo, float hi) {
+  if (steps < 0) throw std::runtime_error("engine: adversarial steps must be >= 0");
+  if (steps == 0) {          // off: the plain step, nothing of the attack is launched (the buffers stay)
+    adv_ = {};
+    return;
+  }
+  if (!(eps >= 0.0f) || !(step_size >= 0.0f) || !(lo <= hi))
+    throw std::runtime_error("engine: adversarial training needs eps >= 0, step_size >= 0 and lo <= hi");
+  check_adversarial_scope(sched_);
+  if (!adv_ws_) {
+    const int64_t rows = ws_align256((int64_t)max_batch_ * IMG * IMG * sizeof(float));
+    const int64_t labs = ws_align256((int64_t)round_up(max_batch_, 32) * sizeof(int32_t));
+    const int64_t total = 2 * rows + labs + ws_align256(sizeof(StepState));
+    HIP_OK(hipMalloc(&adv_ws_, total));
+    launch_fill(adv_ws_, total, 0, nullptr);
+    HIP_OK(hipStreamSynchronize(nullptr));
+    char* b = static_cast<char*>(adv_ws_);
+    adv_x0_ = reinterpret_cast<float*>(b);
+    adv_x_ = reinterpret_cast<float*>(b + rows);
+    adv_labels_ = reinterpret_cast<int32_t*>(b + 2 * rows);
+    adv_state_ = reinterpret_cast<StepState*>(b + 2 * rows + labs);
+    adv_bytes_ = total;
+    // inference semantics from the start (begin_epoch rewrites it with the epoch's seed)
+    launch_set_state(adv_state_, StepState{0, STEP_FLAG_NO_DROPOUT, 0, 0}, compute_);
+  }
+  adv_ = AdvConfig{eps, step_size, lo, hi, steps, random_start};
 }
 
 void Engine::reset_counters() {
@@ -206,6 +250,9 @@ void Engine::begin_epoch(uint64_t seed, uint64_t rng_base, int step0, int flags)
   // 24 bytes as kernel arguments, ordered on the compute stream (never inside a captured graph):
   // no host sync, so the next epoch is enqueued while the previous one still runs
   launch_set_state(buf_.state, StepState{step0, flags, seed, rng_base}, compute_);
+  // the attack's state next to it: inference semantics (no dropout), whatever the training flags
+  if (adv_.steps > 0)
+    launch_set_state(adv_state_, StepState{step0, flags | STEP_FLAG_NO_DROPOUT, seed, rng_base}, compute_);
 }
 
 void Engine::phase_begin(const char* name) {
@@ -264,7 +311,42 @@ void Engine::end_chunk() {
   cur_.side_pending = cur_.side_forked = false;
 }
 
+// The attack of an adversarial step (set_adversarial): adv_init, then per iteration the launch sequence of
+// ops/attack.py fused_adversarial on the engine's own activation buffers, under the attack's StepState.
+// BUFFERS: the attack overwrites a1_, p_, pmask_, z1part_, loss_rows_, dz1_, h_bf_, dl_bf_ and dyc_ with the
+// same kernels at the same B that the training step runs right after it, and each of those writes all it
+// owns whatever it finds there: trunk_fwd every a1 / p / pmask element of rows < B, fc1_fwd every z1part
+// slice, head_train rows < B of loss_rows / dz1 / h_bf / dl_bf and zeros in their padding rows [B, Bp),
+// fc_bwd role B every byte of every record of rows < B (rows >= B of p are masked, not read).  So every
+// buffer the training step reads is written by the training step's own launches; the attack never
+// touches grad, the partials (fcpart_, w2part_, c1part_), loss_log or the training state.
+void Engine::enqueue_attack(const TrunkFwdArgs& tf, const HeadArgs& ha, const StepInput& in, int B, int Bp) {
+  launch_adv_init(AdvInitArgs{in.data, in.idx, in.stride, in.labels, buf_.state, adv_x0_, adv_x_, adv_labels_,
+                              adv_.eps, adv_.lo, adv_.hi, adv_.random_start ? 1 : 0},
+                  B, compute_);
+  TrunkFwdArgs t = tf;
+  t.xin = adv_x_;
+  t.state = adv_state_;
+  t.wait_a = t.wait_b = nullptr;
+  t.wait_err = nullptr;
+  HeadArgs h = ha;
+  h.labels = adv_labels_; h.idx = nullptr; h.idx_step_stride = 0;
+  h.state = adv_state_; h.inv_batch = 1.0f;                 // the summed NLL, as Predictor.adversarial
+  const FcBwdArgs fb{dz1_, p_, pmask_, buf_.w1t, h_bf_, dl_bf_, loss_rows_, adv_state_, nullptr, dyc_,
+                     nullptr, 1.0f, 1.0f, fcpart_};
+  const InputGradStepArgs ig{{dyc_, a1_, buf_.w2d, t.w1c, nullptr}, adv_x_, adv_x0_, adv_x_,
+                             adv_.alpha, adv_.eps, adv_.lo, adv_.hi};
+  for (int k = 0; k < adv_.steps; ++k) {
+    launch_trunk_fwd(t, B, true, compute_);
+    launch_fc1_fwd(p_, buf_.w1, z1part_, B, compute_);
+    launch_head_train(h, B, Bp, compute_);
+    launch_fc_bwd_role(fb, B, Bp, 2, compute_);             // role B alone: the dy records
+    launch_input_grad_step(ig, B, compute_);                // x <- the projected step, in place
+  }
+}
+
 void Engine::enqueue_step(int batch, bool last) {
+  if (adv_.steps > 0) check_adversarial_scope(sched_);
   // the head scales by 1/(B*world): without a transport every rank would train alone on a gradient
   // world times too small
   if (world_ > 1 && sched_ != RCCL && sched_ != XGMI)
@@ -330,6 +412,15 @@ void Engine::enqueue_step(int batch, bool last) {
   a.cb.c1_rows = conv_dgrad_c1_rows(B);
   if (a.cb.c1_rows > C1_PRE_MIN_SLABS) a.cb.c1red = c1red_;   // large batch: conv1 partials pre-reduced
   a.cb.dgrad_full_grid = plan.dgrad_full_grid;
+
+  // ---- adversarial step (SERIAL only): the attack, then today's step on the attacked batch
+  if (adv_.steps > 0) {
+    phase_begin("attack");
+    enqueue_attack(tf, ha, in, B, Bp);
+    phase_end();
+    tf.xin = a.cb.xin = adv_x_;
+    ha.labels = adv_labels_; ha.idx = nullptr; ha.idx_step_stride = 0;
+  }
 
   // ---- forward and fc_bwd, then the schedule's tail
   if (plan.side) fork_comm_once();

@@ -114,6 +114,21 @@ class Engine {
   // aborted validation).  Detaching the xgmi communicator of the XGMI schedule unsets the schedule.
   void set_schedule(int s);
   int schedule() const { return sched_; }
+  // Adversarial training (Madry-style PGD-AT; one step with a random start: FGSM-RS).  With steps > 0 every
+  // training step becomes, all on the compute stream:
+  //   adv_init (x0 = the batch normalised, x = x0 or its random start, the batch's labels)
+  //   steps x [trunk_fwd(xin = x), fc1_fwd, head_train(gathered labels, loss scale 1), fc_bwd role B,
+  //            input_grad_step(x, x0 -> x)]          under the attack's StepState (dropout off)
+  //   today's step with xin = x (trunk_fwd, conv2_dgrad) and the gathered labels, under the training
+  //   StepState (dropout on, keyed by (seed, step)), same loss scale, update and step-counter increment
+  // eps, step_size, lo, hi in normalised units.  steps = 0 switches it off: nothing of it is launched.
+  // The buffers (x0, x, labels, the attack's StepState) are the engine's own, allocated at the first
+  // steps > 0.  Scope: SERIAL, bf16, world size 1 - anything else throws here, in set_schedule and in
+  // enqueue_step (the side-stream schedules update the shadows the attack reads under the previous step's
+  // backward).  Graphs captured in one form keep replaying that form.
+  void set_adversarial(float eps, float step_size, int steps, bool random_start, float lo, float hi);
+  int adversarial_steps() const { return adv_.steps; }
+  int64_t adversarial_bytes() const { return adv_bytes_; }   // 0 until the attack was first switched on
   void reset_counters();
   // OVERLAP / XGMI spin on one stream until the other signals; that is only deadlock-free when the
   // compute and comm streams sit on different hardware queues (HIP shares queues beyond
@@ -192,6 +207,8 @@ class Engine {
   void enqueue_eval(int n_total, int batch);
   void alloc_workspace();
   void alloc_workspace_f32();
+  void check_adversarial_scope(int sched) const;   // throws unless SERIAL, bf16, world 1
+  void enqueue_attack(const TrunkFwdArgs& tf, const HeadArgs& ha, const StepInput& in, int B, int Bp);
 
   EngineBuffers buf_;
   int max_batch_, max_test_batch_;
@@ -246,6 +263,14 @@ class Engine {
   F32Step f32ws_{};
   std::vector<hipGraphExec_t> graphs_;
   std::vector<hipGraph_t> graph_defs_;
+  // adversarial training (set_adversarial): own allocation, made at the first steps > 0
+  struct AdvConfig { float eps = 0, alpha = 0, lo = 0, hi = 0; int steps = 0; bool random_start = false; };
+  AdvConfig adv_;
+  void* adv_ws_ = nullptr;
+  int64_t adv_bytes_ = 0;
+  float *adv_x0_ = nullptr, *adv_x_ = nullptr;   // fp32 [max_batch][784]: the clean batch, the iterate
+  int32_t* adv_labels_ = nullptr;                 // [round_up(max_batch, 32)] the batch's labels
+  StepState* adv_state_ = nullptr;                // the attack's state: STEP_FLAG_NO_DROPOUT (begin_epoch)
 };
 
 }  // namespace mnist

@@ -22,6 +22,10 @@ behaviour):
 * ``--profile``: roctx ranges + per-epoch device timing; ``--json-log``: machine
   readable per-epoch metrics.
 * ``--resume``: optional checkpoint to load before training (off by default).
+* ``--adv-train-eps`` / ``--adv-train-steps`` / ``--adv-train-step-size`` / ``--adv-train-random-start``:
+  adversarial training (PGD-AT; one step with a random start: FGSM-RS), off by default.  Fused engine:
+  single GPU, bf16, inside the engine's step; ``--engine module`` / ``--no-cuda``: the batch is attacked
+  before ``model(data)``.
 """
 from __future__ import annotations
 
@@ -88,6 +92,25 @@ def _framework_flags(parser: argparse.ArgumentParser) -> None:
                    help='steps in the --profile window at the start of training (default 20)')
     g.add_argument('--json-log', default=None, help='append per-epoch JSON metrics to this file')
     g.add_argument('--resume', default=None, help='load a state_dict checkpoint before training')
+    g.add_argument('--adv-train-eps', type=float, default=None, metavar='E',
+                   help='adversarial training: train every batch after an L-inf FGSM / PGD attack of radius E on '
+                        'the current weights, in pixel units on the [0, 1] scale (default: off)')
+    g.add_argument('--adv-train-steps', type=int, default=1, metavar='K',
+                   help='adversarial training: attack iterations per step, 1 = FGSM, more = PGD (default: 1)')
+    g.add_argument('--adv-train-step-size', type=float, default=None, metavar='A',
+                   help='adversarial training: attack step in pixel units (default: E for one step, '
+                        '2.5 * E / K otherwise)')
+    g.add_argument('--adv-train-random-start', action='store_true', default=False,
+                   help='adversarial training: start the attack from a uniform draw in the eps ball')
+
+
+def adversarial_from_args(args) -> dict | None:
+    """The ``adversarial`` dict of ``FusedTrainer`` / the module loop from the ``--adv-train-*`` flags; None
+    when ``--adv-train-eps`` is absent."""
+    if getattr(args, "adv_train_eps", None) is None:
+        return None
+    return {"eps": args.adv_train_eps, "steps": args.adv_train_steps, "step_size": args.adv_train_step_size,
+            "random_start": args.adv_train_random_start}
 
 
 def build_parser(ddp: bool) -> argparse.ArgumentParser:

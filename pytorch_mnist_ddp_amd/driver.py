@@ -37,6 +37,15 @@ from .utils.profiling import PhaseTimes
 # 20-step chunks (profiles/r4/s2/ab/gs_sweep_*.txt); logged losses are read per chunk
 DEFAULT_GRAPH_STEPS = 50
 
+def _adv_record(args) -> dict:
+    """The ``adv_train_*`` keys of an epoch's JSON record: none unless ``--adv-train-eps`` was given."""
+    cfg = getattr(args, "_adversarial", None)
+    if cfg is None:
+        return {}
+    return {"adv_train_eps": cfg["eps"], "adv_train_steps": cfg["steps"], "adv_train_step_size": cfg["step_size"],
+            "adv_train_random_start": cfg["random_start"]}
+
+
 def _json_log(path, rec):
     if path:
         with open(path, "a") as f:
@@ -49,11 +58,53 @@ def _check_finite(loss: float, epoch: int, batch_idx: int) -> None:
         raise FloatingPointError(f"non-finite training loss {loss} at epoch {epoch} batch {batch_idx}")
 
 
+def module_adversarial_config(args) -> dict | None:
+    """The ``--adv-train-*`` flags checked for the module engine (the checks of ``FusedTrainer`` without
+    its world-size and dtype limits: here each rank attacks its own shard and DDP is untouched)."""
+    raw = cli.adversarial_from_args(args)
+    if raw is None:                           # (flags absent: nothing is imported or done)
+        return None
+    from .engine.trainer import adversarial_config
+    return adversarial_config(raw)
+
+
+def craft_adversarial(model, data: torch.Tensor, target: torch.Tensor, cfg: dict, generator=None) -> torch.Tensor:
+    """The training batch ``data`` (float [B,1,28,28], normalised) after the L-inf FGSM / PGD attack ``cfg``
+    (``adversarial_config``: pixel units) on the current weights against ``target``, in inference semantics:
+    no dropout is drawn, the net's mode, parameters and gradients are left as they were.
+
+    On the GPU (bf16 kernels) the native loop ``ops.attack.fused_adversarial``; on the CPU (and with
+    ``compute_dtype`` fp32) the same formula in torch ops over ``Net.forward_reference`` in eval mode
+    (``inference.reference_adversarial``).  This path is the reference the fused engine's adversarial step
+    is compared against.  ``random_start`` draws ``x0 + U(-eps, eps)`` with torch from ``generator`` (default:
+    the run's global CPU generator) and clamps it to the valid range: the same distribution as, but not
+    the bits of, the engine's in-kernel Philox draw (``adv_init``)."""
+    from .inference import adversarial_units, reference_adversarial
+    net = model.module if hasattr(model, "module") else model          # DDP wrapper: attack the net itself
+    B = data.shape[0]
+    x0 = data.detach().reshape(B, 784).to(torch.float32).contiguous()
+    eps_n, alpha_n, lo, hi = adversarial_units(cfg["eps"], cfg["steps"], cfg["step_size"])
+    x_init = None
+    if cfg["random_start"]:
+        u = torch.rand(B, 784, generator=generator, dtype=torch.float32).to(x0.device)
+        x_init = (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
+    labels = target.reshape(B).long()
+    if x0.is_cuda and net.compute_dtype == torch.bfloat16:
+        from .ops.attack import fused_adversarial
+        x_adv = fused_adversarial(net, x0, labels, eps_n, cfg["steps"], alpha_n, lo, hi, x_init)
+    else:
+        x_adv = reference_adversarial(net, x0, labels, eps_n, cfg["steps"], alpha_n, lo, hi, x_init)
+    return x_adv.detach().view(B, 1, 28, 28)
+
+
 def _train_module(args, model, device, loader, optimizer, epoch, distributed, world, rank):
     model.train()
     n_batches = len(loader)
+    adversarial = getattr(args, "_adversarial", None)
     for batch_idx, (data, target) in enumerate(loader):
         data, target = data.to(device), target.to(device)
+        if adversarial is not None:           # adversarial training: the loss below is the attacked batch's
+            data = craft_adversarial(model, data, target, adversarial)
         optimizer.zero_grad()
         output = model(data)
         loss = F.nll_loss(output, target)
@@ -95,6 +146,7 @@ def run(argv=None, ddp_script: bool = True, t_start: float | None = None, holder
     if holder is not None:
         holder["args"] = args
     args._ddp_script = ddp_script
+    args._adversarial = module_adversarial_config(args)      # --adv-train-*: None when off; ValueError early
     # is_available() brings the HIP runtime up (~60 ms) and device_count() initialises amdsmi
     # (~53 ms, measured under cProfile on the box), both on the main thread inside the timer; the
     # device nodes tell the same here, and the fused engine's HIP init runs on the prewarm thread
@@ -201,7 +253,7 @@ def _run_module(args, model, device, train_data, test_data, train_stream, test_s
             train_stream.set_epoch(epoch)
         t0 = time.perf_counter()
         _train_module(args, model, device, train_loader, optimizer, epoch, distributed, world, rank)
-        rec = {"epoch": epoch, "train_s": time.perf_counter() - t0}
+        rec = {"epoch": epoch, "train_s": time.perf_counter() - t0, **_adv_record(args)}
         if not distributed or rank == 0:
             rec["test_loss"], rec["correct"] = _test_module(model_without_ddp, device, test_loader)
         if distributed and args.check_sync:
@@ -398,7 +450,8 @@ def _run_fused(args, model, device, train_data, test_data, train_stream, test_st
                            world_size=world, rank=rank, comm=comm, seed=args.seed, graph_steps=graph_steps,
                            allreduce=allreduce, two_buckets=two_buckets,
                            fp32=getattr(args, "dtype", "bf16") == "fp32", xgmi_pending=xgmi_pending,
-                           streams=streams, rccl_pending=args._pending_comm)
+                           streams=streams, rccl_pending=args._pending_comm,
+                           adversarial=cli.adversarial_from_args(args))
     if xgmi_pending is not None:
         setup.add_info("xgmi_setup_thread_s", xgmi_pending.seconds)
     setup.mark("trainer")
@@ -480,7 +533,7 @@ def _run_fused(args, model, device, train_data, test_data, train_stream, test_st
                                       "t_start_unix": setup.origin,
                                       "trainer_ready_unix": setup.origin + setup.marks.get("trainer", 0.0)})
         rec = {"epoch": epoch, "train_s": st.train_seconds, "steps": st.steps,
-               "img_per_s": st.samples / max(st.train_seconds, 1e-9)}
+               "img_per_s": st.samples / max(st.train_seconds, 1e-9), **_adv_record(args)}
         handle = None
         if log_rank:
             consume_loader_base_seed()      # iter(test_loader)

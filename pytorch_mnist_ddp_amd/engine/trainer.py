@@ -167,6 +167,40 @@ def make_streams(dev) -> tuple:
     return pair
 
 
+ADVERSARIAL_KEYS = ("eps", "steps", "step_size", "random_start")
+
+
+def adversarial_config(adversarial: dict | None, world_size: int = 1, fp32: bool = False) -> dict | None:
+    """``FusedTrainer(adversarial=...)`` checked and completed (no GPU needed): None stays None; else a dict
+    with ``eps`` (>= 0), ``steps`` (integer >= 1, default 1), ``step_size`` (> 0 when given; default as
+    ``Predictor.adversarial``: ``eps`` for one step, ``2.5 * eps / steps`` otherwise) and ``random_start``, all
+    in pixel units on the [0, 1] scale.  ``ValueError`` for anything else, for ``world_size`` > 1 and for
+    ``fp32``: the engine's adversarial step is the SERIAL bf16 step on one GPU."""
+    if adversarial is None:
+        return None
+    unknown = sorted(set(adversarial) - set(ADVERSARIAL_KEYS))
+    if unknown or "eps" not in adversarial:
+        raise ValueError(f"adversarial: keys are {ADVERSARIAL_KEYS} (eps required), got {sorted(adversarial)}")
+    eps, steps = float(adversarial["eps"]), adversarial.get("steps", 1)
+    step_size = adversarial.get("step_size")
+    if not eps >= 0:
+        raise ValueError(f"adversarial: eps must be >= 0, got {eps}")
+    if steps != int(steps) or steps < 1:
+        raise ValueError(f"adversarial: steps must be an integer >= 1, got {steps}")
+    if step_size is not None and not step_size > 0:
+        raise ValueError(f"adversarial: step_size must be > 0, got {step_size}")
+    if world_size > 1:
+        raise ValueError("adversarial training on the fused engine is limited to world size 1 "
+                         "(--engine module attacks each rank's shard)")
+    if fp32:
+        raise ValueError("adversarial training on the fused engine is limited to the bf16 step (fp32=False)")
+    steps = int(steps)
+    if step_size is None:
+        step_size = eps if steps == 1 else 2.5 * eps / steps
+    return {"eps": eps, "steps": steps, "step_size": float(step_size),
+            "random_start": bool(adversarial.get("random_start", False))}
+
+
 class FusedTrainer:
     """``allreduce`` (DDP): "rccl", "xgmi", "auto" (default) or "fastest".  A candidate transport's
     PRODUCTION schedule - the captured chunk graph training replays - is validated on this node before
@@ -181,14 +215,21 @@ class FusedTrainer:
     (tests, bench --force-comm): at world 1, make the xGMI transport a candidate under "auto" / "fastest" too.
     ``fp32`` (``--dtype fp32``): the fp32 step of ``f32_net.hip`` (f32-input MFMA GEMMs, fp32
     activations and gradient operands) in the OVERLAP (fc update on the comm stream) or SERIAL schedule,
-    RCCL or XGMI at world > 1."""
+    RCCL or XGMI at world > 1.
+    ``adversarial`` (``adversarial_config``: ``eps``, ``steps``, ``step_size``, ``random_start`` in pixel units):
+    adversarial training - every step runs ``steps`` L-inf PGD iterations on the current weights (no dropout;
+    ``random_start``: from the in-kernel Philox draw of ``adv_init``) and trains on the attacked batch, all
+    inside the engine's step (``Engine.set_adversarial``).  Single GPU, bf16, SERIAL schedule, chosen without
+    the stream probe; the logged losses are those of the attacked batches."""
 
     def __init__(self, mstate: ModelState, train: MNISTData, test: MNISTData | None, batch_size: int,
                  test_batch_size: int, num_samples: int, world_size: int = 1, rank: int = 0,
                  comm=None, seed: int = 1, graph_steps: int = 10, dropout: bool = True,
                  two_buckets: bool = True, allreduce: str | None = None, overlap: bool = True,
                  xgmi_fuse: bool = True, probe_world1: bool = False, fp32: bool = False, xgmi_pending=None,
-                 streams=None, rccl_pending=None, hooks: dict | None = None):
+                 streams=None, rccl_pending=None, hooks: dict | None = None, adversarial: dict | None = None):
+        # checked before anything is built or loaded (ValueError: adversarial_config)
+        self.adversarial = adversarial_config(adversarial, world_size, fp32)
         C = native.load()
         self.C, self.ms = C, mstate
         # host seconds per setup phase (engine, xgmi_comm, stream_probe, validate.<transport>,
@@ -283,8 +324,14 @@ class FusedTrainer:
                or (allreduce == "xgmi" and _dist.is_initialized()))
         self._xgmi_pending = xgmi_pending        # distributed.PendingXgmiComm started by the caller
         self._rccl_pending = rccl_pending        # distributed.PendingRcclComm (maybe not started)
+        if self.adversarial is not None and ddp:
+            raise ValueError("adversarial training on the fused engine is limited to world size 1 without a "
+                             "gradient transport (no communicator, no process group with allreduce='xgmi')")
         if not ddp:
-            self._setup_single_gpu(overlap)
+            # the adversarial step runs on the compute stream alone: SERIAL, chosen without the stream probe
+            self._setup_single_gpu(overlap and self.adversarial is None)
+            if self.adversarial is not None:
+                self._engine_adversarial(self.adversarial)
         else:
             self._setup_ddp(comm, allreduce, two_buckets, probe_world1, train)
         self.setup.add("engine", time.perf_counter() - _t_init - self.setup.total())
@@ -335,6 +382,34 @@ class FusedTrainer:
         # conv2's part moved too); SERIAL when the streams share a hardware queue
         self.overlap = bool(overlap) and self._probe_streams()
         self.engine.set_schedule(C.SCHED_OVERLAP if self.overlap else C.SCHED_SERIAL)
+
+    # ------------------------------------------------------------------ adversarial training
+    def _engine_adversarial(self, cfg: dict | None) -> None:
+        """Hand ``cfg`` (pixel units) to the engine in normalised units, as ``Predictor.adversarial``
+        converts them; None switches the attack off.  Captured chunks are kept per step form."""
+        if cfg is None:
+            self.engine.set_adversarial(0.0, 0.0, 0, False, 0.0, 0.0)
+            self._use_graph_set("plain")
+            return
+        from ..inference import adversarial_units
+        eps_n, alpha_n, lo, hi = adversarial_units(cfg["eps"], cfg["steps"], cfg["step_size"])
+        self.engine.set_adversarial(eps_n, alpha_n, cfg["steps"], cfg["random_start"], lo, hi)
+        self._use_graph_set("adversarial:" + repr(sorted(cfg.items())))
+
+    def set_adversarial(self, adversarial: dict | None) -> None:
+        """Switch the adversarial step form on (a dict as the constructor's ``adversarial``), change it, or
+        off (None) on a built single-GPU trainer in the SERIAL schedule; takes effect with the next step
+        enqueued.  ``ValueError`` as the constructor's, and for a trainer in another schedule."""
+        cfg = adversarial_config(adversarial, self.world, self.fp32)
+        if cfg is not None and self.engine.schedule != self.C.SCHED_SERIAL:
+            raise ValueError("adversarial training needs the SERIAL schedule: build the trainer with "
+                             "adversarial=... or overlap=False")
+        if cfg is None and self.adversarial is None:
+            return
+        if self.adversarial is None:
+            self._graph_sets.setdefault("plain", self._graphs)     # the plain chunks captured so far
+        self._engine_adversarial(cfg)
+        self.adversarial = cfg
 
     def _use_graph_set(self, name: str) -> None:
         self._graphs = self._graph_sets.setdefault(name, {})

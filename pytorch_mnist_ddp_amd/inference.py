@@ -63,6 +63,45 @@ PIXEL_LO, PIXEL_HI = float(_PIXEL_LUT[0]), float(_PIXEL_LUT[255])
 INFER_FUSED_MAX_B = 0
 
 
+def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int,
+                          step_size: float, lo: float, hi: float, x_init: torch.Tensor | None = None,
+                          norm: str = "linf", targeted: bool = False) -> torch.Tensor:
+    """``ops.attack.fused_adversarial`` in torch ops on any device: ``steps`` projected gradient steps on the
+    summed NLL of ``labels`` through autograd over ``Net.forward_reference`` in eval mode (no dropout; the
+    net's mode is restored afterwards), from ``x_init`` (default ``x0``).  Same arguments (float32 [B, 784]
+    normalised images, normalised units), same formula, same return.  The CPU / fp32 path of
+    ``Predictor.adversarial`` and of adversarial training on the module engine."""
+    B = x0.shape[0]
+    x_adv = x0 if x_init is None else x_init
+    alpha_s = -step_size if targeted else step_size
+    was_training = net.training
+    net.eval()
+    try:
+        for _ in range(int(steps)):
+            xg = x_adv.clone().requires_grad_()
+            with torch.enable_grad():
+                lp = net.forward_reference(xg.view(B, 1, 28, 28))
+                loss = F.nll_loss(lp, labels, reduction='sum')
+                g, = torch.autograd.grad(loss, xg)
+            if norm == "l2":
+                x_adv = pgd_l2_step_reference(g, x_adv, x0, eps, alpha_s, lo, hi)
+            else:
+                t = x_adv + alpha_s * g.sign()
+                t = torch.min(torch.max(t, x0 - eps), x0 + eps)
+                x_adv = t.clamp(lo, hi)
+    finally:
+        net.train(was_training)
+    return x_adv
+
+
+def adversarial_units(eps: float, steps: int, step_size: float | None):
+    """(eps, step_size, lo, hi) in normalised units from pixel units on the [0, 1] scale, with
+    ``Predictor.adversarial``'s default step: ``eps`` for one step, ``2.5 * eps / steps`` otherwise."""
+    if step_size is None:
+        step_size = eps if steps == 1 else 2.5 * eps / steps
+    return eps / MNIST_STD, step_size / MNIST_STD, PIXEL_LO, PIXEL_HI
+
+
 class Predictor:
     def __init__(self, net: Net, dtype: str = "bf16"):
         if dtype not in ("bf16", "fp32"):
@@ -212,25 +251,8 @@ class Predictor:
             x_adv = fused_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init,
                                       norm=norm, targeted=targeted)
         else:
-            x_adv = x0 if x_init is None else x_init
-            alpha_s = -alpha_n if targeted else alpha_n
-            was_training = self.net.training
-            self.net.eval()
-            try:
-                for _ in range(int(steps)):
-                    xg = x_adv.clone().requires_grad_()
-                    with torch.enable_grad():
-                        lp = self.net.forward_reference(xg.view(B, 1, 28, 28))
-                        loss = F.nll_loss(lp, labels, reduction='sum')
-                        g, = torch.autograd.grad(loss, xg)
-                    if norm == "l2":
-                        x_adv = pgd_l2_step_reference(g, x_adv, x0, eps_n, alpha_s, lo, hi)
-                    else:
-                        t = x_adv + alpha_s * g.sign()
-                        t = torch.min(torch.max(t, x0 - eps_n), x0 + eps_n)
-                        x_adv = t.clamp(lo, hi)
-            finally:
-                self.net.train(was_training)
+            x_adv = reference_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init,
+                                          norm=norm, targeted=targeted)
         x_adv = x_adv.view(B, 1, 28, 28)
         return x_adv, self._forward(x_adv)[0]
 

@@ -276,6 +276,53 @@ def pgd_l2_step(dx: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, eps: float,
     return out.view(B, 784)
 
 
+ADV_PHILOX_DOMAIN = 0x41445631      # Philox counter word 1 of adv_init (csrc/include/kernels.h)
+
+
+def adv_init(data_u8: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor | None, state: torch.Tensor, B: int,
+             idx_stride: int = 0, eps: float = 0.0, lo: float = 0.0, hi: float = 0.0, random_start: bool = False,
+             x0: torch.Tensor | None = None, x: torch.Tensor | None = None,
+             labels_out: torch.Tensor | None = None):
+    """The first launch of an adversarial training step (``csrc/kernels/adv_train.hip``), one launch:
+    ``(x0, x, labels_out)`` for the ``B`` rows of the step ``state`` holds (row r = step * ``idx_stride`` + b;
+    image and label ``idx[r]`` of ``data_u8`` / ``labels``, or r itself when ``idx`` is None).
+
+        x0 = the normalised image (bit for bit ``inference._PIXEL_LUT[u8]``);  labels_out = its label
+        x  = x0, or with ``random_start``  min(max(x0 + (2u - 1) * eps, lo), hi),  u = (w >> 8) * 2**-24
+
+    in float32, each operation rounded on its own, ``w`` one Philox-4x32-10 word per element: word e % 4 of
+    ``philox4x32(counter = (b * 196 + e // 4, ADV_PHILOX_DOMAIN, step, 0), key = seed)``.  ``data_u8``: uint8
+    [N, 784]; ``labels`` / ``idx``: int32; ``state``: the 24-byte StepState tensor; ``eps``, ``lo``, ``hi`` in
+    normalised units.  Outputs: float32 [>= B, 784] / int32 [>= B], allocated when None; rows past ``B`` are
+    not written."""
+    dev = data_u8.device
+    if data_u8.dtype != torch.uint8 or not data_u8.is_contiguous() or data_u8.numel() % 784:
+        raise ValueError("adv_init: data_u8 must be contiguous uint8 rows of 784")
+    if labels.dtype != torch.int32 or (idx is not None and idx.dtype != torch.int32):
+        raise ValueError("adv_init: labels and idx must be int32")
+    if B < 1:
+        raise ValueError("adv_init: B must be positive")
+    if x0 is None:
+        x0 = torch.empty(B, 784, dtype=torch.float32, device=dev)
+    if x is None:
+        x = torch.empty(B, 784, dtype=torch.float32, device=dev)
+    if labels_out is None:
+        labels_out = torch.empty(B, dtype=torch.int32, device=dev)
+    for name, t in (("x0", x0), ("x", x)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < B * 784 or t.device != dev:
+            raise ValueError(f"adv_init: {name} must be contiguous float32 with at least B rows of 784")
+    if labels_out.dtype != torch.int32 or labels_out.numel() < B or labels_out.device != dev:
+        raise ValueError("adv_init: labels_out must be int32 with at least B entries")
+    if x0.data_ptr() == x.data_ptr():
+        raise ValueError("adv_init: x must not be x0")
+    if random_start and not (eps >= 0 and lo <= hi):
+        raise ValueError("adv_init: need eps >= 0 and lo <= hi")
+    p = native.ptr
+    _C().adv_init(p(data_u8), p(idx), idx_stride, p(labels), p(state), p(x0), p(x), p(labels_out), eps, lo, hi,
+                  bool(random_start), B, _s())
+    return x0, x, labels_out
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
