@@ -367,6 +367,30 @@ PYBIND11_MODULE(_C, m) {
      "first launch of an adversarial training step: x0 = the step's batch normalised, x = x0 or its random "
      "start clamp(x0 + (2u - 1) eps, lo, hi), labels_out = the batch's labels");
 
+  // ---------------- randomized smoothing ----------------
+  m.attr("SMOOTH_PHILOX_DOMAIN") = SMOOTH_PHILOX_DOMAIN;
+  m.def("smooth_noise", [](uintptr_t x_u8, uintptr_t x_f32, uintptr_t out, float sigma, uint64_t seed,
+                           int64_t sample_base, int64_t id_base, int M, int n, uintptr_t stream) {
+    if (sample_base < 0 || id_base < 0 || sample_base > 0xFFFFFFFFll || id_base > 0xFFFFFFFFll)
+      throw std::runtime_error("smooth_noise: sample_base and id_base must fit 32 bits");
+    SmoothNoiseArgs a{P<const uint8_t>(x_u8), P<const float>(x_f32), P<float>(out), nullptr, sigma, seed,
+                      (uint32_t)sample_base, (uint32_t)id_base, n};
+    launch_smooth_noise(a, M, S(stream));
+    check_launch();
+  }, py::arg("x_u8"), py::arg("x_f32"), py::arg("out"), py::arg("sigma"), py::arg("seed"), py::arg("sample_base"),
+     py::arg("id_base"), py::arg("M"), py::arg("n"), py::arg("stream"),
+     "out[i * n + s] = x0_i + sigma * z: n Gaussian-noised fp32 copies of each of M images (Philox + Box-Muller)");
+  m.def("smooth_noise_step", [](uintptr_t state, uintptr_t x0, uintptr_t x, float sigma, int B, uintptr_t stream) {
+    launch_smooth_noise_step(P<const StepState>(state), P<const float>(x0), P<float>(x), sigma, B, S(stream));
+    check_launch();
+  }, py::arg("state"), py::arg("x0"), py::arg("x"), py::arg("sigma"), py::arg("B"), py::arg("stream"),
+     "step form of smooth_noise: x[b] = x0[b] + sigma * z, counters from the StepState");
+  m.def("smooth_vote", [](uintptr_t logp, uintptr_t counts, int M, int n, bool accumulate, uintptr_t stream) {
+    launch_smooth_vote(SmoothVoteArgs{P<const float>(logp), P<int32_t>(counts), n, accumulate ? 1 : 0}, M, S(stream));
+    check_launch();
+  }, py::arg("logp"), py::arg("counts"), py::arg("M"), py::arg("n"), py::arg("accumulate"), py::arg("stream"),
+     "counts[i][argmax logp[i * n + s]] (+)= 1 over the n rows of each of M images; NaN rows vote for nothing");
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {
@@ -514,12 +538,17 @@ PYBIND11_MODULE(_C, m) {
            "adversarial training step form (normalised units; steps = 0: off); SERIAL, bf16, world 1 only")
       .def_property_readonly("adversarial_steps", &Engine::adversarial_steps)
       .def_property_readonly("adversarial_bytes", &Engine::adversarial_bytes)
+      .def("set_noise", &Engine::set_noise, py::arg("sigma"), py::arg("on") = true,
+           "Gaussian-noise training step form (sigma in normalised units; on = false: off); SERIAL, bf16, world 1 only")
+      .def_property_readonly("noise_on", &Engine::noise_on)
+      .def_property_readonly("noise_sigma", &Engine::noise_sigma)
       .def("reset_counters", &Engine::reset_counters, py::call_guard<py::gil_scoped_release>())
       .def("probe_stream_handoff", &Engine::probe_stream_handoff, py::arg("timeout_s") = 2.0,
            py::call_guard<py::gil_scoped_release>())
       .def("begin_epoch", &Engine::begin_epoch, py::arg("seed"), py::arg("rng_base"), py::arg("step0") = 0, py::arg("flags") = 0)
       .def("train_steps", &Engine::train_steps, py::call_guard<py::gil_scoped_release>())
       .def("capture_train", &Engine::capture_train)
+      .def("graph_nodes", &Engine::graph_nodes, py::arg("id"), "nodes of a captured chunk's compute-chain graph")
       .def("profile_steps", &Engine::profile_steps, py::call_guard<py::gil_scoped_release>())
       .def("gather_rows", &Engine::gather_rows, py::arg("start"), py::arg("n"))
       .def("replay", &Engine::replay, py::call_guard<py::gil_scoped_release>())
@@ -570,6 +599,7 @@ PYBIND11_MODULE(_C, m) {
     preload_input_grad_step();
     preload_attack_step();
     preload_adv_train();
+    preload_smooth();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -677,6 +707,7 @@ PYBIND11_MODULE(_C, m) {
     preload_input_grad_step();
     preload_attack_step();
     preload_adv_train();
+    preload_smooth();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

@@ -281,6 +281,39 @@ struct AdvInitArgs {
 };
 void launch_adv_init(const AdvInitArgs& a, int B, hipStream_t s);
 
+// ---------------- randomized smoothing (smooth.hip) ----------------
+// smooth_noise: out[i * n + s] = x0_i + sigma * z for image i < M, sample s < n (fp32 rows of 784, no clamp), z
+// one Box-Muller normal per element from Philox-4x32-10 words keyed by seed with counter (sample_base + s,
+// SMOOTH_PHILOX_DOMAIN, id_base + i, float4 index): a domain neither dropout stream nor adv_init uses (layout:
+// smooth.hip).  x0_i: exactly one of x_u8 (normalised in-register, bitwise trunk_fwd's value) and x_f32.
+// Rows past M * n are not written.  out / x_f32 16-byte aligned, x_u8 4-byte aligned.
+// Step form: x[b] = x0[b] + sigma * z for the B rows of a step, counter (low 32 bits of rng_base + 2 step,
+// DOMAIN, b, float4 index), key state->seed; x may be x0 (in place).
+// smooth_vote: counts[i][c] (+)= the number of rows s < n of logp[i * n + s][10] whose first maximum is class
+// c; a row holding a NaN votes for nothing.  Rows of counts past M are not written.
+constexpr uint32_t SMOOTH_PHILOX_DOMAIN = 0x534D5431u;   // Philox counter word 1 of smooth_noise ("SMT1")
+static_assert(SMOOTH_PHILOX_DOMAIN != 0u && SMOOTH_PHILOX_DOMAIN != ADV_PHILOX_DOMAIN, "a counter domain of its own");
+constexpr int64_t SMOOTH_MAX_ROWS = 1 << 23;             // one workgroup of 256 threads per row in a 32-bit grid
+struct SmoothNoiseArgs {
+  const uint8_t* x_u8;        // [M][784] raw rows, or null
+  const float* x_f32;         // [M][784] normalised rows, or null
+  float* out;                 // fp32 [M * n][784]
+  const StepState* state;     // step form only
+  float sigma;                // normalised units, >= 0
+  uint64_t seed;              // Philox key
+  uint32_t sample_base, id_base;
+  int n;                      // samples per image
+};
+void launch_smooth_noise(const SmoothNoiseArgs& a, int M, hipStream_t s);
+void launch_smooth_noise_step(const StepState* state, const float* x0, float* x, float sigma, int B, hipStream_t s);
+struct SmoothVoteArgs {
+  const float* logp;          // fp32 [M * n][10]
+  int32_t* counts;            // [M][10]
+  int n;
+  int accumulate;
+};
+void launch_smooth_vote(const SmoothVoteArgs& a, int M, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -352,6 +385,7 @@ void preload_input_grad();
 void preload_input_grad_step();
 void preload_attack_step();
 void preload_adv_train();
+void preload_smooth();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

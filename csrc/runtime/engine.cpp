@@ -190,6 +190,7 @@ void Engine::set_schedule(int s) {
     throw std::runtime_error("engine: unknown schedule " + std::to_string(s));
   }
   if (adv_.steps > 0) check_adversarial_scope(s);
+  if (noise_) check_adversarial_scope(s, "Gaussian-noise training");
   sched_ = s;
   reset_counters();
 }
@@ -197,15 +198,49 @@ void Engine::set_schedule(int s) {
 // Adversarial steps run on the compute stream alone.  The side-stream schedules update the bf16 shadows
 // (w1, w1t, w2d) under the previous step's backward, ordered against the next step's readers by hand-off
 // holds that know nothing of the attack's launches; the fp32 step has no xin form.
-void Engine::check_adversarial_scope(int sched) const {
-  if (f32_) throw std::runtime_error("engine: adversarial training is limited to the bf16 step (fp32 is not supported)");
+void Engine::check_adversarial_scope(int sched, const char* what) const {
+  const std::string w = std::string("engine: ") + what;
+  if (f32_) throw std::runtime_error(w + " is limited to the bf16 step (fp32 is not supported)");
   if (world_ != 1 || comm_ || xgmi_)
-    throw std::runtime_error("engine: adversarial training is limited to world size 1 (no RCCL / XGMI transport)");
+    throw std::runtime_error(w + " is limited to world size 1 (no RCCL / XGMI transport)");
   if (sched != SERIAL) {
     static const char* names[] = {"SERIAL", "OVERLAP", "RCCL", "XGMI"};
-    throw std::runtime_error(std::string("engine: adversarial training is limited to the SERIAL schedule (not ") +
+    throw std::runtime_error(w + " is limited to the SERIAL schedule (not " +
                              (sched >= 0 && sched < 4 ? names[sched] : "?") + ")");
   }
+}
+
+void Engine::alloc_adversarial_workspace() {
+  if (adv_ws_) return;
+  const int64_t rows = ws_align256((int64_t)max_batch_ * IMG * IMG * sizeof(float));
+  const int64_t labs = ws_align256((int64_t)round_up(max_batch_, 32) * sizeof(int32_t));
+  const int64_t total = 2 * rows + labs + ws_align256(sizeof(StepState));
+  HIP_OK(hipMalloc(&adv_ws_, total));
+  launch_fill(adv_ws_, total, 0, nullptr);
+  HIP_OK(hipStreamSynchronize(nullptr));
+  char* b = static_cast<char*>(adv_ws_);
+  adv_x0_ = reinterpret_cast<float*>(b);
+  adv_x_ = reinterpret_cast<float*>(b + rows);
+  adv_labels_ = reinterpret_cast<int32_t*>(b + 2 * rows);
+  adv_state_ = reinterpret_cast<StepState*>(b + 2 * rows + labs);
+  adv_bytes_ = total;
+  // inference semantics from the start (begin_epoch rewrites it with the epoch's seed)
+  launch_set_state(adv_state_, StepState{0, STEP_FLAG_NO_DROPOUT, 0, 0}, compute_);
+}
+
+void Engine::set_noise(float sigma, bool on) {
+  if (!on) {                 // off: the plain step, nothing of it is launched (the buffers stay)
+    noise_ = false;
+    noise_sigma_ = 0.0f;
+    return;
+  }
+  if (!(sigma >= 0.0f)) throw std::runtime_error("engine: Gaussian-noise training needs sigma >= 0");
+  if (adv_.steps > 0)
+    throw std::runtime_error("engine: Gaussian-noise training and adversarial training are mutually exclusive");
+  check_adversarial_scope(sched_, "Gaussian-noise training");
+  alloc_adversarial_workspace();
+  noise_ = true;
+  noise_sigma_ = sigma;
 }
 
 void Engine::set_adversarial(float eps, float step_size, int steps, bool random_start, float lo, float hi) {
@@ -216,23 +251,10 @@ void Engine::set_adversarial(float eps, float step_size, int steps, bool random_
   }
   if (!(eps >= 0.0f) || !(step_size >= 0.0f) || !(lo <= hi))
     throw std::runtime_error("engine: adversarial training needs eps >= 0, step_size >= 0 and lo <= hi");
+  if (noise_)
+    throw std::runtime_error("engine: adversarial training and Gaussian-noise training are mutually exclusive");
   check_adversarial_scope(sched_);
-  if (!adv_ws_) {
-    const int64_t rows = ws_align256((int64_t)max_batch_ * IMG * IMG * sizeof(float));
-    const int64_t labs = ws_align256((int64_t)round_up(max_batch_, 32) * sizeof(int32_t));
-    const int64_t total = 2 * rows + labs + ws_align256(sizeof(StepState));
-    HIP_OK(hipMalloc(&adv_ws_, total));
-    launch_fill(adv_ws_, total, 0, nullptr);
-    HIP_OK(hipStreamSynchronize(nullptr));
-    char* b = static_cast<char*>(adv_ws_);
-    adv_x0_ = reinterpret_cast<float*>(b);
-    adv_x_ = reinterpret_cast<float*>(b + rows);
-    adv_labels_ = reinterpret_cast<int32_t*>(b + 2 * rows);
-    adv_state_ = reinterpret_cast<StepState*>(b + 2 * rows + labs);
-    adv_bytes_ = total;
-    // inference semantics from the start (begin_epoch rewrites it with the epoch's seed)
-    launch_set_state(adv_state_, StepState{0, STEP_FLAG_NO_DROPOUT, 0, 0}, compute_);
-  }
+  alloc_adversarial_workspace();
   adv_ = AdvConfig{eps, step_size, lo, hi, steps, random_start};
 }
 
@@ -347,6 +369,7 @@ void Engine::enqueue_attack(const TrunkFwdArgs& tf, const HeadArgs& ha, const St
 
 void Engine::enqueue_step(int batch, bool last) {
   if (adv_.steps > 0) check_adversarial_scope(sched_);
+  if (noise_) check_adversarial_scope(sched_, "Gaussian-noise training");
   // the head scales by 1/(B*world): without a transport every rank would train alone on a gradient
   // world times too small
   if (world_ > 1 && sched_ != RCCL && sched_ != XGMI)
@@ -417,6 +440,18 @@ void Engine::enqueue_step(int batch, bool last) {
   if (adv_.steps > 0) {
     phase_begin("attack");
     enqueue_attack(tf, ha, in, B, Bp);
+    phase_end();
+    tf.xin = a.cb.xin = adv_x_;
+    ha.labels = adv_labels_; ha.idx = nullptr; ha.idx_step_stride = 0;
+  }
+
+  // ---- Gaussian-noise step (SERIAL only): the batch normalised and gathered, the noise in place, today's step
+  if (noise_) {
+    phase_begin("noise");
+    launch_adv_init(AdvInitArgs{in.data, in.idx, in.stride, in.labels, buf_.state, adv_x0_, adv_x_, adv_labels_,
+                                0.0f, 0.0f, 0.0f, 0},
+                    B, compute_);
+    launch_smooth_noise_step(buf_.state, adv_x0_, adv_x_, noise_sigma_, B, compute_);
     phase_end();
     tf.xin = a.cb.xin = adv_x_;
     ha.labels = adv_labels_; ha.idx = nullptr; ha.idx_step_stride = 0;
@@ -735,7 +770,15 @@ int Engine::add_graphs(hipGraph_t side, hipGraph_t main) {
   HIP_OK(hipGraphInstantiate(&xm, main, nullptr, nullptr, 0));
   graphs_.push_back(xm);
   side_graphs_.push_back(xs);
+  graph_main_defs_.push_back(main);
   return (int)graphs_.size() - 1;
+}
+
+int Engine::graph_nodes(int id) const {
+  if (id < 0 || id >= (int)graph_main_defs_.size()) throw std::runtime_error("engine: unknown graph id");
+  size_t n = 0;
+  HIP_OK(hipGraphGetNodes(graph_main_defs_[id], nullptr, &n));
+  return (int)n;
 }
 
 int Engine::capture_train(int n, int batch, int stride) {

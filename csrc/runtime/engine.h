@@ -129,6 +129,18 @@ class Engine {
   void set_adversarial(float eps, float step_size, int steps, bool random_start, float lo, float hi);
   int adversarial_steps() const { return adv_.steps; }
   int64_t adversarial_bytes() const { return adv_bytes_; }   // 0 until the attack was first switched on
+  // Gaussian-noise training (the base classifier randomized smoothing needs).  With it on every training step
+  // becomes, all on the compute stream:
+  //   adv_init without a random start (x0 = the batch normalised, x = x0, the batch's labels)
+  //   smooth_noise in its step form, in place: x = x0 + sigma * z, keyed by (seed; rng_base + 2 step, row, float4)
+  //   today's step with xin = x (trunk_fwd, conv2_dgrad) and the gathered labels
+  // sigma in normalised units, >= 0; on = false switches it off: nothing of it is launched.  It reuses the
+  // adversarial workspace and has exactly the scope of set_adversarial (SERIAL, bf16, world size 1; the same
+  // refusals here, in set_schedule and in enqueue_step); the two are mutually exclusive.
+  void set_noise(float sigma, bool on);
+  bool noise_on() const { return noise_; }
+  float noise_sigma() const { return noise_sigma_; }
+  int graph_nodes(int id) const;   // nodes of a captured chunk's compute-chain graph (tests: launches per chunk)
   void reset_counters();
   // OVERLAP / XGMI spin on one stream until the other signals; that is only deadlock-free when the
   // compute and comm streams sit on different hardware queues (HIP shares queues beyond
@@ -207,7 +219,8 @@ class Engine {
   void enqueue_eval(int n_total, int batch);
   void alloc_workspace();
   void alloc_workspace_f32();
-  void check_adversarial_scope(int sched) const;   // throws unless SERIAL, bf16, world 1
+  void check_adversarial_scope(int sched, const char* what = "adversarial training") const;   // SERIAL, bf16, world 1
+  void alloc_adversarial_workspace();              // x0, x, labels, the attack's StepState (first use)
   void enqueue_attack(const TrunkFwdArgs& tf, const HeadArgs& ha, const StepInput& in, int B, int Bp);
 
   EngineBuffers buf_;
@@ -263,6 +276,7 @@ class Engine {
   F32Step f32ws_{};
   std::vector<hipGraphExec_t> graphs_;
   std::vector<hipGraph_t> graph_defs_;
+  std::vector<hipGraph_t> graph_main_defs_;       // per graph id: the compute chain's definition (graph_nodes)
   // adversarial training (set_adversarial): own allocation, made at the first steps > 0
   struct AdvConfig { float eps = 0, alpha = 0, lo = 0, hi = 0; int steps = 0; bool random_start = false; };
   AdvConfig adv_;
@@ -271,6 +285,8 @@ class Engine {
   float *adv_x0_ = nullptr, *adv_x_ = nullptr;   // fp32 [max_batch][784]: the clean batch, the iterate
   int32_t* adv_labels_ = nullptr;                 // [round_up(max_batch, 32)] the batch's labels
   StepState* adv_state_ = nullptr;                // the attack's state: STEP_FLAG_NO_DROPOUT (begin_epoch)
+  bool noise_ = false;                            // Gaussian-noise training (set_noise): x0, x, labels reused
+  float noise_sigma_ = 0.0f;
 };
 
 }  // namespace mnist

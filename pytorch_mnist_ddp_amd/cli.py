@@ -26,6 +26,9 @@ behaviour):
   adversarial training (PGD-AT; one step with a random start: FGSM-RS), off by default.  Fused engine:
   single GPU, bf16, inside the engine's step; ``--engine module`` / ``--no-cuda``: the batch is attacked
   before ``model(data)``.
+* ``--noise-train-sigma``: Gaussian-noise training (the base classifier randomized smoothing certifies), off by
+  default, exclusive with ``--adv-train-eps``.  Fused engine: single GPU, bf16, inside the engine's step;
+  ``--engine module`` / ``--no-cuda``: the noise is added to the batch before ``model(data)``.
 """
 from __future__ import annotations
 
@@ -102,6 +105,9 @@ def _framework_flags(parser: argparse.ArgumentParser) -> None:
                         '2.5 * E / K otherwise)')
     g.add_argument('--adv-train-random-start', action='store_true', default=False,
                    help='adversarial training: start the attack from a uniform draw in the eps ball')
+    g.add_argument('--noise-train-sigma', type=float, default=None, metavar='S',
+                   help='Gaussian-noise training: train every batch with N(0, S^2) noise added, S in pixel units on '
+                        'the [0, 1] scale, no clamp (default: off; not together with --adv-train-eps)')
 
 
 def adversarial_from_args(args) -> dict | None:
@@ -128,4 +134,12 @@ def build_parser(ddp: bool) -> argparse.ArgumentParser:
 
 
 def parse_args(ddp: bool, argv=None) -> argparse.Namespace:
-    return build_parser(ddp).parse_args(argv)
+    parser = build_parser(ddp)
+    args = parser.parse_args(argv)
+    # the flags' cross-checks, as parser errors (exit status 2, the usage line)
+    if args.noise_train_sigma is not None:
+        if args.adv_train_eps is not None:
+            parser.error("--noise-train-sigma and --adv-train-eps are mutually exclusive")
+        if not args.noise_train_sigma >= 0:
+            parser.error(f"--noise-train-sigma must be >= 0, got {args.noise_train_sigma}")
+    return args

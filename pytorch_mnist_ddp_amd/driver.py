@@ -37,13 +37,16 @@ from .utils.profiling import PhaseTimes
 # 20-step chunks (profiles/r4/s2/ab/gs_sweep_*.txt); logged losses are read per chunk
 DEFAULT_GRAPH_STEPS = 50
 
-def _adv_record(args) -> dict:
-    """The ``adv_train_*`` keys of an epoch's JSON record: none unless ``--adv-train-eps`` was given."""
+def _step_form_record(args) -> dict:
+    """The keys an epoch's JSON record gains from the step form trained with: the four ``adv_train_*`` keys with
+    ``--adv-train-eps``, ``noise_train_sigma`` with ``--noise-train-sigma`` (the two flags exclude each other),
+    none without either."""
     cfg = getattr(args, "_adversarial", None)
-    if cfg is None:
-        return {}
-    return {"adv_train_eps": cfg["eps"], "adv_train_steps": cfg["steps"], "adv_train_step_size": cfg["step_size"],
-            "adv_train_random_start": cfg["random_start"]}
+    if cfg is not None:
+        return {"adv_train_eps": cfg["eps"], "adv_train_steps": cfg["steps"], "adv_train_step_size": cfg["step_size"],
+                "adv_train_random_start": cfg["random_start"]}
+    sigma = getattr(args, "noise_train_sigma", None)
+    return {} if sigma is None else {"noise_train_sigma": sigma}
 
 
 def _json_log(path, rec):
@@ -66,6 +69,17 @@ def module_adversarial_config(args) -> dict | None:
         return None
     from .engine.trainer import adversarial_config
     return adversarial_config(raw)
+
+
+def add_training_noise(data: torch.Tensor, sigma: float, generator=None) -> torch.Tensor:
+    """The training batch ``data`` (float [B,1,28,28], normalised) with N(0, ``sigma``^2) noise added, ``sigma`` in
+    pixel units on the [0, 1] scale, no clamp: ``data + (sigma / MNIST_STD) * randn``, the draw made with torch on
+    the CPU from ``generator`` (default: the run's global generator) and moved to the batch's device.  The module
+    engine's Gaussian-noise training; the same distribution as, but not the bits of, the fused engine's in-kernel
+    draw (``smooth_noise``)."""
+    from .data.datasets import MNIST_STD
+    z = torch.randn(data.shape, generator=generator, dtype=torch.float32)
+    return data + (sigma / MNIST_STD) * z.to(data.device)
 
 
 def craft_adversarial(model, data: torch.Tensor, target: torch.Tensor, cfg: dict, generator=None) -> torch.Tensor:
@@ -101,8 +115,11 @@ def _train_module(args, model, device, loader, optimizer, epoch, distributed, wo
     model.train()
     n_batches = len(loader)
     adversarial = getattr(args, "_adversarial", None)
+    noise_sigma = getattr(args, "noise_train_sigma", None)
     for batch_idx, (data, target) in enumerate(loader):
         data, target = data.to(device), target.to(device)
+        if noise_sigma is not None:           # Gaussian-noise training: drawn before model(data)
+            data = add_training_noise(data, noise_sigma)
         if adversarial is not None:           # adversarial training: the loss below is the attacked batch's
             data = craft_adversarial(model, data, target, adversarial)
         optimizer.zero_grad()
@@ -147,6 +164,9 @@ def run(argv=None, ddp_script: bool = True, t_start: float | None = None, holder
         holder["args"] = args
     args._ddp_script = ddp_script
     args._adversarial = module_adversarial_config(args)      # --adv-train-*: None when off; ValueError early
+    if getattr(args, "noise_train_sigma", None) is not None:  # --noise-train-sigma: checked early as well
+        from .engine.trainer import noise_config
+        noise_config(args.noise_train_sigma, cli.adversarial_from_args(args))
     # is_available() brings the HIP runtime up (~60 ms) and device_count() initialises amdsmi
     # (~53 ms, measured under cProfile on the box), both on the main thread inside the timer; the
     # device nodes tell the same here, and the fused engine's HIP init runs on the prewarm thread
@@ -253,7 +273,7 @@ def _run_module(args, model, device, train_data, test_data, train_stream, test_s
             train_stream.set_epoch(epoch)
         t0 = time.perf_counter()
         _train_module(args, model, device, train_loader, optimizer, epoch, distributed, world, rank)
-        rec = {"epoch": epoch, "train_s": time.perf_counter() - t0, **_adv_record(args)}
+        rec = {"epoch": epoch, "train_s": time.perf_counter() - t0, **_step_form_record(args)}
         if not distributed or rank == 0:
             rec["test_loss"], rec["correct"] = _test_module(model_without_ddp, device, test_loader)
         if distributed and args.check_sync:
@@ -451,7 +471,8 @@ def _run_fused(args, model, device, train_data, test_data, train_stream, test_st
                            allreduce=allreduce, two_buckets=two_buckets,
                            fp32=getattr(args, "dtype", "bf16") == "fp32", xgmi_pending=xgmi_pending,
                            streams=streams, rccl_pending=args._pending_comm,
-                           adversarial=cli.adversarial_from_args(args))
+                           adversarial=cli.adversarial_from_args(args),
+                           noise_sigma=getattr(args, "noise_train_sigma", None))
     if xgmi_pending is not None:
         setup.add_info("xgmi_setup_thread_s", xgmi_pending.seconds)
     setup.mark("trainer")
@@ -533,7 +554,7 @@ def _run_fused(args, model, device, train_data, test_data, train_stream, test_st
                                       "t_start_unix": setup.origin,
                                       "trainer_ready_unix": setup.origin + setup.marks.get("trainer", 0.0)})
         rec = {"epoch": epoch, "train_s": st.train_seconds, "steps": st.steps,
-               "img_per_s": st.samples / max(st.train_seconds, 1e-9), **_adv_record(args)}
+               "img_per_s": st.samples / max(st.train_seconds, 1e-9), **_step_form_record(args)}
         handle = None
         if log_rank:
             consume_loader_base_seed()      # iter(test_loader)

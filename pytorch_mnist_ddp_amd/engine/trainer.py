@@ -201,6 +201,27 @@ def adversarial_config(adversarial: dict | None, world_size: int = 1, fp32: bool
             "random_start": bool(adversarial.get("random_start", False))}
 
 
+def noise_config(noise_sigma, adversarial: dict | None = None, world_size: int = 1, fp32: bool = False):
+    """``FusedTrainer(noise_sigma=...)`` checked (no GPU needed): None stays None; else the float sigma >= 0, in
+    pixel units on the [0, 1] scale.  ``ValueError`` for a negative or non-finite sigma, together with
+    ``adversarial`` (the two step forms are mutually exclusive), for ``world_size`` > 1 and for ``fp32``: the
+    engine's Gaussian-noise step is the SERIAL bf16 step on one GPU, as the adversarial one."""
+    if noise_sigma is None:
+        return None
+    sigma = float(noise_sigma)
+    if not 0.0 <= sigma < float("inf"):
+        raise ValueError(f"noise_sigma must be a finite number >= 0, got {noise_sigma}")
+    if adversarial is not None:
+        raise ValueError("Gaussian-noise training and adversarial training are mutually exclusive "
+                         "(noise_sigma / --noise-train-sigma with adversarial / --adv-train-eps)")
+    if world_size > 1:
+        raise ValueError("Gaussian-noise training on the fused engine is limited to world size 1 "
+                         "(--engine module adds the noise on each rank's shard)")
+    if fp32:
+        raise ValueError("Gaussian-noise training on the fused engine is limited to the bf16 step (fp32=False)")
+    return sigma
+
+
 class FusedTrainer:
     """``allreduce`` (DDP): "rccl", "xgmi", "auto" (default) or "fastest".  A candidate transport's
     PRODUCTION schedule - the captured chunk graph training replays - is validated on this node before
@@ -227,9 +248,11 @@ class FusedTrainer:
                  comm=None, seed: int = 1, graph_steps: int = 10, dropout: bool = True,
                  two_buckets: bool = True, allreduce: str | None = None, overlap: bool = True,
                  xgmi_fuse: bool = True, probe_world1: bool = False, fp32: bool = False, xgmi_pending=None,
-                 streams=None, rccl_pending=None, hooks: dict | None = None, adversarial: dict | None = None):
-        # checked before anything is built or loaded (ValueError: adversarial_config)
+                 streams=None, rccl_pending=None, hooks: dict | None = None, adversarial: dict | None = None,
+                 noise_sigma: float | None = None):
+        # checked before anything is built or loaded (ValueError: adversarial_config, noise_config)
         self.adversarial = adversarial_config(adversarial, world_size, fp32)
+        self.noise_sigma = noise_config(noise_sigma, adversarial, world_size, fp32)
         C = native.load()
         self.C, self.ms = C, mstate
         # host seconds per setup phase (engine, xgmi_comm, stream_probe, validate.<transport>,
@@ -327,11 +350,16 @@ class FusedTrainer:
         if self.adversarial is not None and ddp:
             raise ValueError("adversarial training on the fused engine is limited to world size 1 without a "
                              "gradient transport (no communicator, no process group with allreduce='xgmi')")
+        if self.noise_sigma is not None and ddp:
+            raise ValueError("Gaussian-noise training on the fused engine is limited to world size 1 without a "
+                             "gradient transport (no communicator, no process group with allreduce='xgmi')")
         if not ddp:
-            # the adversarial step runs on the compute stream alone: SERIAL, chosen without the stream probe
-            self._setup_single_gpu(overlap and self.adversarial is None)
+            # the adversarial / noise step runs on the compute stream alone: SERIAL, chosen without the stream probe
+            self._setup_single_gpu(overlap and self.adversarial is None and self.noise_sigma is None)
             if self.adversarial is not None:
                 self._engine_adversarial(self.adversarial)
+            if self.noise_sigma is not None:
+                self._engine_noise(self.noise_sigma)
         else:
             self._setup_ddp(comm, allreduce, two_buckets, probe_world1, train)
         self.setup.add("engine", time.perf_counter() - _t_init - self.setup.total())
@@ -401,6 +429,8 @@ class FusedTrainer:
         off (None) on a built single-GPU trainer in the SERIAL schedule; takes effect with the next step
         enqueued.  ``ValueError`` as the constructor's, and for a trainer in another schedule."""
         cfg = adversarial_config(adversarial, self.world, self.fp32)
+        if cfg is not None and self.noise_sigma is not None:
+            raise ValueError("adversarial training and Gaussian-noise training are mutually exclusive")
         if cfg is not None and self.engine.schedule != self.C.SCHED_SERIAL:
             raise ValueError("adversarial training needs the SERIAL schedule: build the trainer with "
                              "adversarial=... or overlap=False")
@@ -410,6 +440,33 @@ class FusedTrainer:
             self._graph_sets.setdefault("plain", self._graphs)     # the plain chunks captured so far
         self._engine_adversarial(cfg)
         self.adversarial = cfg
+
+    # ------------------------------------------------------------------ Gaussian-noise training
+    def _engine_noise(self, sigma: float | None) -> None:
+        """Hand ``sigma`` (pixel units) to the engine in normalised units; None switches the noise off.
+        Captured chunks are kept per step form."""
+        if sigma is None:
+            self.engine.set_noise(0.0, False)
+            self._use_graph_set("plain")
+            return
+        from ..data.datasets import MNIST_STD
+        self.engine.set_noise(sigma / MNIST_STD, True)
+        self._use_graph_set("noise:" + repr(sigma))
+
+    def set_noise(self, noise_sigma: float | None) -> None:
+        """Switch the Gaussian-noise step form on (sigma in pixel units), change it, or off (None) on a built
+        single-GPU trainer in the SERIAL schedule; takes effect with the next step enqueued.  ``ValueError`` as
+        the constructor's, and for a trainer in another schedule."""
+        sigma = noise_config(noise_sigma, self.adversarial, self.world, self.fp32)
+        if sigma is not None and self.engine.schedule != self.C.SCHED_SERIAL:
+            raise ValueError("Gaussian-noise training needs the SERIAL schedule: build the trainer with "
+                             "noise_sigma=... or overlap=False")
+        if sigma is None and self.noise_sigma is None:
+            return
+        if self.noise_sigma is None:
+            self._graph_sets.setdefault("plain", self._graphs)     # the plain chunks captured so far
+        self._engine_noise(sigma)
+        self.noise_sigma = sigma
 
     def _use_graph_set(self, name: str) -> None:
         self._graphs = self._graph_sets.setdefault(name, {})

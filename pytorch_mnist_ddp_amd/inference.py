@@ -34,6 +34,15 @@ untargeted or targeted; ``eps`` and ``step_size`` in pixel units on the [0, 1] s
   ``Net.forward_reference`` in eval mode;
 * the returned log-probabilities are the predictor's own forward (above) of the adversarial images.
 
+``Predictor.smoothed_counts`` / ``Predictor.certify`` (randomized smoothing: the class counts of Gaussian-noised
+copies of an image, and the certified L2 radius they give; ``sigma`` in pixel units on the [0, 1] scale):
+
+* GPU, ``dtype="bf16"``: the native loop ``ops.smooth.fused_smooth_counts`` - per chunk of rows ``smooth_noise``
+  (``csrc/kernels/smooth.hip``) -> ``trunk_fwd`` -> ``fc1_fwd`` -> ``head_eval`` -> ``smooth_vote``;
+* CPU, or ``dtype="fp32"``: ``torch.randn`` over ``Net.forward_reference`` in eval mode (the same distribution,
+  not the same bits);
+* the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path.
+
 There is no fallback between them: a GPU predictor without the native extension raises.
 """
 from __future__ import annotations
@@ -278,6 +287,92 @@ class Predictor:
             hits += (lp.argmax(dim=1) == y).sum()
         return float(loss.item()), int(hits.item()), n
 
+    # ------------------------------------------------------------------ randomized smoothing
+    def smoothed_counts(self, x: torch.Tensor, sigma: float, n: int, seed: int = 0, ids=None,
+                        sample_base: int = 0) -> torch.Tensor:
+        """int32 [B, 10]: how many of ``n`` copies ``x + N(0, sigma^2 I)`` of each image the net classifies as
+        each class (no clamp, no dropout; the net's mode, parameters and gradients are untouched).  ``sigma`` in
+        pixel units on the [0, 1] scale; ``x``: uint8 [B,28,28] / [B,784] images or float [B,1,28,28]
+        already-normalised input.
+
+        * GPU, ``dtype="bf16"``: the native loop ``ops.smooth.fused_smooth_counts``.  Image j draws the samples
+          [``sample_base``, ``sample_base`` + n) of the in-kernel Philox stream keyed by ``seed`` under the id
+          ``ids[j]`` (default j): the noised rows of an image do not depend on the batch it arrives in, bit for bit.
+          Its counts follow except on an exact near-tie: ``fc1_fwd`` splits K 32 ways below 512 rows a launch
+          and 4 ways from there, which can move a log-probability's last bits, so the size of a launch - the
+          batch, and its last, smaller chunk - can flip such a vote.
+        * CPU, or ``dtype="fp32"``: the same algorithm with ``torch.randn`` from a generator seeded by ``seed``
+          and the image's id (advanced past the samples [0, ``sample_base``)), over ``forward_reference`` in eval
+          mode: the same distribution, NOT the same bits as the GPU path."""
+        B = self._check_input(x)
+        if not sigma > 0:
+            raise ValueError(f"smoothed_counts: sigma must be > 0, got {sigma}")
+        if n != int(n) or n < 1:
+            raise ValueError(f"smoothed_counts: n must be a positive integer, got {n}")
+        if sample_base < 0:
+            raise ValueError(f"smoothed_counts: sample_base must be >= 0, got {sample_base}")
+        if ids is not None:
+            ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+            if len(ids) != B:
+                raise ValueError(f"smoothed_counts: {len(ids)} ids for {B} images")
+        n, sigma_n = int(n), sigma / MNIST_STD
+        if self.native:
+            from .ops.smooth import fused_smooth_counts
+            if x.dtype == torch.uint8:
+                src = x.reshape(B, 784).contiguous().to(self.device)
+            else:
+                src = x.detach().reshape(B, 784).to(self.device, torch.float32).contiguous()
+            return fused_smooth_counts(self.net, src, sigma_n, n, seed, ids, sample_base)
+        if x.dtype == torch.uint8:
+            x0 = _PIXEL_LUT[x.reshape(B, 784).long().cpu()]
+        else:
+            x0 = x.detach().reshape(B, 784).to("cpu", torch.float32)
+        gen = torch.Generator()
+        counts = torch.zeros(B, 10, dtype=torch.int32)
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                for j in range(B):                                   # per image: a generator run of its own
+                    gen.manual_seed((int(seed) * 0x9E3779B97F4A7C15 + (j if ids is None else ids[j])) & (2 ** 63 - 1))
+                    for s0 in range(0, sample_base, 1000):           # past the samples [0, sample_base)
+                        torch.randn(min(1000, sample_base - s0), 784, generator=gen, dtype=torch.float32)
+                    for s0 in range(0, n, 1000):
+                        ns = min(1000, n - s0)
+                        z = torch.randn(ns, 784, generator=gen, dtype=torch.float32)
+                        rows = (x0[j] + sigma_n * z).view(ns, 1, 28, 28).to(self.device)
+                        pred = self.net.forward_reference(rows).argmax(dim=1).cpu()
+                        counts[j] += torch.bincount(pred, minlength=10).to(torch.int32)
+        finally:
+            self.net.train(was_training)
+        return counts.to(self.device)
+
+    def certify(self, x: torch.Tensor, sigma: float, n0: int = 100, n: int = 1000, alpha: float = 0.001,
+                seed: int = 0, ids=None):
+        """Randomized-smoothing certificate (Cohen, Rosenfeld, Kolter 2019) of each image: ``(classes int64 [B],
+        radii float64 [B], counts int32 [B,10])``, all on the CPU.  The smoothed classifier's class is selected
+        from the samples [0, ``n0``); its vote share is estimated from the disjoint samples [``n0``, ``n0`` + n)
+        (``counts``); ``ops.smooth.certify_from_counts`` turns both into the class and the L2 radius, in pixel
+        units as ``sigma``, within which that class is returned with probability >= 1 - ``alpha`` - or into
+        class -1 and radius 0 (abstain).  Paths, ``seed`` and ``ids`` as ``smoothed_counts``."""
+        from .ops.smooth import certify_from_counts
+        B = self._check_input(x)
+        if not sigma > 0:
+            raise ValueError(f"certify: sigma must be > 0, got {sigma}")
+        if n0 != int(n0) or n0 < 1 or n != int(n) or n < 1:
+            raise ValueError(f"certify: n0 and n must be positive integers, got {n0}, {n}")
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"certify: alpha must be in (0, 1), got {alpha}")
+        if ids is not None and len(ids) != B:
+            raise ValueError(f"certify: {len(ids)} ids for {B} images")
+        counts0 = self.smoothed_counts(x, sigma, int(n0), seed, ids, sample_base=0).cpu()
+        counts = self.smoothed_counts(x, sigma, int(n), seed, ids, sample_base=int(n0)).cpu()
+        classes = torch.empty(B, dtype=torch.int64)
+        radii = torch.empty(B, dtype=torch.float64)
+        for j in range(B):
+            classes[j], radii[j] = certify_from_counts(counts0[j].tolist(), counts[j].tolist(), sigma, alpha)
+        return classes, radii, counts
+
     # ------------------------------------------------------------------ dispatch
     def _check_input(self, x: torch.Tensor) -> int:
         B = int(x.shape[0])
@@ -359,7 +454,35 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack step in pixel units (default: E for one step, 2.5 * E / K otherwise)')
     ap.add_argument('--attack-norm', choices=('linf', 'l2'), default='linf',
                     help='norm of the attack radius E and of its steps (default: linf)')
+    ap.add_argument('--certify-sigma', type=float, default=None, metavar='S',
+                    help='also report certified accuracy under randomized smoothing with Gaussian noise of standard '
+                         'deviation S, in pixel units on the [0, 1] scale (default: off)')
+    ap.add_argument('--certify-n', type=int, default=1000, metavar='N',
+                    help='noise samples per image that estimate the vote share (default: 1000)')
+    ap.add_argument('--certify-n0', type=int, default=100, metavar='N0',
+                    help='noise samples per image that select the class (default: 100)')
+    ap.add_argument('--certify-alpha', type=float, default=0.001, metavar='A',
+                    help='failure probability of the certificate (default: 0.001)')
+    ap.add_argument('--certify-radii', type=_radii, default=(0.0, 0.25, 0.5), metavar='R1,R2,...',
+                    help='L2 radii, in pixel units, at which certified accuracy is reported (default: 0,0.25,0.5)')
+    ap.add_argument('--certify-count', type=int, default=None, metavar='M',
+                    help='certify the first M images of the split (default: all)')
+    ap.add_argument('--certify-seed', type=int, default=0, help='seed of the noise (default: 0)')
     return ap
+
+
+def _radii(text: str) -> tuple:
+    vals = tuple(float(t) for t in text.split(',') if t.strip())
+    if not vals or any(not v >= 0 for v in vals):
+        raise argparse.ArgumentTypeError(f"expected non-negative radii R1,R2,..., got {text!r}")
+    return vals
+
+
+def certified_line(sigma: float, n: int, alpha: float, radius: float, correct: int, m: int, abstained: int) -> str:
+    """One ``Certified set`` line: ``correct`` of ``m`` images are classified correctly, not abstained on and
+    certified at an L2 radius >= ``radius``."""
+    return (f"Certified set (L2 sigma={sigma:g}, n={n}, alpha={alpha:g}, radius={radius:g}): "
+            f"Accuracy: {correct}/{m} ({100.0 * correct / m:.0f}%), abstained {abstained}")
 
 
 def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, norm: str = "linf") -> str:
@@ -394,6 +517,24 @@ def predict_main(argv=None) -> int:
         print(adversarial_line(args.attack_eps, args.attack_steps, adv_loss / n, adv_correct, n, args.attack_norm))
         record.update(adv_eps=args.attack_eps, adv_steps=args.attack_steps, adv_loss=adv_loss / n,
                       adv_correct=adv_correct, adv_norm=args.attack_norm)
+    if args.certify_sigma is not None:
+        m = n if args.certify_count is None else max(1, min(n, args.certify_count))
+        classes = torch.empty(m, dtype=torch.int64)
+        radii = torch.empty(m, dtype=torch.float64)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            classes[i:j], radii[i:j], _ = predictor.certify(images[i:j], args.certify_sigma, args.certify_n0,
+                                                            args.certify_n, args.certify_alpha, args.certify_seed,
+                                                            ids=range(i, j))
+        right = classes == data.targets[:m].long().cpu()
+        abstained = int((classes < 0).sum())
+        certified = [int((right & (radii >= r)).sum()) for r in args.certify_radii]
+        for r, c in zip(args.certify_radii, certified):
+            print(certified_line(args.certify_sigma, args.certify_n, args.certify_alpha, r, c, m, abstained))
+        record.update(certify_sigma=args.certify_sigma, certify_n=args.certify_n, certify_n0=args.certify_n0,
+                      certify_alpha=args.certify_alpha, certify_seed=args.certify_seed, certify_count=m,
+                      certify_radii=list(args.certify_radii), certify_correct=certified,
+                      certify_abstained=abstained)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

@@ -323,6 +323,89 @@ def adv_init(data_u8: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor | No
     return x0, x, labels_out
 
 
+SMOOTH_PHILOX_DOMAIN = 0x534D5431   # Philox counter word 1 of smooth_noise (csrc/include/kernels.h)
+SMOOTH_MAX_ROWS = 1 << 23           # most rows (M * n, or B) one smooth_noise / smooth_vote launch takes (kernels.h)
+
+
+def smooth_noise(x: torch.Tensor, sigma: float, n: int, seed: int, sample_base: int = 0, id_base: int = 0,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """``n`` Gaussian-noised copies of each of the M images ``x`` (``csrc/kernels/smooth.hip``), one launch:
+
+        out[i * n + s] = x0_i + sigma * z          float32 [M * n, 784], no clamp
+
+    ``x``: uint8 [M, 784] raw rows (normalised in the kernel, bit for bit ``inference._PIXEL_LUT[u8]``) or
+    float32 [M, 784] already-normalised rows; ``sigma`` >= 0 in normalised units.  ``z``: Box-Muller normals
+    from ``philox4x32(counter = (sample_base + s, SMOOTH_PHILOX_DOMAIN, id_base + i, e // 4), key = seed)``:
+    words (0, 1) give elements 4v, 4v + 1 (cos, sin), words (2, 3) elements 4v + 2, 4v + 3.  A row depends on
+    (seed, image id, sample index, sigma, x0) alone.  ``out``: float32 with at least M * n rows of 784,
+    allocated when None; rows past M * n are not written.  One launch takes at most ``SMOOTH_MAX_ROWS`` = 2**23
+    rows (one workgroup per row in a 32-bit grid): ``ValueError`` beyond, chunk as ``ops.smooth`` does."""
+    if x.dim() != 2 or x.shape[1] != 784 or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous():
+        raise ValueError("smooth_noise: x must be contiguous uint8 or float32 [M, 784]")
+    M, n = x.shape[0], int(n)
+    if M < 1 or n < 1:
+        raise ValueError("smooth_noise: M and n must be positive")
+    if M * n > SMOOTH_MAX_ROWS:
+        raise ValueError(f"smooth_noise: M * n = {M * n} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    if not sigma >= 0:
+        raise ValueError(f"smooth_noise: sigma must be >= 0, got {sigma}")
+    if sample_base < 0 or sample_base + n > 1 << 32 or id_base < 0 or id_base + M > 1 << 32:
+        raise ValueError("smooth_noise: sample_base + n and id_base + M must not exceed 2**32")
+    if out is None:
+        out = torch.empty(M * n, 784, dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < M * n * 784 or out.device != x.device:
+        raise ValueError("smooth_noise: out must be contiguous float32 with at least M * n rows of 784")
+    p = native.ptr
+    u8 = x.dtype == torch.uint8
+    _C().smooth_noise(p(x) if u8 else 0, 0 if u8 else p(x), p(out), float(sigma), int(seed) & (2 ** 64 - 1),
+                      int(sample_base), int(id_base), M, n, _s())
+    return out
+
+
+def smooth_noise_step(state: torch.Tensor, x0: torch.Tensor, sigma: float, B: int,
+                      x: torch.Tensor | None = None) -> torch.Tensor:
+    """The step form of ``smooth_noise``: ``x[b] = x0[b] + sigma * z`` for the ``B`` rows of the step ``state``
+    holds, counter ``(low 32 bits of rng_base + 2 * step, SMOOTH_PHILOX_DOMAIN, b, e // 4)``, key the state's
+    seed.  ``x`` may be ``x0`` (in place); allocated when None.  Rows past ``B`` are not written.  ``B`` is at
+    most ``SMOOTH_MAX_ROWS`` = 2**23 (``ValueError`` beyond)."""
+    if x0.dtype != torch.float32 or not x0.is_contiguous() or x0.numel() < B * 784 or B < 1:
+        raise ValueError("smooth_noise_step: x0 must be contiguous float32 with at least B >= 1 rows of 784")
+    if B > SMOOTH_MAX_ROWS:
+        raise ValueError(f"smooth_noise_step: B = {B} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    if not sigma >= 0:
+        raise ValueError(f"smooth_noise_step: sigma must be >= 0, got {sigma}")
+    if x is None:
+        x = torch.empty(B, 784, dtype=torch.float32, device=x0.device)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < B * 784 or x.device != x0.device:
+        raise ValueError("smooth_noise_step: x must be contiguous float32 with at least B rows of 784")
+    p = native.ptr
+    _C().smooth_noise_step(p(state), p(x0), p(x), float(sigma), B, _s())
+    return x
+
+
+def smooth_vote(logp: torch.Tensor, M: int, n: int, counts: torch.Tensor | None = None,
+                accumulate: bool = False) -> torch.Tensor:
+    """The vote of randomized smoothing, one launch: ``counts[i, c]`` = the number of rows ``s < n`` of
+    ``logp[i * n + s]`` (float32 [>= M * n, 10]) whose argmax is class c - the first maximum wins a tie, a row
+    holding a NaN votes for nothing.  ``accumulate``: add to ``counts`` (int32 [>= M, 10]; required then)
+    instead of overwriting it.  Rows of ``counts`` past ``M`` are not written.  One launch takes at most
+    ``SMOOTH_MAX_ROWS`` = 2**23 rows M * n (``ValueError`` beyond; accumulate over several launches)."""
+    if logp.dtype != torch.float32 or not logp.is_contiguous() or M < 1 or n < 1 or logp.numel() < M * n * NCLS:
+        raise ValueError("smooth_vote: logp must be contiguous float32 with at least M * n >= 1 rows of 10")
+    if M * n > SMOOTH_MAX_ROWS:
+        raise ValueError(f"smooth_vote: M * n = {M * n} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    if counts is None:
+        if accumulate:
+            raise ValueError("smooth_vote: accumulate needs counts")
+        counts = torch.empty(M, NCLS, dtype=torch.int32, device=logp.device)
+    if counts.dtype != torch.int32 or not counts.is_contiguous() or counts.numel() < M * NCLS \
+            or counts.device != logp.device:
+        raise ValueError("smooth_vote: counts must be contiguous int32 with at least M rows of 10")
+    p = native.ptr
+    _C().smooth_vote(p(logp), p(counts), M, int(n), bool(accumulate), _s())
+    return counts
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
