@@ -391,6 +391,32 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("logp"), py::arg("counts"), py::arg("M"), py::arg("n"), py::arg("accumulate"), py::arg("stream"),
      "counts[i][argmax logp[i * n + s]] (+)= 1 over the n rows of each of M images; NaN rows vote for nothing");
 
+  // ---------------- attribution ----------------
+  m.attr("ATTR_MAX_STEPS") = ATTR_MAX_STEPS;
+  m.attr("ATTR_FINISH_NONE") = (int)ATTR_FINISH_NONE;
+  m.attr("ATTR_FINISH_SCALE") = (int)ATTR_FINISH_SCALE;
+  m.attr("ATTR_FINISH_PATH") = (int)ATTR_FINISH_PATH;
+  m.def("attr_path", [](uintptr_t x_u8, uintptr_t x_f32, uintptr_t base, float base_value, uintptr_t out,
+                        int sample_base, int n_total, int M, int ns, uintptr_t stream) {
+    AttrPathArgs a{P<const uint8_t>(x_u8), P<const float>(x_f32), P<const float>(base), base_value, P<float>(out),
+                   sample_base, n_total, ns};
+    launch_attr_path(a, M, S(stream));
+    check_launch();
+  }, py::arg("x_u8"), py::arg("x_f32"), py::arg("base"), py::arg("base_value"), py::arg("out"),
+     py::arg("sample_base"), py::arg("n_total"), py::arg("M"), py::arg("ns"), py::arg("stream"),
+     "out[i * ns + s] = b_i + alpha (x_i - b_i), alpha = (sample_base + s + 1/2) / n_total: the integration path's rows");
+  m.def("attr_reduce", [](uintptr_t dx, uintptr_t acc, uintptr_t out, uintptr_t x_u8, uintptr_t x_f32, uintptr_t base,
+                          float base_value, float scale, int M, int ns, bool accumulate, int finish,
+                          uintptr_t stream) {
+    AttrReduceArgs a{P<const float>(dx), P<float>(acc), P<float>(out), P<const uint8_t>(x_u8), P<const float>(x_f32),
+                     P<const float>(base), base_value, scale, ns, accumulate ? 1 : 0, finish};
+    launch_attr_reduce(a, M, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("acc"), py::arg("out"), py::arg("x_u8"), py::arg("x_f32"), py::arg("base"),
+     py::arg("base_value"), py::arg("scale"), py::arg("M"), py::arg("ns"), py::arg("accumulate"), py::arg("finish"),
+     py::arg("stream"),
+     "acc[i] (+)= the sum of dx[i * ns + s] in ascending s; finish: out = acc * scale [* (x_i - b_i)]");
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {
@@ -600,6 +626,7 @@ PYBIND11_MODULE(_C, m) {
     preload_attack_step();
     preload_adv_train();
     preload_smooth();
+    preload_attr();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -708,6 +735,7 @@ PYBIND11_MODULE(_C, m) {
     preload_attack_step();
     preload_adv_train();
     preload_smooth();
+    preload_attr();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

@@ -314,6 +314,44 @@ struct SmoothVoteArgs {
 };
 void launch_smooth_vote(const SmoothVoteArgs& a, int M, hipStream_t s);
 
+// ---------------- attribution: integrated gradients, SmoothGrad (attr.hip) ----------------
+// attr_path: out[i * ns + s] = b_i + alpha * (x_i - b_i) for image i < M, sample s < ns (fp32 rows of 784), alpha =
+// (float(sample_base + s) + 0.5f) / float(n_total): the midpoints of n_total equal steps from the baseline b_i to
+// the image x_i.  x_i: exactly one of x_u8 (normalised in-register, bitwise trunk_fwd's value) and x_f32; b_i: the
+// fp32 rows `base`, or the scalar base_value when base is null.  Each operation rounded on its own.  Rows past
+// M * ns are not written.  out / x_f32 / base 16-byte aligned, x_u8 4-byte aligned.
+// attr_reduce: acc[i] (+)= sum over s < ns of dx[i * ns + s], per element in ascending s in fp32, from the stored
+// acc (accumulate) or from 0: the same bits under any chunking of an image's samples over accumulating launches.
+// finish (after the last add): ATTR_FINISH_SCALE stores out = acc * scale, ATTR_FINISH_PATH out = (acc * scale) *
+// (x_i - b_i) with x_i, b_i as above; ATTR_FINISH_NONE stores the running sum to acc.  out may alias acc.  Rows of
+// acc / out past M are not written.  No atomics.
+constexpr int ATTR_MAX_STEPS = 1 << 24;                  // n_total: every sample index is an exact float
+enum AttrFinish { ATTR_FINISH_NONE = 0, ATTR_FINISH_SCALE = 1, ATTR_FINISH_PATH = 2 };
+struct AttrPathArgs {
+  const uint8_t* x_u8;        // [M][784] raw rows, or null
+  const float* x_f32;         // [M][784] normalised rows, or null
+  const float* base;          // fp32 [M][784] baseline rows, or null: base_value everywhere
+  float base_value;           // normalised units
+  float* out;                 // fp32 [M * ns][784]
+  int sample_base, n_total;   // this launch holds the samples [sample_base, sample_base + ns) of n_total
+  int ns;                     // samples per image in this launch
+};
+void launch_attr_path(const AttrPathArgs& a, int M, hipStream_t s);
+struct AttrReduceArgs {
+  const float* dx;            // fp32 [M * ns][784] gradient rows
+  float* acc;                 // fp32 [M][784] running sums
+  float* out;                 // fp32 [M][784] (finish); may be acc
+  const uint8_t* x_u8;        // ATTR_FINISH_PATH: the image and the baseline, as AttrPathArgs
+  const float* x_f32;
+  const float* base;
+  float base_value;
+  float scale;                // -1 / n as a float
+  int ns;
+  int accumulate;
+  int finish;                 // AttrFinish
+};
+void launch_attr_reduce(const AttrReduceArgs& a, int M, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -386,6 +424,7 @@ void preload_input_grad_step();
 void preload_attack_step();
 void preload_adv_train();
 void preload_smooth();
+void preload_attr();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

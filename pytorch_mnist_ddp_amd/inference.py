@@ -43,6 +43,15 @@ copies of an image, and the certified L2 radius they give; ``sigma`` in pixel un
   not the same bits);
 * the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path.
 
+``Predictor.attribute`` (integrated gradients and SmoothGrad of log p_y(x): n gradient rows per image, reduced;
+``sigma`` and scalar baselines in pixel units on the [0, 1] scale):
+
+* GPU, ``dtype="bf16"``: the native loop ``ops.attribute.fused_attribution`` - per chunk of rows ``attr_path``
+  (``csrc/kernels/attr.hip``) or ``smooth_noise`` -> ``trunk_fwd`` -> ``fc1_fwd`` -> ``head_train`` -> ``fc_bwd``
+  (role B only) -> ``input_grad`` -> ``attr_reduce`` (``csrc/kernels/attr.hip``, accumulating in a fixed order);
+* CPU, or ``dtype="fp32"``: ``reference_attribution``, the same formulas over autograd through
+  ``Net.forward_reference`` in eval mode (SmoothGrad: the same distribution, not the same bits).
+
 There is no fallback between them: a GPU predictor without the native extension raises.
 """
 from __future__ import annotations
@@ -54,9 +63,9 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
-from .data.datasets import MNIST_STD, load_mnist, normalize_u8
+from .data.datasets import MNIST_MEAN, MNIST_STD, load_mnist, normalize_u8
 from .models.net import Net
-from .ops.functional import PGD_L2_TINY, pgd_l2_step_reference
+from .ops.functional import PGD_L2_TINY, attr_path_reference, attr_reduce_reference, pgd_l2_step_reference
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -101,6 +110,68 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
     finally:
         net.train(was_training)
     return x_adv
+
+
+ATTRIBUTION_METHODS = ("integrated_gradients", "smoothgrad")
+_REF_ROWS = 1000                    # rows per forward / backward (and per generator draw) of the torch paths
+
+
+def _smooth_generator_seed(seed: int, image_id: int) -> int:
+    """The seed of an image's ``torch.Generator`` on the torch paths of ``smoothed_counts`` and SmoothGrad."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + int(image_id)) & (2 ** 63 - 1)
+
+
+def reference_attribution(net: Net, x0: torch.Tensor, labels: torch.Tensor, method: str, n: int, base=0.0,
+                          sigma_n: float = 0.0, seed: int = 0, ids=None) -> torch.Tensor:
+    """``ops.attribute.fused_attribution`` in torch ops on any device: float32 [B, 784] attribution of
+    log p_labels(x0), with g = d NLL / d x by autograd over ``Net.forward_reference`` in eval mode (the net's mode
+    is restored afterwards):
+
+        "integrated_gradients":  -(x0 - b) * (1/n) * sum_s g(b + alpha_s (x0 - b)),  alpha_s = (s + 1/2) / n
+        "smoothgrad":            -(1/n) * sum_s g(x0 + sigma_n z_s)
+
+    ``x0``: float32 [B, 784] normalised images; ``base``: a float or float32 [B, 784] (normalised units).  The
+    path rows, the sum in ascending s, the scale float32(-1/n) and the product are ``attr_path_reference`` /
+    ``attr_reduce_reference``: the arithmetic of the kernels.  Image j is processed alone, ``_REF_ROWS`` rows at a
+    time; its SmoothGrad noise is ``torch.randn`` from a generator seeded by ``seed`` and ``ids[j]`` (default j)
+    as ``Predictor.smoothed_counts`` seeds it: the same distribution as the GPU path, not the same bits.  The CPU /
+    fp32 path of ``Predictor.attribute`` and the reference of its GPU tests."""
+    import numpy as np
+    if method not in ATTRIBUTION_METHODS:
+        raise ValueError(f"reference_attribution: method must be one of {ATTRIBUTION_METHODS}, got {method!r}")
+    path = method == "integrated_gradients"
+    B, n, dev = x0.shape[0], int(n), x0.device
+    xc = x0.detach().to("cpu", torch.float32).reshape(B, 784)
+    bc = base.detach().to("cpu", torch.float32).reshape(B, 784) if isinstance(base, torch.Tensor) else None
+    lab = labels.reshape(B).long().to(dev)
+    scale = float(np.float32(-1.0) / np.float32(n))
+    out = torch.empty(B, 784, dtype=torch.float32)
+    gen = torch.Generator()
+    was_training = net.training
+    net.eval()
+    try:
+        for j in range(B):
+            bj = float(base) if bc is None else bc[j:j + 1]
+            if not path:
+                gen.manual_seed(_smooth_generator_seed(seed, j if ids is None else ids[j]))
+            acc = None
+            for s0 in range(0, n, _REF_ROWS):
+                ns = min(_REF_ROWS, n - s0)
+                if path:
+                    rows = torch.from_numpy(attr_path_reference(xc[j:j + 1], n, s0, ns, bj))
+                else:
+                    rows = xc[j] + sigma_n * torch.randn(ns, 784, generator=gen, dtype=torch.float32)
+                xg = rows.to(dev).requires_grad_()
+                with torch.enable_grad():
+                    lp = net.forward_reference(xg.view(ns, 1, 28, 28))
+                    g, = torch.autograd.grad(F.nll_loss(lp, lab[j].expand(ns), reduction='sum'), xg)
+                last = s0 + ns == n
+                acc = attr_reduce_reference(g, 1, ns, acc, scale if last else None,
+                                            xc[j:j + 1] if path and last else None, bj)
+            out[j] = torch.from_numpy(acc[0])
+    finally:
+        net.train(was_training)
+    return out.to(dev)
 
 
 def adversarial_units(eps: float, steps: int, step_size: float | None):
@@ -373,6 +444,81 @@ class Predictor:
             classes[j], radii[j] = certify_from_counts(counts0[j].tolist(), counts[j].tolist(), sigma, alpha)
         return classes, radii, counts
 
+    # ------------------------------------------------------------------ attribution
+    def attribute(self, x: torch.Tensor, labels: torch.Tensor | None = None, method: str = "integrated_gradients",
+                  steps: int = 32, baseline=None, sigma: float = 0.15, seed: int = 0, ids=None):
+        """(attr, log_probs): float32 [B,1,28,28] attribution of log p_y(x) to the NORMALISED input and the float32
+        [B,10] log-probabilities of the clean input.  y is ``labels`` ([B] integers), or the class predicted on the
+        clean input when ``labels`` is None.  With g = d NLL_y / d x (what ``input_gradient`` returns):
+
+        * ``"integrated_gradients"`` (Sundararajan et al. 2017), midpoint rule over ``steps`` points from the
+          baseline b: ``-(x - b) * mean_s g(b + (s + 1/2) / steps * (x - b))``; its sum over the pixels approaches
+          log p_y(x) - log p_y(b) as ``steps`` grows (completeness).  ``baseline``: None = the black image, a float
+          in pixel units on the [0, 1] scale, or a tensor in any form ``x`` may take.
+        * ``"smoothgrad"`` (Smilkov et al. 2017): ``-mean_s g(x + N(0, sigma^2 I))`` over ``steps`` noised copies,
+          no clamp; ``sigma`` in pixel units, ``seed`` and ``ids`` as ``smoothed_counts`` takes them (image j draws
+          the samples [0, steps) under the id ``ids[j]``, default j).  ``baseline`` is not used; ``sigma``, ``seed``
+          and ``ids`` are used by this method only.
+
+        Inference semantics (no dropout); the net's mode, parameters and gradients are untouched.  GPU with
+        ``dtype="bf16"``: the native loop ``ops.attribute.fused_attribution``; CPU, or ``dtype="fp32"``:
+        ``reference_attribution``.  ``x``: uint8 [B,28,28] / [B,784] images or float [B,1,28,28] normalised input."""
+        import numpy as np
+        B = self._check_input(x)
+        if method not in ATTRIBUTION_METHODS:
+            raise ValueError(f"attribute: method must be one of {ATTRIBUTION_METHODS}, got {method!r}")
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"attribute: steps must be a positive integer, got {steps}")
+        steps, path = int(steps), method == "integrated_gradients"
+        base = 0.0
+        if path:
+            if baseline is None:
+                base = PIXEL_LO
+            elif isinstance(baseline, torch.Tensor):
+                if baseline.numel() != B * 784:
+                    raise ValueError(f"attribute: the baseline must hold {B} images, got {tuple(baseline.shape)}")
+                if baseline.dtype == torch.uint8:
+                    base = _PIXEL_LUT.to(baseline.device)[baseline.reshape(B, 784).long()]
+                else:
+                    base = baseline.detach().reshape(B, 784)
+                base = base.to(self.device, torch.float32).contiguous()
+            elif isinstance(baseline, (int, float)) and baseline == baseline:
+                base = float((np.float32(baseline) - np.float32(MNIST_MEAN)) / np.float32(MNIST_STD))
+            else:
+                raise ValueError("attribute: baseline must be None, a float in pixel units or a tensor of images")
+        else:
+            if not sigma > 0:
+                raise ValueError(f"attribute: sigma must be > 0, got {sigma}")
+            if ids is not None:
+                ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+                if len(ids) != B:
+                    raise ValueError(f"attribute: {len(ids)} ids for {B} images")
+        lp, pred = self._forward(x)
+        if labels is None:
+            labels = pred
+        else:
+            if labels.numel() != B:
+                raise ValueError(f"attribute: {labels.numel()} labels for {B} images")
+            labels = labels.reshape(B).long().to(self.device)
+            if int(labels.min()) < 0 or int(labels.max()) > 9:
+                raise ValueError("attribute: labels must be in [0, 10)")
+        sigma_n = sigma / MNIST_STD
+        if self.native:
+            from .ops.attribute import fused_attribution
+            if x.dtype == torch.uint8:
+                src = x.reshape(B, 784).contiguous().to(self.device)
+            else:
+                src = x.detach().reshape(B, 784).to(self.device, torch.float32).contiguous()
+            attr = fused_attribution(self.net, src, labels, method, steps, base, sigma_n, seed, ids)
+        else:
+            if x.dtype == torch.uint8:
+                x0 = _PIXEL_LUT.to(x.device)[x.reshape(B, 784).long()]
+            else:
+                x0 = x.detach().reshape(B, 784)
+            attr = reference_attribution(self.net, x0.to(self.device, torch.float32), labels, method, steps, base,
+                                         sigma_n, seed, ids)
+        return attr.view(B, 1, 28, 28), lp
+
     # ------------------------------------------------------------------ dispatch
     def _check_input(self, x: torch.Tensor) -> int:
         B = int(x.shape[0])
@@ -445,6 +591,16 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--saliency', default=None, metavar='OUT.npy',
                     help='also write d NLL / d (normalised image) against the true labels for the evaluated '
                          'split as a float32 [N,28,28] .npy file (default: off)')
+    ap.add_argument('--saliency-method', choices=('gradient',) + ATTRIBUTION_METHODS, default='gradient',
+                    help='what --saliency writes: the raw gradient, or the integrated-gradients / SmoothGrad '
+                         'attribution of log p(true label) (default: gradient)')
+    ap.add_argument('--saliency-steps', type=int, default=32, metavar='N',
+                    help='path points (integrated gradients) or noised copies (SmoothGrad) per image (default: 32)')
+    ap.add_argument('--saliency-sigma', type=float, default=0.15, metavar='S',
+                    help='SmoothGrad noise standard deviation in pixel units on the [0, 1] scale (default: 0.15)')
+    ap.add_argument('--saliency-baseline', type=float, default=None, metavar='V',
+                    help='integrated-gradients baseline: a constant image of pixel value V (default: 0, black)')
+    ap.add_argument('--saliency-seed', type=int, default=0, help='seed of the SmoothGrad noise (default: 0)')
     ap.add_argument('--attack-eps', type=float, default=None, metavar='E',
                     help='also report loss and accuracy under an L-inf FGSM / PGD attack of radius E, in pixel '
                          'units on the [0, 1] scale (default: off)')
@@ -491,6 +647,20 @@ def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, 
     return f"Adversarial set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}): {figures}"
 
 
+def completeness_gap(predictor: "Predictor", attr: torch.Tensor, lp: torch.Tensor, labels: torch.Tensor,
+                     baseline: float | None = None) -> float:
+    """sum over the images of |sum attr - (log p_y(x) - log p_y(b))| for integrated gradients ``attr`` of images
+    with clean log-probabilities ``lp``, against the constant baseline of pixel value ``baseline`` (None: black);
+    log p_y(b) from ``predictor.log_probs``."""
+    import numpy as np
+    B = attr.shape[0]
+    b = PIXEL_LO if baseline is None else float((np.float32(baseline) - np.float32(MNIST_MEAN)) / np.float32(MNIST_STD))
+    y = labels.reshape(B, 1).long().to(lp.device)
+    lp_b = predictor.log_probs(torch.full((1, 1, 28, 28), b, dtype=torch.float32))[0].to(lp.device)
+    delta = lp.gather(1, y)[:, 0].double() - lp_b[y[:, 0]].double()
+    return float((attr.reshape(B, 784).double().sum(dim=1) - delta).abs().sum())
+
+
 def predict_main(argv=None) -> int:
     args = build_predict_parser().parse_args(argv)
     use_cuda = not args.no_cuda and torch.cuda.is_available()
@@ -500,16 +670,34 @@ def predict_main(argv=None) -> int:
     images = data.device_images(device) if use_cuda else data.images
     loss_sum, correct, n = predictor.evaluate(images, data.targets, args.batch_size)
     print(test_line(loss_sum / n, correct, n))
+    attribution = {}
     if args.saliency:
         import numpy as np
+        method = args.saliency_method
         out = np.empty((n, 28, 28), dtype=np.float32)
+        gap = 0.0
         for i in range(0, n, args.batch_size):
-            g, _ = predictor.input_gradient(images[i:i + args.batch_size], data.targets[i:i + args.batch_size])
+            xb, yb = images[i:i + args.batch_size], data.targets[i:i + args.batch_size]
+            if method == "gradient":
+                g, _ = predictor.input_gradient(xb, yb)
+            else:
+                g, lp = predictor.attribute(xb, yb, method, args.saliency_steps, args.saliency_baseline,
+                                            args.saliency_sigma, args.saliency_seed, ids=range(i, i + xb.shape[0]))
+                if method == "integrated_gradients":
+                    gap += completeness_gap(predictor, g, lp, yb, args.saliency_baseline)
             out[i:i + g.shape[0]] = g.reshape(-1, 28, 28).cpu().numpy()
         with open(args.saliency, "wb") as f:      # (np.save on a name would append ".npy")
             np.save(f, out)
+        if method != "gradient":
+            attribution = {"saliency_method": method, "saliency_steps": args.saliency_steps}
+            if method == "smoothgrad":
+                attribution.update(saliency_sigma=args.saliency_sigma, saliency_seed=args.saliency_seed)
+            else:
+                attribution.update(saliency_baseline=0.0 if args.saliency_baseline is None else args.saliency_baseline,
+                                   saliency_completeness_gap=gap / n)
     record = {"checkpoint": args.checkpoint, "device": str(device), "source": data.source,
               "test_loss": loss_sum / n, "correct": correct, "n": n}
+    record.update(attribution)
     if args.attack_eps is not None:
         adv_loss, adv_correct, _ = predictor.robust_evaluate(images, data.targets, args.attack_eps, args.attack_steps,
                                                              args.attack_step_size, args.batch_size,

@@ -406,6 +406,164 @@ def smooth_vote(logp: torch.Tensor, M: int, n: int, counts: torch.Tensor | None 
     return counts
 
 
+ATTR_MAX_STEPS = 1 << 24            # most steps n_total of attr_path: every sample index is an exact float (kernels.h)
+ATTR_FINISH_NONE, ATTR_FINISH_SCALE, ATTR_FINISH_PATH = 0, 1, 2     # attr_reduce finish forms (kernels.h AttrFinish)
+
+
+def _attr_rows(a):
+    """float32 numpy [M, 784] normalised rows of a uint8 / float32 tensor or array (uint8: the pixel LUT)."""
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        from ..data.datasets import normalize_u8
+        lut = normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256).numpy()
+        a = lut[a.astype(np.int64)]
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 784)
+
+
+def _attr_base(base, M: int):
+    """float32 numpy baseline that broadcasts against [M, 784]: rows, or one value."""
+    import numpy as np
+    if isinstance(base, (int, float)):
+        return np.float32(base)
+    b = _attr_rows(base)
+    if b.shape[0] != M:
+        raise ValueError(f"attribution: {b.shape[0]} baseline rows for {M} images")
+    return b
+
+
+def attr_path_reference(x, n_total: int, sample_base: int = 0, ns: int | None = None, base=0.0):
+    """``attr_path`` in numpy float32, bit for bit: float32 [M * ns, 784] rows ``b + alpha * (x - b)`` with
+    ``alpha = (float32(sample_base + s) + 0.5) / float32(n_total)``, every operation rounded on its own.  ``x``:
+    uint8 or float32 [M, 784] (tensor or array); ``base``: a float or float32 [M, 784]; normalised units."""
+    import numpy as np
+    x = _attr_rows(x)
+    M = x.shape[0]
+    ns = n_total - sample_base if ns is None else int(ns)
+    if n_total < 1 or n_total > ATTR_MAX_STEPS or sample_base < 0 or ns < 1 or sample_base + ns > n_total:
+        raise ValueError("attr_path: need 0 <= sample_base, ns >= 1 and sample_base + ns <= n_total <= ATTR_MAX_STEPS")
+    b = _attr_base(base, M)
+    alpha = (np.arange(sample_base, sample_base + ns).astype(np.float32) + np.float32(0.5)) / np.float32(n_total)
+    d = (x - b).astype(np.float32)                                           # [M, 784]
+    m = (alpha[None, :, None] * d[:, None, :]).astype(np.float32)            # [M, ns, 784]
+    bb = b if np.ndim(b) == 0 else b[:, None, :]
+    return (bb + m).astype(np.float32).reshape(M * ns, 784)
+
+
+def attr_reduce_reference(dx, M: int, ns: int, acc=None, scale: float | None = None, x=None, base=0.0):
+    """``attr_reduce`` in numpy float32, bit for bit: per element the rows ``dx[i * ns + s]`` are added in
+    ascending ``s`` onto ``acc`` (float32 [M, 784]; None: zeros).  ``scale`` None: the running sums (no finish);
+    else ``sums * scale``, times ``(x - base)`` when ``x`` is given (as ``attr_path_reference`` reads them)."""
+    import numpy as np
+    dx = _attr_rows(dx)[:M * ns].reshape(M, ns, 784)
+    t = np.zeros((M, 784), dtype=np.float32) if acc is None else _attr_rows(acc)[:M].copy()
+    with np.errstate(all="ignore"):
+        for s in range(ns):
+            t = (t + dx[:, s]).astype(np.float32)
+        if scale is None:
+            return t
+        t = (t * np.float32(scale)).astype(np.float32)
+        if x is not None:
+            x = _attr_rows(x)
+            t = (t * (x - _attr_base(base, M)).astype(np.float32)).astype(np.float32)
+    return t
+
+
+def _attr_image_args(name: str, x: torch.Tensor, base, M: int):
+    """(x_u8, x_f32, base pointer, base value) of an image / baseline pair, checked."""
+    if x.dim() != 2 or x.shape != (M, 784) or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be contiguous uint8 or float32 [M, 784]")
+    p = native.ptr
+    u8 = x.dtype == torch.uint8
+    if isinstance(base, torch.Tensor):
+        if base.shape != (M, 784) or base.dtype != torch.float32 or not base.is_contiguous() or base.device != x.device:
+            raise ValueError(f"{name}: a baseline tensor must be contiguous float32 [M, 784] on x's device")
+        return (p(x) if u8 else 0, 0 if u8 else p(x), p(base), 0.0)
+    if not isinstance(base, (int, float)) or base != base:
+        raise ValueError(f"{name}: the baseline must be a float or a float32 [M, 784] tensor")
+    return (p(x) if u8 else 0, 0 if u8 else p(x), 0, float(base))
+
+
+def attr_path(x: torch.Tensor, n_total: int, sample_base: int = 0, ns: int | None = None, base=0.0,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """The rows of the integration path of integrated gradients (``csrc/kernels/attr.hip``), one launch:
+
+        out[i * ns + s] = b_i + alpha * (x_i - b_i),  alpha = (float32(sample_base + s) + 0.5) / float32(n_total)
+
+    float32 [M * ns, 784]: the samples [``sample_base``, ``sample_base`` + ``ns``) (default: up to ``n_total``) of
+    the midpoints of ``n_total`` equal steps from the baseline to the image, every operation rounded on its own
+    (``attr_path_reference`` gives the same bits).  ``x``: uint8 [M, 784] raw rows (normalised in the kernel, bit
+    for bit ``inference._PIXEL_LUT[u8]``) or float32 [M, 784] normalised rows; ``base``: a float (normalised units)
+    or a float32 [M, 784] tensor.  ``out``: float32 with at least M * ns rows of 784, allocated when None; rows
+    past M * ns are not written.  At most ``SMOOTH_MAX_ROWS`` rows a launch (``ValueError`` beyond)."""
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("attr_path: x must be contiguous uint8 or float32 [M, 784] on the GPU")
+    M, n_total, sample_base = x.shape[0], int(n_total), int(sample_base)
+    ns = n_total - sample_base if ns is None else int(ns)
+    if M < 1 or ns < 1:
+        raise ValueError("attr_path: M and ns must be positive")
+    if M * ns > SMOOTH_MAX_ROWS:
+        raise ValueError(f"attr_path: M * ns = {M * ns} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    if n_total > ATTR_MAX_STEPS or sample_base < 0 or sample_base + ns > n_total:
+        raise ValueError("attr_path: need 0 <= sample_base and sample_base + ns <= n_total <= ATTR_MAX_STEPS")
+    img = _attr_image_args("attr_path", x, base, M)
+    if out is None:
+        out = torch.empty(M * ns, 784, dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < M * ns * 784 or out.device != x.device:
+        raise ValueError("attr_path: out must be contiguous float32 with at least M * ns rows of 784")
+    _C().attr_path(*img, native.ptr(out), sample_base, n_total, M, ns, _s())
+    return out
+
+
+def attr_reduce(dx: torch.Tensor, M: int, ns: int, acc: torch.Tensor | None = None, accumulate: bool = False,
+                scale: float | None = None, x: torch.Tensor | None = None, base=0.0,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """The per-image reduction of gradient rows (``csrc/kernels/attr.hip``), one launch: per element
+    ``dx[i * ns + s]`` (float32 [>= M * ns, 784]) is added in ascending ``s``, in float32, onto ``acc[i]`` (float32
+    [>= M, 784]; ``accumulate``: from what it holds, else from 0).  That fixed order makes the sum of an image's
+    rows the same bits under any split of its samples over accumulating launches (``attr_reduce_reference`` gives
+    them).  ``scale`` None: the running sums are stored to ``acc``, which is returned.  With ``scale`` (float32
+    ``-1 / n``) the launch finishes: ``out = acc * scale``, times ``(x_i - b_i)`` when ``x`` is given (``x`` /
+    ``base`` as ``attr_path`` takes them); ``out`` (float32 [>= M, 784], may be ``acc``) is allocated when None and
+    returned, ``acc`` is then left as it was (unless it is ``out``).  Rows past M are not written.  At most
+    ``SMOOTH_MAX_ROWS`` rows a launch (``ValueError`` beyond)."""
+    M, ns = int(M), int(ns)
+    if M * ns > SMOOTH_MAX_ROWS:
+        raise ValueError(f"attr_reduce: M * ns = {M * ns} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    if dx.dtype != torch.float32 or not dx.is_contiguous() or M < 1 or ns < 1 or dx.numel() < M * ns * 784:
+        raise ValueError("attr_reduce: dx must be contiguous float32 with at least M * ns >= 1 rows of 784")
+    if dx.device.type != "cuda":
+        raise ValueError("attr_reduce: dx must be on the GPU")
+    dev = dx.device
+    if acc is None:
+        if accumulate:
+            raise ValueError("attr_reduce: accumulate needs acc")
+        acc = torch.empty(M, 784, dtype=torch.float32, device=dev)
+    for name, t in (("acc", acc), ("out", out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < M * 784
+                              or t.device != dev):
+            raise ValueError(f"attr_reduce: {name} must be contiguous float32 with at least M rows of 784 on dx's device")
+    p = native.ptr
+    if scale is None:
+        if x is not None or out is not None:
+            raise ValueError("attr_reduce: x and out belong to a finishing launch (give scale)")
+        _C().attr_reduce(p(dx), p(acc), 0, 0, 0, 0, 0.0, 0.0, M, ns, bool(accumulate), ATTR_FINISH_NONE, _s())
+        return acc
+    if out is None:
+        out = torch.empty(M, 784, dtype=torch.float32, device=dev)
+    if x is None:
+        _C().attr_reduce(p(dx), p(acc), p(out), 0, 0, 0, 0.0, float(scale), M, ns, bool(accumulate),
+                         ATTR_FINISH_SCALE, _s())
+        return out
+    if x.device != dev:
+        raise ValueError("attr_reduce: x must be on dx's device")
+    img = _attr_image_args("attr_reduce", x, base, M)
+    _C().attr_reduce(p(dx), p(acc), p(out), *img, float(scale), M, ns, bool(accumulate), ATTR_FINISH_PATH, _s())
+    return out
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
