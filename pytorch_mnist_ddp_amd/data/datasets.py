@@ -58,6 +58,12 @@ def normalize_u8(u8: torch.Tensor) -> torch.Tensor:
     return x.unsqueeze(-3)
 
 
+# The 256 normalised pixel values, by normalize_u8's own arithmetic on the CPU (IEEE division: what the
+# kernels' in-register normalisation gives, bit for bit); entries 0 and 255 bound the valid range.
+PIXEL_LUT = normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256)
+PIXEL_LO, PIXEL_HI = float(PIXEL_LUT[0]), float(PIXEL_LUT[255])
+
+
 _warned = set()
 
 

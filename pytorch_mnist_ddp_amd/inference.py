@@ -10,8 +10,8 @@ Dispatch of one batch of B images:
 * GPU, ``dtype="bf16"``, B <= ``INFER_FUSED_MAX_B``: the single-launch fused forward
   (``csrc/kernels/infer_fwd.hip`` through ``ops.functional.infer_forward``; the constant is 0 as
   measured, see below);
-* GPU, ``dtype="bf16"``, larger B: the three-launch eval path (``trunk_fwd`` -> ``fc1_fwd`` ->
-  ``head_eval``), as the trainer's per-epoch eval runs it;
+* GPU, ``dtype="bf16"``, larger B: the three-launch eval chain (``ops.chain.EvalChain``), as the
+  trainer's per-epoch eval runs it;
 * CPU, or ``dtype="fp32"``: ``Net.forward_reference`` (stock torch ops) in eval mode under ``no_grad``.
 
 ``Predictor.input_gradient`` (saliency, adversarial examples) returns the gradient of the summed NLL
@@ -22,63 +22,54 @@ wrt the normalised image, in the same inference semantics (no dropout):
   (``ops.fused_net.fused_input_gradient``); no conv weight gradient is computed;
 * CPU, or ``dtype="fp32"``: torch autograd over ``Net.forward_reference`` in eval mode.
 
-``Predictor.adversarial`` / ``Predictor.robust_evaluate`` (L-inf or L2 FGSM / PGD on that gradient,
-untargeted or targeted; ``eps`` and ``step_size`` in pixel units on the [0, 1] scale):
+The other methods split the same way.  On the GPU with ``dtype="bf16"`` each runs a native loop over the launch
+chains of ``ops/chain.py`` (no autograd, no per-step allocation, no host sync; the loop's module lists its launches);
+on the CPU, or with ``dtype="fp32"``, the same formula in torch ops over autograd through ``Net.forward_reference``
+in eval mode (where noise is drawn: the same distribution, not the same bits):
 
-* GPU, ``dtype="bf16"``: the native loop ``ops.attack.fused_adversarial`` - per step ``trunk_fwd`` ->
-  ``fc1_fwd`` -> ``head_train`` -> ``fc_bwd`` (role B only) -> ``input_grad`` in its step form, which
-  updates the iterate in place (L2: ``input_grad`` in its plain form, then ``pgd_l2_step`` of
-  ``csrc/kernels/attack_step.hip``, one workgroup per image); no autograd, no per-step allocation, no
-  host sync;
-* CPU, or ``dtype="fp32"``: the same formula in torch ops over autograd through
-  ``Net.forward_reference`` in eval mode;
-* the returned log-probabilities are the predictor's own forward (above) of the adversarial images.
-
-``Predictor.smoothed_counts`` / ``Predictor.certify`` (randomized smoothing: the class counts of Gaussian-noised
-copies of an image, and the certified L2 radius they give; ``sigma`` in pixel units on the [0, 1] scale):
-
-* GPU, ``dtype="bf16"``: the native loop ``ops.smooth.fused_smooth_counts`` - per chunk of rows ``smooth_noise``
-  (``csrc/kernels/smooth.hip``) -> ``trunk_fwd`` -> ``fc1_fwd`` -> ``head_eval`` -> ``smooth_vote``;
-* CPU, or ``dtype="fp32"``: ``torch.randn`` over ``Net.forward_reference`` in eval mode (the same distribution,
-  not the same bits);
-* the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path.
-
-``Predictor.attribute`` (integrated gradients and SmoothGrad of log p_y(x): n gradient rows per image, reduced;
-``sigma`` and scalar baselines in pixel units on the [0, 1] scale):
-
-* GPU, ``dtype="bf16"``: the native loop ``ops.attribute.fused_attribution`` - per chunk of rows ``attr_path``
-  (``csrc/kernels/attr.hip``) or ``smooth_noise`` -> ``trunk_fwd`` -> ``fc1_fwd`` -> ``head_train`` -> ``fc_bwd``
-  (role B only) -> ``input_grad`` -> ``attr_reduce`` (``csrc/kernels/attr.hip``, accumulating in a fixed order);
-* CPU, or ``dtype="fp32"``: ``reference_attribution``, the same formulas over autograd through
-  ``Net.forward_reference`` in eval mode (SmoothGrad: the same distribution, not the same bits).
+* ``adversarial`` / ``robust_evaluate`` (L-inf or L2 FGSM / PGD, untargeted or targeted; ``eps`` and ``step_size`` in
+  pixel units on the [0, 1] scale): ``ops.attack.fused_adversarial`` / ``reference_adversarial``; the returned
+  log-probabilities are the predictor's own forward (above) of the adversarial images;
+* ``smoothed_counts`` / ``certify`` (randomized smoothing: the class counts of Gaussian-noised copies of an image and
+  the certified L2 radius they give; ``sigma`` in pixel units): ``ops.smooth.fused_smooth_counts`` / ``torch.randn``
+  over the reference forward; the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path;
+* ``attribute`` (integrated gradients and SmoothGrad of log p_y(x): n gradient rows per image, reduced; ``sigma`` and
+  scalar baselines in pixel units): ``ops.attribute.fused_attribution`` / ``reference_attribution``.
 
 There is no fallback between them: a GPU predictor without the native extension raises.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
-from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
 
-from .data.datasets import MNIST_MEAN, MNIST_STD, load_mnist, normalize_u8
+from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist  # noqa: F401
+from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
 from .ops.functional import PGD_L2_TINY, attr_path_reference, attr_reduce_reference, pgd_l2_step_reference
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
-
-# The 256 normalised pixel values, by normalize_u8's own arithmetic on the CPU (IEEE division: what the
-# kernels' in-register normalisation gives, bit for bit); entries 0 and 255 bound the valid range.
-_PIXEL_LUT = normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256)
-PIXEL_LO, PIXEL_HI = float(_PIXEL_LUT[0]), float(_PIXEL_LUT[255])
 
 # Largest batch the fused single-launch kernel serves; above it the three-launch path runs.  Taken
 # from tools/infer_bench.py's table (profiles/infer/infer_bench.txt, docs/PERF_NOTES.md): as measured,
 # the three-launch path is faster at every batch size, B = 1 included (16.9 against 21.1 us), so the
 # Predictor never dispatches to the fused kernel until that changes.
 INFER_FUSED_MAX_B = 0
+
+
+@contextlib.contextmanager
+def _eval_mode(net: Net):
+    """``net`` in eval mode (no dropout) inside the block; its mode is restored afterwards."""
+    was_training = net.training
+    net.eval()
+    try:
+        yield
+    finally:
+        net.train(was_training)
 
 
 def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int,
@@ -92,9 +83,7 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
     B = x0.shape[0]
     x_adv = x0 if x_init is None else x_init
     alpha_s = -step_size if targeted else step_size
-    was_training = net.training
-    net.eval()
-    try:
+    with _eval_mode(net):
         for _ in range(int(steps)):
             xg = x_adv.clone().requires_grad_()
             with torch.enable_grad():
@@ -107,8 +96,6 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
                 t = x_adv + alpha_s * g.sign()
                 t = torch.min(torch.max(t, x0 - eps), x0 + eps)
                 x_adv = t.clamp(lo, hi)
-    finally:
-        net.train(was_training)
     return x_adv
 
 
@@ -147,9 +134,7 @@ def reference_attribution(net: Net, x0: torch.Tensor, labels: torch.Tensor, meth
     scale = float(np.float32(-1.0) / np.float32(n))
     out = torch.empty(B, 784, dtype=torch.float32)
     gen = torch.Generator()
-    was_training = net.training
-    net.eval()
-    try:
+    with _eval_mode(net):
         for j in range(B):
             bj = float(base) if bc is None else bc[j:j + 1]
             if not path:
@@ -169,9 +154,31 @@ def reference_attribution(net: Net, x0: torch.Tensor, labels: torch.Tensor, meth
                 acc = attr_reduce_reference(g, 1, ns, acc, scale if last else None,
                                             xc[j:j + 1] if path and last else None, bj)
             out[j] = torch.from_numpy(acc[0])
-    finally:
-        net.train(was_training)
     return out.to(dev)
+
+
+def normalised_pixel(value: float) -> float:
+    """The pixel value ``value`` on the [0, 1] scale in normalised units, in float32 arithmetic (a scalar baseline)."""
+    import numpy as np
+    return float((np.float32(value) - np.float32(MNIST_MEAN)) / np.float32(MNIST_STD))
+
+
+def _rows_f32(x: torch.Tensor, B: int, device) -> torch.Tensor:
+    """Detached contiguous float32 [B, 784] normalised rows on ``device`` of uint8 images (through the pixel LUT:
+    the kernels' normalisation, bit for bit, wherever ``x`` lives) or of float, already-normalised input."""
+    if x.dtype == torch.uint8:
+        x = _PIXEL_LUT.to(x.device)[x.reshape(B, 784).long()]
+    return x.detach().reshape(B, 784).to(device, torch.float32).contiguous()
+
+
+def _ids(name: str, ids, B: int):
+    """``ids`` (None, a tensor or a sequence) as None or a list of ``B`` ints."""
+    if ids is None:
+        return None
+    ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+    if len(ids) != B:
+        raise ValueError(f"{name}: {len(ids)} ids for {B} images")
+    return ids
 
 
 def adversarial_units(eps: float, steps: int, step_size: float | None):
@@ -246,26 +253,19 @@ class Predictor:
         ([B] integers), or against the predicted class when ``labels`` is None.  ``x``: uint8
         [B,28,28] / [B,784] images (normalised first) or float [B,1,28,28] already-normalised input."""
         B = self._check_input(x)
-        xf = normalize_u8(x.reshape(B, 28, 28)) if x.dtype == torch.uint8 else x.reshape(B, 1, 28, 28)
-        xf = xf.detach().to(self.device, torch.float32).reshape(B, 1, 28, 28)
+        xf = _rows_f32(x, B, self.device)
         if labels is not None:
-            if labels.numel() != B:
-                raise ValueError(f"input_gradient: {labels.numel()} labels for {B} images")
-            labels = labels.reshape(B).long().to(self.device)
+            labels = self._labels("input_gradient", labels, B, check_range=False)
         if self.native:
             from .ops.fused_net import fused_input_gradient
-            grad, lp = fused_input_gradient(self.net, xf.reshape(B, 784).contiguous(), labels)
+            grad, lp = fused_input_gradient(self.net, xf, labels)
             return grad.reshape(B, 1, 28, 28), lp
-        xf = xf.clone().requires_grad_()
-        was_training = self.net.training
-        self.net.eval()
-        try:
+        xf = xf.view(B, 1, 28, 28).clone().requires_grad_()
+        with _eval_mode(self.net):
             with torch.enable_grad():
                 lp = self.net.forward_reference(xf)
                 target = lp.detach().argmax(dim=1) if labels is None else labels
                 grad, = torch.autograd.grad(F.nll_loss(lp, target, reduction='sum'), xf)
-        finally:
-            self.net.train(was_training)
         return grad, lp.detach()
 
     def adversarial(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1, steps: int = 1,
@@ -295,24 +295,14 @@ class Predictor:
             raise ValueError(f"adversarial: eps must be >= 0, got {eps}")
         if steps != int(steps) or steps < 1:
             raise ValueError(f"adversarial: steps must be a positive integer, got {steps}")
-        if step_size is None:
-            step_size = eps if steps == 1 else 2.5 * eps / steps
-        elif not step_size > 0:
+        if step_size is not None and not step_size > 0:
             raise ValueError(f"adversarial: step_size must be > 0, got {step_size}")
-        if x.dtype == torch.uint8:               # the kernels' normalisation, bit for bit, on any device
-            x0 = _PIXEL_LUT.to(x.device)[x.reshape(B, 784).long()]
-        else:
-            x0 = x.detach().reshape(B, 784)
-        x0 = x0.to(self.device, torch.float32).contiguous()
+        x0 = _rows_f32(x, B, self.device)
         if labels is None:
             labels = self._forward(x0.view(B, 1, 28, 28))[1]
         else:
-            if labels.numel() != B:
-                raise ValueError(f"adversarial: {labels.numel()} labels for {B} images")
-            labels = labels.reshape(B).long().to(self.device)
-            if int(labels.min()) < 0 or int(labels.max()) > 9:
-                raise ValueError("adversarial: labels must be in [0, 10)")
-        eps_n, alpha_n, lo, hi = eps / MNIST_STD, step_size / MNIST_STD, PIXEL_LO, PIXEL_HI
+            labels = self._labels("adversarial", labels, B, check_range=True)
+        eps_n, alpha_n, lo, hi = adversarial_units(eps, steps, step_size)
         x_init = None
         if random_start:
             draw = dict(generator=generator, dtype=torch.float32,
@@ -382,40 +372,25 @@ class Predictor:
             raise ValueError(f"smoothed_counts: n must be a positive integer, got {n}")
         if sample_base < 0:
             raise ValueError(f"smoothed_counts: sample_base must be >= 0, got {sample_base}")
-        if ids is not None:
-            ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
-            if len(ids) != B:
-                raise ValueError(f"smoothed_counts: {len(ids)} ids for {B} images")
+        ids = _ids("smoothed_counts", ids, B)
         n, sigma_n = int(n), sigma / MNIST_STD
         if self.native:
             from .ops.smooth import fused_smooth_counts
-            if x.dtype == torch.uint8:
-                src = x.reshape(B, 784).contiguous().to(self.device)
-            else:
-                src = x.detach().reshape(B, 784).to(self.device, torch.float32).contiguous()
-            return fused_smooth_counts(self.net, src, sigma_n, n, seed, ids, sample_base)
-        if x.dtype == torch.uint8:
-            x0 = _PIXEL_LUT[x.reshape(B, 784).long().cpu()]
-        else:
-            x0 = x.detach().reshape(B, 784).to("cpu", torch.float32)
+            return fused_smooth_counts(self.net, self._rows_native(x, B), sigma_n, n, seed, ids, sample_base)
+        x0 = _rows_f32(x, B, "cpu")
         gen = torch.Generator()
         counts = torch.zeros(B, 10, dtype=torch.int32)
-        was_training = self.net.training
-        self.net.eval()
-        try:
-            with torch.no_grad():
-                for j in range(B):                                   # per image: a generator run of its own
-                    gen.manual_seed((int(seed) * 0x9E3779B97F4A7C15 + (j if ids is None else ids[j])) & (2 ** 63 - 1))
-                    for s0 in range(0, sample_base, 1000):           # past the samples [0, sample_base)
-                        torch.randn(min(1000, sample_base - s0), 784, generator=gen, dtype=torch.float32)
-                    for s0 in range(0, n, 1000):
-                        ns = min(1000, n - s0)
-                        z = torch.randn(ns, 784, generator=gen, dtype=torch.float32)
-                        rows = (x0[j] + sigma_n * z).view(ns, 1, 28, 28).to(self.device)
-                        pred = self.net.forward_reference(rows).argmax(dim=1).cpu()
-                        counts[j] += torch.bincount(pred, minlength=10).to(torch.int32)
-        finally:
-            self.net.train(was_training)
+        with _eval_mode(self.net), torch.no_grad():
+            for j in range(B):                                   # per image: a generator run of its own
+                gen.manual_seed(_smooth_generator_seed(seed, j if ids is None else ids[j]))
+                for s0 in range(0, sample_base, _REF_ROWS):      # past the samples [0, sample_base)
+                    torch.randn(min(_REF_ROWS, sample_base - s0), 784, generator=gen, dtype=torch.float32)
+                for s0 in range(0, n, _REF_ROWS):
+                    ns = min(_REF_ROWS, n - s0)
+                    z = torch.randn(ns, 784, generator=gen, dtype=torch.float32)
+                    rows = (x0[j] + sigma_n * z).view(ns, 1, 28, 28).to(self.device)
+                    pred = self.net.forward_reference(rows).argmax(dim=1).cpu()
+                    counts[j] += torch.bincount(pred, minlength=10).to(torch.int32)
         return counts.to(self.device)
 
     def certify(self, x: torch.Tensor, sigma: float, n0: int = 100, n: int = 1000, alpha: float = 0.001,
@@ -434,8 +409,7 @@ class Predictor:
             raise ValueError(f"certify: n0 and n must be positive integers, got {n0}, {n}")
         if not 0.0 < alpha < 1.0:
             raise ValueError(f"certify: alpha must be in (0, 1), got {alpha}")
-        if ids is not None and len(ids) != B:
-            raise ValueError(f"certify: {len(ids)} ids for {B} images")
+        ids = _ids("certify", ids, B)
         counts0 = self.smoothed_counts(x, sigma, int(n0), seed, ids, sample_base=0).cpu()
         counts = self.smoothed_counts(x, sigma, int(n), seed, ids, sample_base=int(n0)).cpu()
         classes = torch.empty(B, dtype=torch.int64)
@@ -463,7 +437,6 @@ class Predictor:
         Inference semantics (no dropout); the net's mode, parameters and gradients are untouched.  GPU with
         ``dtype="bf16"``: the native loop ``ops.attribute.fused_attribution``; CPU, or ``dtype="fp32"``:
         ``reference_attribution``.  ``x``: uint8 [B,28,28] / [B,784] images or float [B,1,28,28] normalised input."""
-        import numpy as np
         B = self._check_input(x)
         if method not in ATTRIBUTION_METHODS:
             raise ValueError(f"attribute: method must be one of {ATTRIBUTION_METHODS}, got {method!r}")
@@ -477,45 +450,23 @@ class Predictor:
             elif isinstance(baseline, torch.Tensor):
                 if baseline.numel() != B * 784:
                     raise ValueError(f"attribute: the baseline must hold {B} images, got {tuple(baseline.shape)}")
-                if baseline.dtype == torch.uint8:
-                    base = _PIXEL_LUT.to(baseline.device)[baseline.reshape(B, 784).long()]
-                else:
-                    base = baseline.detach().reshape(B, 784)
-                base = base.to(self.device, torch.float32).contiguous()
+                base = _rows_f32(baseline, B, self.device)
             elif isinstance(baseline, (int, float)) and baseline == baseline:
-                base = float((np.float32(baseline) - np.float32(MNIST_MEAN)) / np.float32(MNIST_STD))
+                base = normalised_pixel(baseline)
             else:
                 raise ValueError("attribute: baseline must be None, a float in pixel units or a tensor of images")
         else:
             if not sigma > 0:
                 raise ValueError(f"attribute: sigma must be > 0, got {sigma}")
-            if ids is not None:
-                ids = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
-                if len(ids) != B:
-                    raise ValueError(f"attribute: {len(ids)} ids for {B} images")
+            ids = _ids("attribute", ids, B)
         lp, pred = self._forward(x)
-        if labels is None:
-            labels = pred
-        else:
-            if labels.numel() != B:
-                raise ValueError(f"attribute: {labels.numel()} labels for {B} images")
-            labels = labels.reshape(B).long().to(self.device)
-            if int(labels.min()) < 0 or int(labels.max()) > 9:
-                raise ValueError("attribute: labels must be in [0, 10)")
+        labels = pred if labels is None else self._labels("attribute", labels, B, check_range=True)
         sigma_n = sigma / MNIST_STD
         if self.native:
             from .ops.attribute import fused_attribution
-            if x.dtype == torch.uint8:
-                src = x.reshape(B, 784).contiguous().to(self.device)
-            else:
-                src = x.detach().reshape(B, 784).to(self.device, torch.float32).contiguous()
-            attr = fused_attribution(self.net, src, labels, method, steps, base, sigma_n, seed, ids)
+            attr = fused_attribution(self.net, self._rows_native(x, B), labels, method, steps, base, sigma_n, seed, ids)
         else:
-            if x.dtype == torch.uint8:
-                x0 = _PIXEL_LUT.to(x.device)[x.reshape(B, 784).long()]
-            else:
-                x0 = x.detach().reshape(B, 784)
-            attr = reference_attribution(self.net, x0.to(self.device, torch.float32), labels, method, steps, base,
+            attr = reference_attribution(self.net, _rows_f32(x, B, self.device), labels, method, steps, base,
                                          sigma_n, seed, ids)
         return attr.view(B, 1, 28, 28), lp
 
@@ -526,23 +477,31 @@ class Predictor:
             raise ValueError(f"Predictor expects [B,28,28] / [B,784] / [B,1,28,28] input, got {tuple(x.shape)}")
         return B
 
+    def _rows_native(self, x: torch.Tensor, B: int) -> torch.Tensor:
+        """The rows the native loops take, contiguous [B, 784] on the predictor's device: uint8 images stay uint8
+        (the kernels normalise them), float input becomes detached float32."""
+        if x.dtype == torch.uint8:
+            return x.reshape(B, 784).contiguous().to(self.device)
+        return x.detach().reshape(B, 784).to(self.device, torch.float32).contiguous()
+
+    def _labels(self, name: str, labels: torch.Tensor, B: int, check_range: bool) -> torch.Tensor:
+        """int64 [B] labels on the predictor's device; ``check_range``: each in [0, 10)."""
+        if labels.numel() != B:
+            raise ValueError(f"{name}: {labels.numel()} labels for {B} images")
+        labels = labels.reshape(B).long().to(self.device)
+        if check_range and (int(labels.min()) < 0 or int(labels.max()) > 9):
+            raise ValueError(f"{name}: labels must be in [0, 10)")
+        return labels
+
     def _forward(self, x: torch.Tensor):
         B = self._check_input(x)
         if not self.native:
-            xf = normalize_u8(x.reshape(B, 28, 28)) if x.dtype == torch.uint8 else \
-                x.reshape(B, 1, 28, 28).to(torch.float32)
-            was_training = self.net.training
-            self.net.eval()
-            try:
-                with torch.no_grad():
-                    lp = self.net.forward_reference(xf.to(self.device))
-            finally:
-                self.net.train(was_training)
+            xf = _rows_f32(x, B, self.device).view(B, 1, 28, 28)
+            with _eval_mode(self.net), torch.no_grad():
+                lp = self.net.forward_reference(xf)
             return lp, lp.argmax(dim=1)
-        if x.dtype == torch.uint8:
-            out = self._native(B, u8=x.reshape(B, 784).contiguous().to(self.device))
-        else:
-            out = self._native(B, x=x.reshape(B, 784).to(self.device, torch.float32).contiguous())
+        src = self._rows_native(x, B)
+        out = self._native(B, u8=src) if src.dtype == torch.uint8 else self._native(B, x=src)
         lp = out.logp[:B].clone()
         pred = out.pred[:B].long() if out.pred is not None else lp.argmax(dim=1)
         return lp, pred
@@ -550,6 +509,7 @@ class Predictor:
     def _native(self, B: int, u8=None, x=None, labels=None):
         """One batch through the HIP kernels; returns the buffer set holding rows [0, B)."""
         from .ops import functional as Fk
+        from .ops.chain import EvalChain
         self._st.sync()
         ms = self._st.ms
         if B <= INFER_FUSED_MAX_B:
@@ -558,21 +518,10 @@ class Predictor:
             Fk.infer_forward(ms, self._infer_buf, B, u8=u8, x=x, labels=labels)
             return self._infer_buf
         buf = self._eval_buf
-        if buf is None or buf.B != B:
-            z = dict(device=self.device)
-            buf = self._eval_buf = SimpleNamespace(
-                B=B, pred=None,
-                p=torch.zeros(Fk.round_up(B, 64), Fk.NFLAT, dtype=torch.bfloat16, **z),
-                z1part=torch.zeros(ms.C.FC1_KSPLIT, B, Fk.NH, dtype=torch.float32, **z),
-                loss_rows=torch.zeros(B, dtype=torch.float32, **z),
-                correct=torch.zeros(B, dtype=torch.int32, **z),
-                logp=torch.zeros(B, Fk.NCLS, dtype=torch.float32, **z))
-        p, o = Fk.native.ptr, ms.offsets
-        P = p(ms.param)
-        ms.C.trunk_fwd(p(u8), 0, 0, 0, P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], p(ms.w2f),
-                       P + 4 * o["conv2.bias"], 0, p(buf.p), 0, B, False, Fk.native.stream_handle(), xin=p(x))
-        Fk.fc1_fwd(ms, buf)
-        Fk.head_eval(ms, labels, None, buf)
+        if buf is None or buf.rows != B:
+            buf = self._eval_buf = Fk.EvalBuffers.allocate(B, self.device)
+        p = Fk.native.ptr
+        EvalChain(ms, buf).run(B, u8=p(u8), xin=p(x), labels=p(labels))
         return buf
 
 
@@ -652,9 +601,8 @@ def completeness_gap(predictor: "Predictor", attr: torch.Tensor, lp: torch.Tenso
     """sum over the images of |sum attr - (log p_y(x) - log p_y(b))| for integrated gradients ``attr`` of images
     with clean log-probabilities ``lp``, against the constant baseline of pixel value ``baseline`` (None: black);
     log p_y(b) from ``predictor.log_probs``."""
-    import numpy as np
     B = attr.shape[0]
-    b = PIXEL_LO if baseline is None else float((np.float32(baseline) - np.float32(MNIST_MEAN)) / np.float32(MNIST_STD))
+    b = PIXEL_LO if baseline is None else normalised_pixel(baseline)
     y = labels.reshape(B, 1).long().to(lp.device)
     lp_b = predictor.log_probs(torch.full((1, 1, 28, 28), b, dtype=torch.float32))[0].to(lp.device)
     delta = lp.gather(1, y)[:, 0].double() - lp_b[y[:, 0]].double()

@@ -10,8 +10,7 @@ loop's chain computes; both attribute log p_y(x), hence the factor -1:
 One chunk of rows is seven launches on the current stream, with no autograd, no host sync and no allocation:
 
     attr_path (csrc/kernels/attr.hip: the rows of the path) or smooth_noise (csrc/kernels/smooth.hip: the noised rows)
-    -> trunk_fwd (xin = those rows, training form, STEP_FLAG_NO_DROPOUT) -> fc1_fwd
-    -> head_train (labels given directly, loss scale 1.0) -> fc_bwd, role B only -> input_grad in its plain form
+    -> the four launches of the gradient chain (``ops.chain.GradChain``) -> input_grad in its plain form
     -> attr_reduce (csrc/kernels/attr.hip: the per-image sum in ascending sample order, accumulating over the sample
        chunks of an image; the last one finishes: * -1/n, and * (x - b) for integrated gradients)
 
@@ -27,8 +26,9 @@ import numpy as np
 import torch
 
 from . import native
-from .functional import ATTR_FINISH_NONE, ATTR_FINISH_PATH, ATTR_FINISH_SCALE, FC_ROLE_B, round_up
-from .fused_net import _step_state, fused_state
+from .chain import GradChain
+from .functional import ATTR_FINISH_NONE, ATTR_FINISH_PATH, ATTR_FINISH_SCALE
+from .fused_net import fused_state
 from .smooth import smooth_chunks
 
 METHODS = ("integrated_gradients", "smoothgrad")
@@ -65,8 +65,7 @@ def fused_attribution(net, x: torch.Tensor, labels: torch.Tensor, method: str, n
     path = method == "integrated_gradients"
     st = fused_state(net)
     st.sync()
-    C, ms = native.load(), st.ms
-    dev = ms.device
+    dev = st.ms.device
     if x.dim() != 2 or x.shape[1] != 784 or x.dtype not in (torch.uint8, torch.float32) or x.device != dev:
         raise ValueError("fused_attribution: x must be uint8 or float32 [B, 784] on the net's device")
     B, n = x.shape[0], int(n)
@@ -94,23 +93,17 @@ def fused_attribution(net, x: torch.Tensor, labels: torch.Tensor, method: str, n
     lab = labels.reshape(B).to(dev, torch.int32).repeat_interleave(n).contiguous()   # [B * n]: every chunk points into it
     acc = torch.empty(B, 784, dtype=torch.float32, device=dev)
     out = torch.empty(B, 784, dtype=torch.float32, device=dev)
-    state = _step_state(st, False, dev, 1)      # zero seed and counter, STEP_FLAG_NO_DROPOUT: nothing is drawn
     rb = _buffers(st, rows_max, dev)
-    buf = st.take(rows_max, dev)
-    p, o = native.ptr, ms.offsets
-    P, s = p(ms.param), native.stream_handle()
-    c1w, c1b, c2b = P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], P + 4 * o["conv2.bias"]
-    f1b, f2w, f2b = P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"], P + 4 * o["fc2.bias"]
-    px, pdx, pst, plab, pacc, pout = p(rb.x), p(rb.dx), p(state), p(lab), p(acc), p(out)
-    a1, pp, pmask, z1part, loss_rows = p(buf.a1), p(buf.p), p(buf.pmask), p(buf.z1part), p(buf.loss_rows)
-    dz1, h_bf, dl_bf, dyc, fcpart = p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), p(buf.dyc), p(buf.fcpart)
-    w2f, w2d, w1, w1t = p(ms.w2f), p(ms.w2d), p(ms.w1), p(ms.w1t)
+    chain = GradChain(st, rows_max)
+    C, s, p = native.load(), native.stream_handle(), native.ptr
+    px, pdx, plab, pacc, pout = p(rb.x), p(rb.dx), p(lab), p(acc), p(out)
     u8 = x.dtype == torch.uint8
     src, row_bytes = p(x), 784 * x.element_size()
     seed = int(seed) & (2 ** 64 - 1)
     scale = float(np.float32(-1.0) / np.float32(n))
+    run, grad = chain.run, chain.input_grad
     for i0, m, s0, ns in plan:
-        rows, Bp = m * ns, round_up(m * ns, 32)
+        rows = m * ns
         at = src + i0 * row_bytes
         xu8, xf32 = (at, 0) if u8 else (0, at)
         bat = pbase + i0 * 3136 if pbase else 0
@@ -118,16 +111,11 @@ def fused_attribution(net, x: torch.Tensor, labels: torch.Tensor, method: str, n
             C.attr_path(xu8, xf32, bat, base_value, px, s0, n, m, ns, s)
         else:
             C.smooth_noise(xu8, xf32, px, sigma_n, seed, s0, ids[i0], m, ns, s)
-        C.trunk_fwd(0, 0, 0, pst, c1w, c1b, w2f, c2b, a1, pp, pmask, rows, True, s, xin=px)
-        C.fc1_fwd(pp, w1, z1part, rows, s)
-        C.head_train(z1part, f1b, f2w, f2b, plab + 4 * (i0 * n + s0), 0, 0, pst, 1.0, loss_rows, dz1, h_bf, dl_bf,
-                     rows, Bp, s)
-        C.fc_bwd(dz1, pp, pmask, w1t, h_bf, dl_bf, loss_rows, pst, 0, dyc, 0, 1.0, 1.0, rows, Bp, s,
-                 role=FC_ROLE_B, part=fcpart)
-        C.input_grad(dyc, a1, w2d, c1w, pdx, rows, s)
+        run(px, plab + 4 * (i0 * n + s0), rows)
+        grad(pdx, rows)
         last = s0 + ns == n
         finish = (ATTR_FINISH_PATH if path else ATTR_FINISH_SCALE) if last else ATTR_FINISH_NONE
         C.attr_reduce(pdx, pacc + i0 * 3136, pout + i0 * 3136 if last else 0, xu8 if path and last else 0,
                       xf32 if path and last else 0, bat if last else 0, base_value, scale, m, ns, s0 > 0, finish, s)
-    st.give(buf)                                # last use enqueued: the next taker is stream ordered after it
+    chain.release()                             # last use enqueued: the next taker is stream ordered after it
     return out

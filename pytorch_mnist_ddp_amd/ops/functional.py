@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import torch
 
 from . import native
+from .chain import param_ptrs, round_up  # noqa: F401  (round_up: this module's callers import it from here)
 
 NFLAT, NH, NCLS = 9216, 128, 10
 DYC_REC = 144                       # compact dy record bytes (csrc/include/kernels.h DYC_REC)
@@ -23,10 +24,6 @@ def _C():
 
 def _s() -> int:
     return native.stream_handle()
-
-
-def round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 @dataclass
@@ -74,6 +71,26 @@ class StepBuffers:
         )
 
 
+@dataclass
+class EvalBuffers:
+    """The set of the three-launch eval forward (``chain.EvalChain``); ``rows`` rows serve any launch of fewer."""
+    rows: int
+    p: torch.Tensor           # bf16 [rows64, 9216]
+    z1part: torch.Tensor      # f32 [KSPLIT, rows, 128]
+    loss_rows: torch.Tensor   # f32 [rows]
+    correct: torch.Tensor     # i32 [rows]
+    logp: torch.Tensor        # f32 [rows, 10]
+    pred: None = None         # (``InferBuffers`` holds one: the Predictor reads either set)
+    x: torch.Tensor | None = None   # f32 [rows, 784] input rows, set by a loop that writes its own (ops.smooth)
+
+    @staticmethod
+    def allocate(rows: int, device) -> "EvalBuffers":
+        def z(*shape, dtype=torch.float32):
+            return torch.zeros(*shape, dtype=dtype, device=device)
+        return EvalBuffers(rows, z(round_up(rows, 64), NFLAT, dtype=torch.bfloat16), z(_C().FC1_KSPLIT, rows, NH),
+                           z(rows), z(rows, dtype=torch.int32), z(rows, NCLS))
+
+
 def pmask_flat(pmask: torch.Tensor) -> torch.Tensor:
     """The trunk's pool/dropout flags in torch flatten order [B, 9216] (channel-major) from the device
     layout [B][36][64][4] (pooled position / 4, channel, position % 4; mnist_common.h)."""
@@ -84,10 +101,9 @@ def pmask_flat(pmask: torch.Tensor) -> torch.Tensor:
 def trunk_fwd(ms, data_u8: torch.Tensor | None, idx: torch.Tensor | None, buf: StepBuffers, train: bool,
               idx_stride: int = 0, state: torch.Tensor | None = None, xin: torch.Tensor | None = None) -> None:
     """``xin`` (float32 [B, 784], already normalised) replaces the dataset rows ``data_u8`` / ``idx``."""
-    p, o = native.ptr, ms.offsets
+    p, w = native.ptr, param_ptrs(ms)
     _C().trunk_fwd(p(data_u8), p(idx), idx_stride, p(state if state is not None else ms.state),
-                   p(ms.param) + 4 * o["conv1.weight"], p(ms.param) + 4 * o["conv1.bias"], p(ms.w2f),
-                   p(ms.param) + 4 * o["conv2.bias"], p(buf.a1) if train else 0, p(buf.p),
+                   w.c1w, w.c1b, w.w2f, w.c2b, p(buf.a1) if train else 0, p(buf.p),
                    p(buf.pmask) if train else 0, buf.B, train, _s(), xin=p(xin))
 
 
@@ -100,18 +116,16 @@ def head_train(ms, labels: torch.Tensor, idx: torch.Tensor | None, buf: StepBuff
                state: torch.Tensor | None = None, inv_batch: float | None = None) -> None:
     """``idx`` None: ``labels`` holds one int32 label per batch row.  ``inv_batch``: the loss scale
     (default 1 / B, the mean NLL; 1.0 gives the gradient of the summed NLL)."""
-    p, o = native.ptr, ms.offsets
+    p, w = native.ptr, param_ptrs(ms)
     B = buf.B
-    _C().head_train(p(buf.z1part), p(ms.param) + 4 * o["fc1.bias"], p(ms.param) + 4 * o["fc2.weight"],
-                    p(ms.param) + 4 * o["fc2.bias"], p(labels), p(idx), idx_stride,
+    _C().head_train(p(buf.z1part), w.f1b, w.f2w, w.f2b, p(labels), p(idx), idx_stride,
                     p(state if state is not None else ms.state), 1.0 / B if inv_batch is None else inv_batch,
                     p(buf.loss_rows), p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), B, round_up(B, 32), _s())
 
 
 def head_eval(ms, labels: torch.Tensor | None, idx: torch.Tensor | None, buf: StepBuffers) -> None:
-    p, o = native.ptr, ms.offsets
-    _C().head_eval(p(buf.z1part), p(ms.param) + 4 * o["fc1.bias"], p(ms.param) + 4 * o["fc2.weight"],
-                   p(ms.param) + 4 * o["fc2.bias"], p(labels), p(idx), p(buf.loss_rows), p(buf.correct),
+    p, w = native.ptr, param_ptrs(ms)
+    _C().head_eval(p(buf.z1part), w.f1b, w.f2w, w.f2b, p(labels), p(idx), p(buf.loss_rows), p(buf.correct),
                    p(buf.logp), buf.B, _s())
 
 
@@ -145,7 +159,7 @@ def fc_bwd(ms, buf: StepBuffers, grad_scale: float = 1.0, loss_log: torch.Tensor
     a grad scale other than 1 and a foreign grad buffer."""
     p = native.ptr
     B = buf.B
-    _C().fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), p(ms.w1t), p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
+    _C().fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), param_ptrs(ms).w1t, p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
                 p(state if state is not None else ms.state), p(ms.grad), p(buf.dyc), p(loss_log), grad_scale,
                 1.0 / B, B, round_up(B, 32), _s(), role=role, part=p(buf.fcpart),
                 ada=_ada_args(ms, wt, False) if update else None)
@@ -161,7 +175,7 @@ def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, gra
     ``update`` replaces the reduce launch by one fused with the Adadelta step: ``UPD_WHOLE`` (the serial
     step's single launch, which also updates the fc region from ``ms.grad``), ``("parts", lo, hi)`` (reduce
     parts [lo, hi) of the conv bucket only) or ``UPD_C1`` (the conv1 parts on one-wave workgroups)."""
-    p, o = native.ptr, ms.offsets
+    p, w = native.ptr, param_ptrs(ms)
     form, lo, hi = 0, 0, 0
     if update == UPD_WHOLE:
         form = 1
@@ -172,8 +186,7 @@ def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, gra
         if kind != "parts":
             raise ValueError(f"conv_bwd: unknown update form {update!r}")
         form = 2
-    _C().conv_bwd(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"],
-                  p(ms.param) + 4 * o["conv1.bias"], p(data_u8), p(idx), idx_stride, p(ms.state),
+    _C().conv_bwd(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, w.c1b, p(data_u8), p(idx), idx_stride, p(ms.state),
                   p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s(), xin=p(xin), stages=stages,
                   c1red=p(c1red), update=form, upd_lo=lo, upd_hi=hi,
                   ada=_ada_args(ms, wt, advance_step) if form else None)
@@ -186,17 +199,19 @@ def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.T
     B = buf.B
     if out is None:
         out = torch.empty(B, 784, dtype=torch.float32, device=buf.dyc.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 784 or \
-            out.device != buf.dyc.device:
-        raise ValueError("input_grad: out must be contiguous float32 [B, 784] on the buffers' device")
-    p, o = native.ptr, ms.offsets
-    _C().input_grad(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"], p(out), B, _s())
+    else:
+        _f32_rows("input_grad", "out", out, B, buf.dyc.device)
+    p, w = native.ptr, param_ptrs(ms)
+    _C().input_grad(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(out), B, _s())
     return out.view(B, 784)
 
 
-def _f32_rows(name: str, what: str, t: torch.Tensor, B: int, device) -> None:
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * 784 or t.device != device:
-        raise ValueError(f"{name}: {what} must be contiguous float32 [B, 784] on the buffers' device")
+def _f32_rows(name: str, what: str, t: torch.Tensor, B: int, device, at_least: str | None = None) -> None:
+    """``t`` must be contiguous float32 [B, 784] on ``device``; ``at_least`` (the message's name for B): or more rows."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or \
+            (t.numel() < B * 784 if at_least else t.numel() != B * 784):
+        shape = f"with at least {at_least} rows of 784" if at_least else "[B, 784]"
+        raise ValueError(f"{name}: {what} must be contiguous float32 {shape} on the buffers' device")
 
 
 def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
@@ -225,9 +240,9 @@ def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps
             raise ValueError("input_grad_step: dx must not alias x, x0 or out")
     if not (eps >= 0 and alpha >= 0 and lo <= hi):
         raise ValueError("input_grad_step: need eps >= 0, alpha >= 0 and lo <= hi")
-    p, o = native.ptr, ms.offsets
-    _C().input_grad_step(p(buf.dyc), p(buf.a1), p(ms.w2d), p(ms.param) + 4 * o["conv1.weight"], p(x), p(x0),
-                         p(out), alpha, eps, lo, hi, B, _s(), dx=p(dx))
+    p, w = native.ptr, param_ptrs(ms)
+    _C().input_grad_step(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(x), p(x0), p(out), alpha, eps, lo, hi, B, _s(),
+                         dx=p(dx))
     return out.view(B, 784)
 
 
@@ -287,7 +302,7 @@ def adv_init(data_u8: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor | No
     ``(x0, x, labels_out)`` for the ``B`` rows of the step ``state`` holds (row r = step * ``idx_stride`` + b;
     image and label ``idx[r]`` of ``data_u8`` / ``labels``, or r itself when ``idx`` is None).
 
-        x0 = the normalised image (bit for bit ``inference._PIXEL_LUT[u8]``);  labels_out = its label
+        x0 = the normalised image (bit for bit ``data.datasets.PIXEL_LUT[u8]``);  labels_out = its label
         x  = x0, or with ``random_start``  min(max(x0 + (2u - 1) * eps, lo), hi),  u = (w >> 8) * 2**-24
 
     in float32, each operation rounded on its own, ``w`` one Philox-4x32-10 word per element: word e % 4 of
@@ -308,9 +323,8 @@ def adv_init(data_u8: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor | No
         x = torch.empty(B, 784, dtype=torch.float32, device=dev)
     if labels_out is None:
         labels_out = torch.empty(B, dtype=torch.int32, device=dev)
-    for name, t in (("x0", x0), ("x", x)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < B * 784 or t.device != dev:
-            raise ValueError(f"adv_init: {name} must be contiguous float32 with at least B rows of 784")
+    _f32_rows("adv_init", "x0", x0, B, dev, at_least="B")
+    _f32_rows("adv_init", "x", x, B, dev, at_least="B")
     if labels_out.dtype != torch.int32 or labels_out.numel() < B or labels_out.device != dev:
         raise ValueError("adv_init: labels_out must be int32 with at least B entries")
     if x0.data_ptr() == x.data_ptr():
@@ -333,7 +347,7 @@ def smooth_noise(x: torch.Tensor, sigma: float, n: int, seed: int, sample_base: 
 
         out[i * n + s] = x0_i + sigma * z          float32 [M * n, 784], no clamp
 
-    ``x``: uint8 [M, 784] raw rows (normalised in the kernel, bit for bit ``inference._PIXEL_LUT[u8]``) or
+    ``x``: uint8 [M, 784] raw rows (normalised in the kernel, bit for bit ``data.datasets.PIXEL_LUT[u8]``) or
     float32 [M, 784] already-normalised rows; ``sigma`` >= 0 in normalised units.  ``z``: Box-Muller normals
     from ``philox4x32(counter = (sample_base + s, SMOOTH_PHILOX_DOMAIN, id_base + i, e // 4), key = seed)``:
     words (0, 1) give elements 4v, 4v + 1 (cos, sin), words (2, 3) elements 4v + 2, 4v + 3.  A row depends on
@@ -353,8 +367,7 @@ def smooth_noise(x: torch.Tensor, sigma: float, n: int, seed: int, sample_base: 
         raise ValueError("smooth_noise: sample_base + n and id_base + M must not exceed 2**32")
     if out is None:
         out = torch.empty(M * n, 784, dtype=torch.float32, device=x.device)
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < M * n * 784 or out.device != x.device:
-        raise ValueError("smooth_noise: out must be contiguous float32 with at least M * n rows of 784")
+    _f32_rows("smooth_noise", "out", out, M * n, x.device, at_least="M * n")
     p = native.ptr
     u8 = x.dtype == torch.uint8
     _C().smooth_noise(p(x) if u8 else 0, 0 if u8 else p(x), p(out), float(sigma), int(seed) & (2 ** 64 - 1),
@@ -376,8 +389,7 @@ def smooth_noise_step(state: torch.Tensor, x0: torch.Tensor, sigma: float, B: in
         raise ValueError(f"smooth_noise_step: sigma must be >= 0, got {sigma}")
     if x is None:
         x = torch.empty(B, 784, dtype=torch.float32, device=x0.device)
-    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < B * 784 or x.device != x0.device:
-        raise ValueError("smooth_noise_step: x must be contiguous float32 with at least B rows of 784")
+    _f32_rows("smooth_noise_step", "x", x, B, x0.device, at_least="B")
     p = native.ptr
     _C().smooth_noise_step(p(state), p(x0), p(x), float(sigma), B, _s())
     return x
@@ -417,9 +429,8 @@ def _attr_rows(a):
         a = a.detach().cpu().numpy()
     a = np.asarray(a)
     if a.dtype == np.uint8:
-        from ..data.datasets import normalize_u8
-        lut = normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256).numpy()
-        a = lut[a.astype(np.int64)]
+        from ..data.datasets import PIXEL_LUT
+        a = PIXEL_LUT.numpy()[a.astype(np.int64)]
     return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 784)
 
 
@@ -495,7 +506,7 @@ def attr_path(x: torch.Tensor, n_total: int, sample_base: int = 0, ns: int | Non
     float32 [M * ns, 784]: the samples [``sample_base``, ``sample_base`` + ``ns``) (default: up to ``n_total``) of
     the midpoints of ``n_total`` equal steps from the baseline to the image, every operation rounded on its own
     (``attr_path_reference`` gives the same bits).  ``x``: uint8 [M, 784] raw rows (normalised in the kernel, bit
-    for bit ``inference._PIXEL_LUT[u8]``) or float32 [M, 784] normalised rows; ``base``: a float (normalised units)
+    for bit ``data.datasets.PIXEL_LUT[u8]``) or float32 [M, 784] normalised rows; ``base``: a float (normalised units)
     or a float32 [M, 784] tensor.  ``out``: float32 with at least M * ns rows of 784, allocated when None; rows
     past M * ns are not written.  At most ``SMOOTH_MAX_ROWS`` rows a launch (``ValueError`` beyond)."""
     if x.dim() != 2 or x.device.type != "cuda":
@@ -511,8 +522,7 @@ def attr_path(x: torch.Tensor, n_total: int, sample_base: int = 0, ns: int | Non
     img = _attr_image_args("attr_path", x, base, M)
     if out is None:
         out = torch.empty(M * ns, 784, dtype=torch.float32, device=x.device)
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < M * ns * 784 or out.device != x.device:
-        raise ValueError("attr_path: out must be contiguous float32 with at least M * ns rows of 784")
+    _f32_rows("attr_path", "out", out, M * ns, x.device, at_least="M * ns")
     _C().attr_path(*img, native.ptr(out), sample_base, n_total, M, ns, _s())
     return out
 
@@ -541,10 +551,9 @@ def attr_reduce(dx: torch.Tensor, M: int, ns: int, acc: torch.Tensor | None = No
         if accumulate:
             raise ValueError("attr_reduce: accumulate needs acc")
         acc = torch.empty(M, 784, dtype=torch.float32, device=dev)
-    for name, t in (("acc", acc), ("out", out)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < M * 784
-                              or t.device != dev):
-            raise ValueError(f"attr_reduce: {name} must be contiguous float32 with at least M rows of 784 on dx's device")
+    _f32_rows("attr_reduce", "acc", acc, M, dev, at_least="M")
+    if out is not None:
+        _f32_rows("attr_reduce", "out", out, M, dev, at_least="M")
     p = native.ptr
     if scale is None:
         if x is not None or out is not None:
@@ -667,10 +676,8 @@ def infer_forward(ms, buf: InferBuffers, B: int, *, u8: torch.Tensor | None = No
         raise ValueError("infer_forward: idx must be int32 with at least B entries")
     if labels is not None and labels.dtype != torch.int32:
         raise ValueError("infer_forward: labels must be int32")
-    p, o = native.ptr, ms.offsets
-    P = p(ms.param)
-    _C().infer_fwd(p(u8), p(idx), p(x), p(labels), P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], p(ms.w2f),
-                   P + 4 * o["conv2.bias"], p(ms.w1), P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"],
-                   P + 4 * o["fc2.bias"], p(buf.z1part), p(buf.tickets), p(buf.logp), p(buf.pred),
+    p, w = native.ptr, param_ptrs(ms)
+    _C().infer_fwd(p(u8), p(idx), p(x), p(labels), w.c1w, w.c1b, w.w2f, w.c2b, w.w1, w.f1b, w.f2w, w.f2b,
+                   p(buf.z1part), p(buf.tickets), p(buf.logp), p(buf.pred),
                    p(buf.loss_rows) if labels is not None else 0, p(buf.correct) if labels is not None else 0,
                    B, _s())

@@ -34,7 +34,8 @@ from __future__ import annotations
 import torch
 
 from . import native
-from .functional import StepBuffers, input_grad, round_up
+from .chain import param_ptrs, round_up
+from .functional import StepBuffers, input_grad
 
 _SEED_MIX = 0x9E3779B97F4A7C15
 
@@ -121,7 +122,7 @@ class TrunkFunction(torch.autograd.Function):
     def forward(ctx, x, st, training, flags, c1w, c1b, c2w, c2b):
         C = native.load()
         ms = st.ms
-        p, o = native.ptr, ms.offsets
+        p, w = native.ptr, param_ptrs(ms)
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         x = x.reshape(x.shape[0], -1).to(torch.float32).contiguous()
         if x.shape[1] != 784:
@@ -129,9 +130,7 @@ class TrunkFunction(torch.autograd.Function):
         B = x.shape[0]
         buf = st.take(B, x.device)
         state = _step_state(st, training, x.device, flags)
-        P = p(ms.param)
-        C.trunk_fwd(0, 0, 0, p(state), P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], p(ms.w2f),
-                    P + 4 * o["conv2.bias"], p(buf.a1) if training else 0, p(buf.p),
+        C.trunk_fwd(0, 0, 0, p(state), w.c1w, w.c1b, w.w2f, w.c2b, p(buf.a1) if training else 0, p(buf.p),
                     p(buf.pmask) if training else 0, B, bool(training), native.stream_handle(), xin=p(x))
         ctx.training = bool(training)
         ctx.st = st
@@ -148,8 +147,7 @@ class TrunkFunction(torch.autograd.Function):
         buf, ms = pas.buf, st.ms
         if pas.grad is None:
             raise RuntimeError("fused Net: the trunk backward ran without the head backward")
-        p, o = native.ptr, ms.offsets
-        P = p(ms.param)
+        p, o, w = native.ptr, ms.offsets, param_ptrs(ms)
         dx = None
         if ctx.needs_input_grad[0]:       # same stream, same inputs as conv_bwd (which writes none of them)
             dx = input_grad(ms, buf).view(ctx.x_shape).to(ctx.x_dtype)
@@ -157,8 +155,7 @@ class TrunkFunction(torch.autograd.Function):
             st.give(buf)
             ctx.pas = None
             return (dx, None, None, None, None, None, None, None)
-        C.conv_bwd(p(buf.dyc), p(buf.a1), p(ms.w2d), P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"],
-                   0, 0, 0, p(pas.state), p(buf.c1part), p(buf.w2part), p(pas.grad), 1.0, buf.B,
+        C.conv_bwd(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, w.c1b, 0, 0, 0, p(pas.state), p(buf.c1part), p(buf.w2part), p(pas.grad), 1.0, buf.B,
                    native.stream_handle(), xin=p(pas.x))
         st.give(buf)                      # last use enqueued: the next forward may refill it
         grad = pas.grad
@@ -178,15 +175,13 @@ class HeadFunction(torch.autograd.Function):
         C = native.load()
         ms = st.ms
         pas, st.last_pass = st.last_pass, None
-        p, o = native.ptr, ms.offsets
+        p, w = native.ptr, param_ptrs(ms)
         buf = pas.buf
         B = buf.B
         s = native.stream_handle()
-        P = p(ms.param)
-        C.fc1_fwd(p(buf.p), p(ms.w1), p(buf.z1part), B, s)
+        C.fc1_fwd(p(buf.p), w.w1, p(buf.z1part), B, s)
         logp = torch.empty(B, 10, dtype=torch.float32, device=feat.device)
-        C.head_fwd(p(buf.z1part), P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"], P + 4 * o["fc2.bias"],
-                   p(pas.state), p(logp), B, bool(training), s)
+        C.head_fwd(p(buf.z1part), w.f1b, w.f2w, w.f2b, p(pas.state), p(logp), B, bool(training), s)
         ctx.training = bool(training)
         ctx.st, ctx.pas = st, pas
         if not training:
@@ -200,16 +195,14 @@ class HeadFunction(torch.autograd.Function):
         C = native.load()
         st, pas = ctx.st, ctx.pas
         buf, ms = pas.buf, st.ms
-        p, o = native.ptr, ms.offsets
+        p, o, w = native.ptr, ms.offsets, param_ptrs(ms)
         B = buf.B
         s = native.stream_handle()
-        P = p(ms.param)
         dlogp = dlogp.to(torch.float32).contiguous()
         pas.grad = grad = torch.empty_like(ms.grad)
-        C.head_train(p(buf.z1part), P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"], P + 4 * o["fc2.bias"],
-                     0, 0, 0, p(pas.state), 1.0 / B, p(buf.loss_rows), p(buf.dz1), p(buf.h_bf), p(buf.dl_bf),
-                     B, round_up(B, 32), s, dlogp=p(dlogp))
-        C.fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), p(ms.w1t), p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
+        C.head_train(p(buf.z1part), w.f1b, w.f2w, w.f2b, 0, 0, 0, p(pas.state), 1.0 / B, p(buf.loss_rows),
+                     p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), B, round_up(B, 32), s, dlogp=p(dlogp))
+        C.fc_bwd(p(buf.dz1), p(buf.p), p(buf.pmask), w.w1t, p(buf.h_bf), p(buf.dl_bf), p(buf.loss_rows),
                  p(pas.state), p(grad), p(buf.dyc), 0, 1.0, 1.0 / B, B, round_up(B, 32), s, part=p(buf.fcpart))
         ctx.pas = None
         views = [grad[o[n]:o[n] + t.numel()].view(t.shape) for n, t in _named(ms, _FC)]

@@ -6,7 +6,7 @@ copies of x.  One chunk of rows is five launches on the current stream, with no 
 host sync:
 
     smooth_noise (csrc/kernels/smooth.hip: the noised fp32 rows, from the uint8 or fp32 image)
-    -> trunk_fwd (xin = those rows, eval form) -> fc1_fwd -> head_eval
+    -> the three launches of the eval chain (``ops.chain.EvalChain``, xin = those rows)
     -> smooth_vote (accumulate: the per-image class counts)
 
 The certificate: with cA the class most voted among ``n0`` selection samples and k its count among ``n``
@@ -19,12 +19,12 @@ from __future__ import annotations
 import functools
 import math
 from statistics import NormalDist
-from types import SimpleNamespace
 
 import torch
 
 from . import native
-from .functional import NCLS, NFLAT, NH, SMOOTH_MAX_ROWS, round_up
+from .chain import EvalChain
+from .functional import NCLS, SMOOTH_MAX_ROWS, EvalBuffers
 
 ABSTAIN = -1
 
@@ -133,19 +133,13 @@ def smooth_chunks(B: int, n: int, ids, rows_per_launch: int):
     return plan
 
 
-def _buffers(st, rows: int, dev, C):
-    """The activation set of the loop, kept on the net's fused state and reused while it is large enough."""
+def _buffers(st, rows: int, dev) -> EvalBuffers:
+    """The activation set of the loop with the row buffer ``x`` on it, kept on the net's fused state and reused
+    while it is large enough."""
     buf = getattr(st, "smooth_buf", None)
     if buf is None or buf.rows < rows or buf.x.device != dev:
-        z = dict(device=dev)
-        buf = st.smooth_buf = SimpleNamespace(
-            rows=rows,
-            x=torch.zeros(rows, 784, dtype=torch.float32, **z),
-            p=torch.zeros(round_up(rows, 64), NFLAT, dtype=torch.bfloat16, **z),
-            z1part=torch.zeros(C.FC1_KSPLIT, rows, NH, dtype=torch.float32, **z),
-            loss_rows=torch.zeros(rows, dtype=torch.float32, **z),
-            correct=torch.zeros(rows, dtype=torch.int32, **z),
-            logp=torch.zeros(rows, NCLS, dtype=torch.float32, **z))
+        buf = st.smooth_buf = EvalBuffers.allocate(rows, dev)
+        buf.x = torch.zeros(rows, 784, dtype=torch.float32, device=dev)
     return buf
 
 
@@ -165,8 +159,7 @@ def fused_smooth_counts(net, x: torch.Tensor, sigma_n: float, n: int, seed: int 
     from .fused_net import fused_state
     st = fused_state(net)
     st.sync()
-    C, ms = native.load(), st.ms
-    dev = ms.device
+    dev = st.ms.device
     if x.dim() != 2 or x.shape[1] != 784 or x.dtype not in (torch.uint8, torch.float32) or x.device != dev:
         raise ValueError("fused_smooth_counts: x must be uint8 or float32 [B, 784] on the net's device")
     B, n = x.shape[0], int(n)
@@ -177,23 +170,19 @@ def fused_smooth_counts(net, x: torch.Tensor, sigma_n: float, n: int, seed: int 
         raise ValueError(f"fused_smooth_counts: {len(ids)} ids for {B} images")
     x = x.contiguous()
     plan = smooth_chunks(B, n, ids, rows_per_launch)
-    buf = _buffers(st, max(m * ns for _, m, _, ns in plan), dev, C)
+    buf = _buffers(st, max(m * ns for _, m, _, ns in plan), dev)
     counts = torch.empty(B, NCLS, dtype=torch.int32, device=dev)
-    p, o = native.ptr, ms.offsets
-    P, s = p(ms.param), native.stream_handle()
-    c1w, c1b, c2b = P + 4 * o["conv1.weight"], P + 4 * o["conv1.bias"], P + 4 * o["conv2.bias"]
-    f1b, f2w, f2b = P + 4 * o["fc1.bias"], P + 4 * o["fc2.weight"], P + 4 * o["fc2.bias"]
-    px, pp, pz, plogp = p(buf.x), p(buf.p), p(buf.z1part), p(buf.logp)
-    ploss, pcorrect, w2f, w1 = p(buf.loss_rows), p(buf.correct), p(ms.w2f), p(ms.w1)
+    chain = EvalChain(st.ms, buf)
+    C, s, p = native.load(), native.stream_handle(), native.ptr
+    px, plogp, pcounts = p(buf.x), p(buf.logp), p(counts)
     u8 = x.dtype == torch.uint8
     src, row_bytes = p(x), 784 * x.element_size()
     seed = int(seed) & (2 ** 64 - 1)
+    run = chain.run
     for i0, m, s0, ns in plan:
         rows = m * ns
         at = src + i0 * row_bytes
         C.smooth_noise(at if u8 else 0, 0 if u8 else at, px, sigma_n, seed, sample_base + s0, ids[i0], m, ns, s)
-        C.trunk_fwd(0, 0, 0, 0, c1w, c1b, w2f, c2b, 0, pp, 0, rows, False, s, xin=px)
-        C.fc1_fwd(pp, w1, pz, rows, s)
-        C.head_eval(pz, f1b, f2w, f2b, 0, 0, ploss, pcorrect, plogp, rows, s)
-        C.smooth_vote(plogp, p(counts) + 4 * NCLS * i0, m, ns, s0 > 0, s)
+        run(rows, xin=px)
+        C.smooth_vote(plogp, pcounts + 4 * NCLS * i0, m, ns, s0 > 0, s)
     return counts

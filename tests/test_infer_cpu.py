@@ -19,6 +19,14 @@ from pytorch_mnist_ddp_amd.utils.checkpoint import save_state_dict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def test_pixel_lut_is_normalize_u8_and_shared_with_inference():
+    from pytorch_mnist_ddp_amd import inference
+    from pytorch_mnist_ddp_amd.data.datasets import PIXEL_HI, PIXEL_LO, PIXEL_LUT
+    assert torch.equal(PIXEL_LUT, normalize_u8(torch.arange(256, dtype=torch.uint8).view(1, 16, 16)).reshape(256))
+    assert inference._PIXEL_LUT is PIXEL_LUT
+    assert (inference.PIXEL_LO, inference.PIXEL_HI) == (PIXEL_LO, PIXEL_HI) == (float(PIXEL_LUT[0]), float(PIXEL_LUT[255]))
+
+
 def test_infer_plan_invariants():
     C = native.load()
     assert C.INFER_BANDS == 12
