@@ -137,6 +137,38 @@ AdadeltaArgs ada_from_dict(const py::dict& d) {
     throw std::runtime_error("adadelta arguments: missing model/optimizer pointer");
   return a;
 }
+
+// F32Step of a stand-alone fp32 launch from caller-owned device pointers (null where a key is absent)
+F32Step f32_from_dict(const py::dict& d, int64_t idx_step_stride, float inv_batch) {
+  auto ptr = [&](const char* k) -> uintptr_t { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; };
+  F32Step a{};
+  a.data_u8 = P<const uint8_t>(ptr("data_u8"));
+  a.idx = P<const int32_t>(ptr("idx"));
+  a.idx_step_stride = idx_step_stride;
+  a.labels = P<const int32_t>(ptr("labels"));
+  a.state = P<const StepState>(ptr("state"));
+  a.param = P<const float>(ptr("param"));
+  a.grad = P<float>(ptr("grad"));
+  a.loss_log = P<float>(ptr("loss_log"));
+  a.inv_batch = inv_batch;
+  a.w2fwd = P<float>(ptr("w2fwd"));
+  a.w2bwd = P<float>(ptr("w2bwd"));
+  a.w1p = P<float>(ptr("w1p"));
+  a.a1 = P<float>(ptr("a1"));
+  a.dx1 = P<float>(ptr("dx1"));
+  a.y2 = P<float>(ptr("y2"));
+  a.p = P<float>(ptr("p"));
+  a.pm = P<uint8_t>(ptr("pm"));
+  a.z1part = P<float>(ptr("z1part"));
+  a.h = P<float>(ptr("h"));
+  a.dz1 = P<float>(ptr("dz1"));
+  a.dl = P<float>(ptr("dl"));
+  a.loss_rows = P<float>(ptr("loss_rows"));
+  a.correct = P<int32_t>(ptr("correct"));
+  a.c2part = P<float>(ptr("c2part"));
+  a.c1part = P<float>(ptr("c1part"));
+  return a;
+}
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -287,6 +319,36 @@ PYBIND11_MODULE(_C, m) {
      py::arg("eps"), py::arg("weight_decay"), py::arg("w2f"), py::arg("w2d"), py::arg("w1"), py::arg("w1t"),
      py::arg("state_inc"), py::arg("region"), py::arg("update"), py::arg("stream"), py::arg("grid") = 0,
      py::arg("wt") = false);
+
+  // ---------------- fp32 step, one launcher at a time (tests) ----------------
+  m.attr("F32_MAX_SPLITS") = F32_MAX_SPLITS;
+  m.attr("F32_C1W_BLOCKS") = F32_C1W_BLOCKS;
+  m.attr("F32_STAGE_ALL") = (int)F32_STAGE_ALL;
+  m.def("f32_fc1_splits", &f32_fc1_splits);
+  m.def("f32_conv2w_splits", &f32_conv2w_splits);
+  m.def("f32_conv1w_splits", &f32_conv1w_splits);
+  m.def("f32_forward", [](py::dict ptrs, int64_t idx_stride, float inv_batch, int B, bool train, int stages,
+                          uintptr_t stream) {
+    launch_f32_forward(f32_from_dict(ptrs, idx_stride, inv_batch), B, train, S(stream), stages);
+    check_launch();
+  }, py::arg("ptrs"), py::arg("idx_stride"), py::arg("inv_batch"), py::arg("B"), py::arg("train"), py::arg("stages"),
+     py::arg("stream"),
+     "launch_f32_forward on caller-owned buffers; stages: bit 0 prep, 1 conv1, 2 conv2, 3 pool, 4 fc1, 5 head");
+  m.def("f32_backward", [](py::dict ptrs, int64_t idx_stride, float inv_batch, int B, int stage, uintptr_t stream) {
+    const F32Step a = f32_from_dict(ptrs, idx_stride, inv_batch);
+    if (B < 1) throw std::runtime_error("f32_backward: empty batch");
+    switch (stage) {
+      case 0: launch_f32_fc_small(a, B, S(stream)); break;
+      case 1: launch_f32_fc1w(a, B, S(stream)); break;
+      case 2: launch_f32_fc1x(a, B, S(stream)); break;
+      case 3: launch_f32_conv2w(a, B, S(stream)); break;
+      case 4: launch_f32_conv2x_conv1w(a, B, S(stream)); break;
+      case 5: launch_f32_conv_reduce(a, B, S(stream)); break;
+      default: throw std::runtime_error("f32_backward: bad stage");
+    }
+    check_launch();
+  }, py::arg("ptrs"), py::arg("idx_stride"), py::arg("inv_batch"), py::arg("B"), py::arg("stage"), py::arg("stream"),
+     "one backward launcher: 0 fc_small, 1 fc1w, 2 fc1x, 3 conv2w, 4 conv2x + conv1w, 5 conv_reduce");
 
   // ---------------- single-launch inference forward ----------------
   m.attr("INFER_BANDS") = INFER_BANDS;

@@ -465,8 +465,12 @@ int f32_fc1_splits(int B);
 int f32_conv2w_splits(int B);
 int f32_conv1w_splits(int B);
 // prep + conv1 + conv2 + pool (+dropout) + fc1 + head (train: loss + logit / dz1 gradients; eval:
-// per-row NLL + hits)
-void launch_f32_forward(const F32Step& a, int B, bool train, hipStream_t s);
+// per-row NLL + hits).  `stages` (tests): only the kernels whose bit is set are launched, in that order
+enum F32Stage : int {
+  F32_STAGE_PREP = 1, F32_STAGE_CONV1 = 2, F32_STAGE_CONV2 = 4, F32_STAGE_POOL = 8, F32_STAGE_FC1 = 16,
+  F32_STAGE_HEAD = 32, F32_STAGE_ALL = 63
+};
+void launch_f32_forward(const F32Step& a, int B, bool train, hipStream_t s, int stages = F32_STAGE_ALL);
 // fc2 / fc1-bias grads + loss log, fc1 weight grad, fc1 input grad (+ unpool), conv2 weight grad,
 // conv2 input grad (+ conv1 ReLU), conv1 weight grad, split-K reduce: every gradient of the step
 void launch_f32_backward(const F32Step& a, int B, hipStream_t s);

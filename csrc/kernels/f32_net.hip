@@ -678,19 +678,25 @@ int f32_fc1_splits(int B) { return B <= 1024 ? 36 : 9; }
 int f32_conv2w_splits(int B) { return nsplit((int64_t)B * NPIX2, kchunk((int64_t)B * NPIX2, F32_MAX_SPLITS)); }
 int f32_conv1w_splits(int B) { return F32_C1W_BLOCKS; }
 
-void launch_f32_forward(const F32Step& a, int B, bool train, hipStream_t s) {
+void launch_f32_forward(const F32Step& a, int B, bool train, hipStream_t s, int stages) {
   if (B < 1) throw std::runtime_error("f32 forward: empty batch");
+  if (stages <= 0 || stages > F32_STAGE_ALL) throw std::runtime_error("f32 forward: bad stage mask");
   // (training: + the position-major fc1 weight copy for the backward)
-  hipLaunchKernelGGL(f32_prep_kernel, dim3(blocks(C2 * K2) + (train ? blocks(NH * NFLAT / 4) : 0)), dim3(256), 0, s,
-                     a, train ? 1 : 0);
-  hipLaunchKernelGGL(f32_conv1_kernel, dim3(B * C1_WG_PER_IMG), dim3(256), 0, s, a, B);
-  gemm<64, 64>(PConv2Fwd{B * NPIX2, C2, K2, K2, a.a1, a.w2fwd, a.param + OFF_CONV2_B, a.y2}, 1, s);
-  if (train)
+  if (stages & F32_STAGE_PREP)
+    hipLaunchKernelGGL(f32_prep_kernel, dim3(blocks(C2 * K2) + (train ? blocks(NH * NFLAT / 4) : 0)), dim3(256), 0, s,
+                       a, train ? 1 : 0);
+  if (stages & F32_STAGE_CONV1)
+    hipLaunchKernelGGL(f32_conv1_kernel, dim3(B * C1_WG_PER_IMG), dim3(256), 0, s, a, B);
+  if (stages & F32_STAGE_CONV2)
+    gemm<64, 64>(PConv2Fwd{B * NPIX2, C2, K2, K2, a.a1, a.w2fwd, a.param + OFF_CONV2_B, a.y2}, 1, s);
+  if ((stages & F32_STAGE_POOL) && train)
     hipLaunchKernelGGL(f32_pool_kernel<true>, dim3(blocks((int64_t)B * C2 * 9)), dim3(256), 0, s, a, B);
-  else
+  else if (stages & F32_STAGE_POOL)
     hipLaunchKernelGGL(f32_pool_kernel<false>, dim3(blocks((int64_t)B * C2 * 9)), dim3(256), 0, s, a, B);
   const int s1 = f32_fc1_splits(B);
-  gemm<64, 64>(PFc1{B, NH, NFLAT, NFLAT / s1, a.p, a.param + OFF_FC1_W, a.z1part}, s1, s);
+  if (stages & F32_STAGE_FC1)
+    gemm<64, 64>(PFc1{B, NH, NFLAT, NFLAT / s1, a.p, a.param + OFF_FC1_W, a.z1part}, s1, s);
+  if (!(stages & F32_STAGE_HEAD)) return;
   if (train)
     hipLaunchKernelGGL(f32_head_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, a, B, s1);
   else

@@ -622,6 +622,79 @@ def dense_dy(buf: StepBuffers) -> torch.Tensor:
     return dense.view(B, 24, 24, 64)
 
 
+# ---------------------------------------------------------------------------- fp32 step, one launcher at a time
+# launch_f32_forward's stage mask and the backward launchers of csrc/kernels/f32_net.hip (kernels.h F32Stage)
+F32_PREP, F32_CONV1, F32_CONV2, F32_POOL, F32_FC1, F32_HEAD, F32_FWD_ALL = 1, 2, 4, 8, 16, 32, 63
+F32_FC_SMALL, F32_FC1W, F32_FC1X, F32_CONV2W, F32_CONV2X_CONV1W, F32_CONV_REDUCE = range(6)
+F32_MAX_SPLITS, F32_C1W_BLOCKS = 128, 1024      # kernels.h
+
+
+def f32_fc1_splits(B: int) -> int:
+    return 36 if B <= 1024 else 9
+
+
+@dataclass
+class F32Buffers:
+    """The workspace of the fp32 step (kernels.h F32Step) for batch ``B``, every tensor with one guard row or
+    guard slab beyond what B needs.  ``trunk`` False: no conv activations (a1 / dx1 keep the guard row only)."""
+    B: int
+    w2fwd: torch.Tensor       # f32 [9+1, 32, 64]
+    w2bwd: torch.Tensor       # f32 [9+1, 64, 32]
+    w1p: torch.Tensor         # f32 [128+1, 144, 64]
+    a1: torch.Tensor          # f32 [B+1, 26, 26, 32]
+    dx1: torch.Tensor         # f32 [B+1, 26, 26, 32]
+    y2: torch.Tensor          # f32 [B+1, 24, 24, 64]  conv2 pre-activation, then its gradient
+    p: torch.Tensor           # f32 [B+1, 9216]
+    pm: torch.Tensor          # u8  [B+1, 144, 64]
+    z1part: torch.Tensor      # f32 [splits * B + 1, 128]
+    h: torch.Tensor           # f32 [B+1, 128]
+    dz1: torch.Tensor         # f32 [B+1, 128]
+    dl: torch.Tensor          # f32 [B+1, 16]
+    loss_rows: torch.Tensor   # f32 [B+2]: a launch may use rows [out_row, out_row + B)
+    correct: torch.Tensor     # i32 [B+2]
+    c2part: torch.Tensor      # f32 [F32_MAX_SPLITS+1, 64, 289]
+    c1part: torch.Tensor      # f32 [F32_C1W_BLOCKS+1, 32, 10]
+
+    @staticmethod
+    def allocate(B: int, device, trunk: bool = True) -> "F32Buffers":
+        def z(*shape, dtype=torch.float32):
+            return torch.zeros(*shape, dtype=dtype, device=device)
+        Bt = B if trunk else 0
+        return F32Buffers(B, z(10, 32, 64), z(10, 64, 32), z(129, 144, 64), z(Bt + 1, 26, 26, 32), z(Bt + 1, 26, 26, 32),
+                          z(B + 1, 24, 24, 64), z(B + 1, NFLAT), z(B + 1, 144, 64, dtype=torch.uint8),
+                          z(f32_fc1_splits(B) * B + 1, NH), z(B + 1, NH), z(B + 1, NH), z(B + 1, 16), z(B + 2),
+                          z(B + 2, dtype=torch.int32), z(F32_MAX_SPLITS + 1, 64, 289), z(F32_C1W_BLOCKS + 1, 32, 10))
+
+    def tensors(self) -> dict:
+        return {k: v for k, v in vars(self).items() if isinstance(v, torch.Tensor)}
+
+
+def _f32_ptrs(buf: F32Buffers, out_row: int, **ext) -> dict:
+    d = {k: native.ptr(v) for k, v in {**buf.tensors(), **ext}.items() if v is not None}
+    d["loss_rows"] += 4 * out_row
+    d["correct"] += 4 * out_row
+    return d
+
+
+def f32_forward(buf: F32Buffers, param: torch.Tensor, data_u8: torch.Tensor, labels: torch.Tensor,
+                idx: torch.Tensor | None = None, idx_stride: int = 0, state: torch.Tensor | None = None,
+                inv_batch: float = 0.0, train: bool = True, stages: int = F32_FWD_ALL, out_row: int = 0) -> None:
+    """The forward kernels of the fp32 step named by the ``stages`` mask, in order, on caller-owned buffers.
+    ``state`` None: the eval form's null StepState (step 0, no dropout).  ``out_row``: first row of
+    ``buf.loss_rows`` / ``buf.correct`` the launch uses."""
+    ptrs = _f32_ptrs(buf, out_row, param=param, data_u8=data_u8, labels=labels, idx=idx, state=state)
+    _C().f32_forward(ptrs, idx_stride, inv_batch, buf.B, bool(train), stages, _s())
+
+
+def f32_backward(buf: F32Buffers, stage: int, param: torch.Tensor, grad: torch.Tensor, data_u8: torch.Tensor,
+                 labels: torch.Tensor, idx: torch.Tensor | None = None, idx_stride: int = 0,
+                 state: torch.Tensor | None = None, inv_batch: float = 0.0, loss_log: torch.Tensor | None = None,
+                 out_row: int = 0) -> None:
+    """One backward launcher of the fp32 step (``F32_FC_SMALL`` .. ``F32_CONV_REDUCE``) on caller-owned buffers."""
+    ptrs = _f32_ptrs(buf, out_row, param=param, grad=grad, data_u8=data_u8, labels=labels, idx=idx, state=state,
+                     loss_log=loss_log)
+    _C().f32_backward(ptrs, idx_stride, inv_batch, buf.B, stage, _s())
+
 
 # ---------------------------------------------------------------------------- single-launch inference
 @dataclass

@@ -9,6 +9,8 @@ operands that kernel reads, the comparators (``assert_rounded_bf16``, ``assert_w
 ``assert_decisions``) and the per-kernel checks built from them, shared by
 tests/test_forward_oracle_cpu.py and tests/test_gpu_forward_stages.py.  The last part is the same for the
 backward kernels (tests/test_backward_oracle_cpu.py, tests/test_gpu_backward_stages.py).
+The fp32 step's kernels (csrc/kernels/f32_net.hip) have their own stage oracle at the end of the file
+(tests/test_fp32_oracle_cpu.py, tests/test_gpu_fp32_stages.py).
 """
 from __future__ import annotations
 
@@ -1045,3 +1047,568 @@ SHADOW_SPECIAL_BITS = (0x3F80, 0x3F82, 0xBF80, 0xBF82, 0x3F81, 0x3F81, 0, 0x8000
 SHADOW_SPECIAL_AT = {"fc1.weight": [o * 9216 + i for o in (0, 63, 64, 127) for i in (0, 31, 32, 4607, 9215)][:18],
                      "conv2.weight": [0, 1, 8, 9, 287, 288, 289, 4000, 4001, 9215, 9216, 12345, 18000, 18142, 18143,
                                       18144, 18430, 18431]}
+
+
+# ---------------------------------------------------------------- fp32-path stage oracle
+# One function per kernel of csrc/kernels/f32_net.hip on the operands that kernel reads, in the kernel's own
+# layouts (csrc/include/kernels.h F32Step), no bf16 rounding anywhere.  dtype = F64 is the oracle, dtype = F32 the
+# torch-fp32 twin that sets each stage's eps and is the CPU proof's stand-in for the kernels; ``mut`` names the
+# single mutations of tests/test_fp32_oracle_cpu.py.  ``f32_run_stage`` is the per-launch protocol (sentinel,
+# launch, ownership, oracle, repeat) shared by that test and tests/test_gpu_fp32_stages.py.
+import dataclasses
+
+F32_ULPS = 4.0               # floor of an fp32 output's eps, in ulps of the largest reference magnitude (head: HEAD_ULPS)
+F32_SENT_F, F32_SENT_I, F32_SENT_B = 0x7FC0F32A, -0x55555556, 0xAA      # sentinel bits: f32 (a NaN), i32, u8
+F32_LOG_N, F32_OUT_ROW = 8, 1     # loss_log entries; loss_rows / correct are used from this row on (an offset pointer)
+F32_FWD = {"prep": 1, "conv1": 2, "conv2": 4, "pool": 8, "fc1": 16, "head": 32}
+F32_BWD = {"fc_small": 0, "fc1w": 1, "fc1x": 2, "conv2w": 3, "conv2x_conv1w": 4, "conv_reduce": 5}
+F32_TRUNK_B, F32_HAND_B = (1, 3, 33, 65), (257, 1025)
+PARAM_SHAPES = {"fc1.weight": (128, 9216), "fc1.bias": (128,), "fc2.weight": (10, 128), "fc2.bias": (10,),
+                "conv1.weight": (32, 1, 3, 3), "conv1.bias": (32,), "conv2.weight": (64, 32, 3, 3), "conv2.bias": (64,)}
+
+
+@dataclasses.dataclass
+class F32Cfg:
+    """What a launch takes besides its buffers: the StepState fields (``state`` False: a null pointer, the eval
+    form), the input form (rows through ``idx`` or pre-gathered) and the loss scale."""
+    B: int
+    step: int = FWD_STEP
+    seed: int = FWD_SEED
+    rng_base: int = FWD_RNG_BASE
+    flags: int = 0
+    world: int = 1
+    use_idx: bool = True
+    train: bool = True
+
+    @property
+    def stride(self):
+        return self.B if self.train else 0
+
+    @property
+    def inv_batch(self):
+        return float(torch.tensor(1.0 / (self.B * self.world), dtype=F32)) if self.train else 0.0
+
+    @property
+    def dropout(self):
+        return self.train and not (self.flags & 1)
+
+    def rows(self, idx):
+        """Dataset rows of the batch: row b of the step is step * stride + b, through idx when it is given."""
+        r = (self.step if self.train else 0) * self.stride + torch.arange(self.B)
+        return idx.long()[r] if self.use_idx else r
+
+
+def f32_splits(B: int) -> dict:
+    """f32_net.hip's host split rules: fc1 split-K, conv2 weight-gradient chunk / slabs, conv1 slabs."""
+    K = B * 576
+    kc = (-(-K // 128) + 15) // 16 * 16
+    return dict(fc1=36 if B <= 1024 else 9, conv2w_kc=kc, conv2w=-(-K // kc), conv1w=1024)
+
+
+def f32_flat_params(net) -> torch.Tensor:
+    flat = torch.zeros(PARAM_TOTAL, dtype=F32)
+    for n, p in net.named_parameters():
+        flat[ADA_OFFS[n]:ADA_OFFS[n] + ADA_NUMEL[n]] = p.detach().reshape(-1).float()
+    return flat
+
+
+def f32_params(flat) -> dict:
+    return {k: flat[o:o + ADA_NUMEL[k]].view(PARAM_SHAPES[k]) for k, o in ADA_OFFS.items()}
+
+
+def f32o_prep(param, train=True, mut=None):
+    """Pure permutations of conv2.weight [co][ci][tap] and fc1.weight [o][c*144 + pos]."""
+    d = f32_params(param)
+    w2 = d["conv2.weight"].reshape(64, 32, 9)
+    w2b = d["conv2.weight"].transpose(2, 3).reshape(64, 32, 9) if mut == "w2bwd_taps_transposed" else w2
+    out = {"w2fwd": w2.permute(2, 1, 0).contiguous(), "w2bwd": w2b.permute(2, 0, 1).contiguous()}
+    if train:
+        w1 = d["fc1.weight"]
+        out["w1p"] = w1.view(128, 144, 64).contiguous() if mut == "w1p_swapped" else \
+            w1.view(128, 64, 144).permute(0, 2, 1).contiguous()
+    return out
+
+
+def f32o_conv1(x_norm, param, dtype=F64):
+    """a1 NHWC [B,26,26,32] = relu(conv1) of the normalised rows [B,784]."""
+    d = f32_params(param)
+    return stage_conv1(x_norm, d["conv1.weight"], d["conv1.bias"], dtype).permute(0, 2, 3, 1).contiguous()
+
+
+def f32o_conv2(a1, w2fwd, param, dtype=F64):
+    """y2 NHWC [B,24,24,64] from a1 NHWC and w2fwd [tap][ci][co]."""
+    w = w2fwd.view(3, 3, 32, 64).permute(3, 2, 0, 1)
+    y = F.conv2d(a1.permute(0, 3, 1, 2).to(dtype), w.to(dtype), f32_params(param)["conv2.bias"].to(dtype))
+    return y.permute(0, 2, 3, 1).contiguous()
+
+
+def f32o_pool(y2, cfg, dtype=F64, mut=None):
+    """f32_pool: ``p`` [B,9216] torch flatten order, ``pm`` u8 [B,144,64] (None in the eval form), and the window
+    values ``win`` [B,9216,4].  Dropout-1 draws Philox at rng_base + 2 step, block (b*9216 + flat) >> 4; under
+    STEP_FLAG_NO_DROPOUT nothing is drawn: every unit is kept and p is unscaled."""
+    B = y2.shape[0]
+    win = pool_windows(y2.permute(0, 3, 1, 2).contiguous().to(dtype))
+    r = F.relu(win)
+    if mut == "last_max_wins":
+        pooled, code = r[..., 0].clone(), torch.zeros(r.shape[:-1], dtype=torch.long)
+        for k in range(1, 4):
+            m = r[..., k] >= pooled
+            pooled, code = torch.where(m, r[..., k], pooled), torch.where(m, torch.full_like(code, k), code)
+    else:
+        pooled, code = first_strict_max(r)
+    keep = torch.ones(B, 9216, dtype=dtype)
+    if cfg.dropout:
+        elems = torch.arange(B).view(-1, 1) * 9216 + torch.arange(9216)
+        off = cfg.rng_base + 2 * cfg.step + (1 if mut == "philox_offset" else 0)
+        keep = keep_mask_at(cfg.seed, off, elems, 192).to(dtype)
+    p = pooled * keep * torch.tensor(INV_KEEP1_F32 if cfg.dropout else 1.0, dtype=dtype)
+    pm = None
+    if cfg.train:
+        pos = pooled >= 0 if mut == "pooled_geq" else pooled > 0
+        flat = code | (keep.long() << 2) | (pos.long() << 3)
+        pm = flat.view(B, 64, 144).permute(0, 2, 1).contiguous().to(torch.uint8)
+    return dict(p=p, pm=pm, win=win, keep=keep)
+
+
+def f32o_head(z1part, param, labels, cfg, dtype=F64, mut=None):
+    """f32_head on z1part [S,B,128]: stage_head with dropout-2 at rng_base + 2 step + 1 and the launch's inv_batch;
+    ``dl`` [B,16] (columns 10..15 zero), ``correct`` (eval)."""
+    d = f32_params(param)
+    B = z1part.shape[1]
+    keep2 = None
+    if cfg.dropout:
+        keep2 = keep_mask_at(cfg.seed, cfg.rng_base + 2 * cfg.step + 1, torch.arange(B).view(-1, 1) * 128 + torch.arange(128), 128)
+    inv = float(torch.tensor(1.0 / B, dtype=F32)) if mut == "inv_batch_no_world" else cfg.inv_batch
+    zp = z1part[:12] if mut == "head_12_partials" else z1part
+    out = stage_head(zp, d["fc1.bias"], d["fc2.weight"], d["fc2.bias"], labels, keep2, inv if cfg.train else 1.0, dtype)
+    w2 = d["fc2.weight"].to(dtype)
+    if mut == "dl_no_label":
+        out["dl"] = out["logp"].exp() * inv
+        out["dz1"] = (out["dl"] @ w2) * (1.0 if keep2 is None else keep2.to(dtype) * 2.0) * (out["z1"] > 0)
+    if mut == "drop2_scale_missing" and keep2 is not None:
+        out["dz1"] = (out["dl"] @ w2) * keep2.to(dtype) * (out["z1"] > 0)
+    out["dl"] = torch.cat([out["dl"], torch.zeros(B, 6, dtype=dtype)], 1)
+    out["keep2"] = keep2
+    top = out["logp"].topk(2, 1).values
+    out["gap"] = top[:, 0] - top[:, 1]
+    out["correct"] = (first_strict_max(out["logp"])[1] == labels.long()).to(torch.int32)
+    return out
+
+
+def f32o_fc_small(h, dl, dz1, loss_rows, dtype=F64, mut=None):
+    B = h.shape[0]
+    d = dl[:, :10].to(dtype)
+    n = (B + 3) // 4 * 4 if mut == "loss_padded_B" else B
+    return {"fc2.weight": d.t() @ h.to(dtype), "fc2.bias": d.sum(0), "fc1.bias": dz1.to(dtype).sum(0),
+            "loss": loss_rows.to(dtype).sum() / torch.tensor(float(n), dtype=dtype)}
+
+
+def f32o_fc1w(dz1, p, dtype=F64):
+    return dz1.to(dtype).t() @ p.to(dtype)
+
+
+def f32o_fc1x(dz1, w1p, pm, cfg, dtype=F64, mut=None):
+    """fc1 input gradient through dropout-1 and the un-pooling: dense NHWC ``dy2`` [R,24,24,64] and ``routed``,
+    the elements that may be non-zero (the window position pm & 3 of the units with pm & 12 == 12)."""
+    R_ = dz1.shape[0]
+    dp = dz1.to(dtype) @ w1p.reshape(128, 9216).to(dtype)                       # [R, pos*64 + c]
+    scale = INV_KEEP1_F32 if cfg.dropout and mut != "drop1_scale_missing" else 1.0
+    pmv = pm.reshape(R_, 12, 12, 64).long()
+    live, code = (pmv & 12) == 12, pmv & 3
+    if mut == "wrong_quadrant":
+        code = code ^ 1
+    g = torch.where(live, dp.view(R_, 12, 12, 64) * torch.tensor(scale, dtype=dtype), torch.zeros((), dtype=dtype))
+    dy = torch.zeros(R_, 12, 2, 12, 2, 64, dtype=dtype)
+    routed = torch.zeros(R_, 12, 2, 12, 2, 64, dtype=torch.bool)
+    for q in range(4):
+        dy[:, :, q >> 1, :, q & 1, :] = torch.where(code == q, g, torch.zeros((), dtype=dtype))
+        routed[:, :, q >> 1, :, q & 1, :] = (pmv & 3 == q) & live
+    return dict(dy2=dy.view(R_, 24, 24, 64), routed=routed.view(R_, 24, 24, 64))
+
+
+def f32o_conv2w(dy2, a1, dtype=F64, mut=None):
+    """conv2 weight + bias partial slabs [splits,64,289]: slab z sums the output pixels [z kc, min(K, (z+1) kc)) of
+    the batch's K = 576 B; column n = tap*32 + ci, column 288 the bias."""
+    B = dy2.shape[0]
+    sp = f32_splits(B)
+    kc, S, K = sp["conv2w_kc"], sp["conv2w"], B * 576
+    cols = F.unfold(a1.permute(0, 3, 1, 2).to(dtype), 3).view(B, 32, 9, 576).permute(0, 3, 2, 1).reshape(K, 288)
+    d = dy2.reshape(K, 64).to(dtype)
+    part = torch.zeros(S, 64, 289, dtype=dtype)
+    for z in range(S):
+        r = slice(z * kc, min(K, (z + 1) * kc))
+        part[z, :, :288] = d[r].t() @ cols[r]
+        part[z, :, 288] = part[z, :, 287] if mut == "bias_wrong_n" else d[r].sum(0)
+    return part
+
+
+def f32o_conv2x(dy2, w2bwd, a1, dtype=F64, mut=None):
+    """conv2 input gradient (w2bwd [tap][co][ci]) times the stored a1 > 0: dx1 NHWC [B,26,26,32] and the mask."""
+    w = w2bwd.view(3, 3, 64, 32).permute(2, 3, 0, 1)
+    da1 = F.conv_transpose2d(dy2.permute(0, 3, 1, 2).to(dtype), w.to(dtype)).permute(0, 2, 3, 1)
+    mask = a1 >= 0 if mut == "relu_geq" else a1 > 0
+    return dict(dx1=torch.where(mask, da1, torch.zeros((), dtype=dtype)).contiguous(), mask=mask)
+
+
+def f32o_conv1w(dx1, x_norm, dtype=F64, mut=None):
+    """conv1 weight + bias partial slabs [1024,32,10]: slab g sums the pixels [P g / G, P (g+1) / G) of P = 676 B."""
+    B, G = dx1.shape[0], 1024
+    P_ = 676 * B
+    xc = F.unfold(x_norm.reshape(B, 1, 28, 28).to(dtype), 3).permute(0, 2, 1).reshape(P_, 9)
+    d = dx1.reshape(P_, 32).to(dtype)
+    vals = torch.cat([d.unsqueeze(2) * xc.unsqueeze(1), d.unsqueeze(2)], 2)           # [P,32,10]
+    bounds = torch.arange(G + 1) * P_ // G
+    seg = torch.searchsorted(bounds[1:].contiguous(), torch.arange(P_), right=True)
+    out = torch.zeros(G, 32, 10, dtype=dtype).index_add_(0, seg, vals)
+    if mut == "c1w_range_off_by_one":           # a slab that ends inside an image's first row takes one pixel more
+        for g in range(G - 1):
+            lo, hi = int(bounds[g]), int(bounds[g + 1])
+            if hi > lo and lo // 676 != hi // 676 and hi < P_:
+                out[g] += vals[hi]
+    return out
+
+
+def f32o_conv_reduce(c2part, c1part, dtype=F64, mut=None, stale=None):
+    """The slabs' sums in torch layouts.  c2part [s2,64,289], c1part [1024,32,10]; ``stale``: the slab after them."""
+    c2 = c2part.to(dtype)
+    if mut == "last_slab_dropped":
+        c2 = c2[:-1]
+    if mut == "stale_slab":
+        c2 = torch.cat([c2, stale.to(dtype).unsqueeze(0)])
+    s, c1 = c2.sum(0), c1part.to(dtype).sum(0)
+    return {"conv2.weight": s[:, :288].reshape(64, 9, 32).permute(0, 2, 1).reshape(64, 32, 3, 3).contiguous(),
+            "conv2.bias": s[:, 288].contiguous(), "conv1.weight": c1[:, :9].reshape(32, 1, 3, 3).contiguous(),
+            "conv1.bias": c1[:, 9].contiguous()}
+
+
+def f32_eps(r32, r64, head=False):
+    """(eps, measured): measured = 8 x max |torch fp32 - float64|; eps = that, not below 4 (head tensors 16) fp32
+    ulps of the reference's largest magnitude - except that a measured 0 stays 0: exact agreement."""
+    raw = EPS_MARGIN * float((r32.to(F64) - r64).abs().max())
+    if raw == 0.0:
+        return 0.0, 0.0
+    _, e = torch.frexp(r64.abs().max())
+    return max(raw, (HEAD_ULPS if head else F32_ULPS) * 2.0 ** (int(e) - 24)), raw
+
+
+def _held(stats, key, out, r32, r64, head=False, what=""):
+    eps, raw = f32_eps(r32, r64, head)
+    dev = assert_within(out, r64, eps, f"{what} {key}")
+    stats[key] = (dev, eps, raw)
+
+
+def f32_bits(t):
+    return t.contiguous().view(torch.int32) if t.dtype == F32 else t
+
+
+def f32_sentinel(t):
+    if t.dtype == F32:
+        t.view(torch.int32).fill_(F32_SENT_F)
+    elif t.dtype == torch.uint8:
+        t.fill_(F32_SENT_B)
+    else:
+        t.fill_(F32_SENT_I)
+
+
+def f32_owned(stage, cfg) -> list:
+    """[(buffer, index)]: what a launch of ``stage`` at cfg may write - everything else keeps its bits."""
+    B, sp, o = cfg.B, f32_splits(cfg.B), F32_OUT_ROW
+    rows = slice(0, B)
+    g = lambda k: ("grad", slice(ADA_OFFS[k], ADA_OFFS[k] + ADA_NUMEL[k]))
+    return {
+        "prep": [("w2fwd", slice(0, 9)), ("w2bwd", slice(0, 9))] + ([("w1p", slice(0, 128))] if cfg.train else []),
+        "conv1": [("a1", rows)], "conv2": [("y2", rows)],
+        "pool": [("p", rows)] + ([("pm", rows)] if cfg.train else []),
+        "fc1": [("z1part", slice(0, sp["fc1"] * B))],
+        "head": [("loss_rows", slice(o, o + B))] + ([("h", rows), ("dz1", rows), ("dl", rows)] if cfg.train
+                                                    else [("correct", slice(o, o + B))]),
+        "fc_small": [g("fc2.weight"), g("fc2.bias"), g("fc1.bias"), ("loss_log", slice(cfg.step, cfg.step + 1))],
+        "fc1w": [g("fc1.weight")], "fc1x": [("y2", rows)], "conv2w": [("c2part", slice(0, sp["conv2w"]))],
+        "conv2x_conv1w": [("dx1", rows), ("c1part", slice(0, 1024))],
+        "conv_reduce": [g(k) for k in CONV_NAMES],
+    }[stage]
+
+
+def f32_x_rows(t, cfg):
+    """The normalised rows [B,784] of the launch's batch, and its labels."""
+    src = cfg.rows(t["idx"])
+    return normalize_u8(t["data_u8"][src]).reshape(cfg.B, 784), t["labels"][src].long()
+
+
+def f32_check(stage, before, after, cfg):
+    """One launch of ``stage``: ``before`` / ``after`` are all buffers (with their guard rows) copied back around
+    it.  Everything the stage does not own keeps its bits; everything it owns is compared with the oracle on the
+    operands in ``before``.  Returns {tensor: (deviation, eps, measured eps)} / {decision: (share below margin, cap)}."""
+    B, sp, o, what = cfg.B, f32_splits(cfg.B), F32_OUT_ROW, f"f32 {stage} B={cfg.B}"
+    own = f32_owned(stage, cfg)
+    for name in after:
+        a, b = f32_bits(after[name]).clone(), f32_bits(before[name]).clone()
+        for n, ix in own:
+            if n == name:
+                a[ix], b[ix] = 0, 0
+        assert torch.equal(a, b), f"{what}: {name} was written outside what the stage owns ({int((a != b).sum())} elements)"
+    t, s = before, {}
+    if stage == "prep":
+        for k, v in f32o_prep(t["param"], cfg.train).items():
+            assert torch.equal(f32_bits(after[k][:v.shape[0]]), f32_bits(v)), f"{what}: {k} is not the permutation"
+    elif stage == "conv1":
+        x, _ = f32_x_rows(t, cfg)
+        _held(s, "a1", after["a1"][:B], f32o_conv1(x, t["param"], F32), f32o_conv1(x, t["param"]), what=what)
+    elif stage == "conv2":
+        args = (t["a1"][:B], t["w2fwd"][:9], t["param"])
+        _held(s, "y2", after["y2"][:B], f32o_conv2(*args, F32), f32o_conv2(*args), what=what)
+    elif stage == "pool":
+        r64, r32 = f32o_pool(t["y2"][:B], cfg), f32o_pool(t["y2"][:B], cfg, F32)
+        _held(s, "p", after["p"][:B], r32["p"], r64["p"], what=what)
+        assert (f32_bits(after["p"][:B])[r64["keep"] == 0] == 0).all(), f"{what}: p is not +0 where dropout-1 drops"
+        if cfg.train:
+            pm, ref = after["pm"][:B].long(), r64["pm"].long()
+            assert (pm >> 4 == 0).all(), f"{what}: pm bits above bit 3"
+            assert torch.equal((pm >> 2) & 1, (ref >> 2) & 1), f"{what}: keep bits differ from Philox"
+            # y2 is an operand: the fp32 twin's pooled values equal float64's, tau is 0 and every decision is held
+            tau = EPS_MARGIN * float((r32["win"].to(F64) - r64["win"]).abs().max())
+            top = r64["win"].topk(2, -1).values
+            best = top[..., 0].view(B, 64, 144).permute(0, 2, 1)
+            gap = (top[..., 0] - top[..., 1]).view(B, 64, 144).permute(0, 2, 1)
+            inf = torch.full_like(best, float("inf"))
+            m_code = torch.where(best <= -tau, inf, torch.minimum(gap, best.abs())) if tau > 0 else inf
+            s["argmax below margin"] = (assert_decisions(pm & 3, ref & 3, m_code, tau, CAP, f"{what} argmax code"), CAP)
+            s["pooled>0 below margin"] = (assert_decisions((pm >> 3) & 1, (ref >> 3) & 1, best.abs() if tau > 0 else inf,
+                                                           tau, CAP, f"{what} pooled > 0 bit"), CAP)
+    elif stage == "fc1":
+        S = sp["fc1"]
+        w1 = f32_params(t["param"])["fc1.weight"]
+        got = after["z1part"][:S * B].view(S, B, 128)
+        _held(s, "z1part", got, stage_fc1_partials(t["p"][:B], w1, S, F32), stage_fc1_partials(t["p"][:B], w1, S), what=what)
+    elif stage == "head":
+        _, y = f32_x_rows(t, cfg) if "data_u8" in t else (None, t["labels"][cfg.rows(t["idx"])].long())
+        z = t["z1part"][:sp["fc1"] * B].view(sp["fc1"], B, 128)
+        r64, r32 = f32o_head(z, t["param"], y, cfg), f32o_head(z, t["param"], y, cfg, F32)
+        _held(s, "loss_rows", after["loss_rows"][o:o + B], r32["nll"], r64["nll"], True, what)
+        if cfg.train:
+            for k in ("h", "dz1", "dl"):
+                _held(s, k, after[k][:B], r32[k], r64[k], True, what)
+            assert (f32_bits(after["dl"][:B, 10:]) == 0).all(), f"{what}: dl columns 10..15 are not +0"
+            live = torch.ones(B, 128, dtype=torch.bool) if r64["keep2"] is None else r64["keep2"] > 0
+            assert (after["dz1"][:B][~live] == 0).all() and (after["h"][:B][~live] == 0).all(), \
+                f"{what}: not 0 where dropout-2 drops"
+            ez = f32_eps(r32["z1"], r64["z1"], True)[0]
+            s["dz1 zero below margin"] = (assert_decisions((after["dz1"][:B] == 0)[live], (r64["z1"] <= 0)[live],
+                                                           r64["z1"].abs()[live], ez, CAP, f"{what} dz1 zero pattern"), CAP)
+        else:
+            el = f32_eps(r32["logp"], r64["logp"], True)[0]
+            s["correct below margin"] = (assert_decisions(after["correct"][o:o + B], r64["correct"], r64["gap"], el, CAP,
+                                                          f"{what} correct"), CAP)
+    elif stage == "fc_small":
+        args = (t["h"][:B], t["dl"][:B], t["dz1"][:B], t["loss_rows"][o:o + B])
+        r64, r32 = f32o_fc_small(*args), f32o_fc_small(*args, F32)
+        gv = f32_params(after["grad"])
+        for k in ("fc2.weight", "fc2.bias", "fc1.bias"):
+            _held(s, k, gv[k], r32[k], r64[k], what=what)
+        _held(s, "loss_log", after["loss_log"][cfg.step], r32["loss"], r64["loss"], True, what)
+    elif stage == "fc1w":
+        args = (t["dz1"][:B], t["p"][:B])
+        _held(s, "fc1.weight", f32_params(after["grad"])["fc1.weight"], f32o_fc1w(*args, F32), f32o_fc1w(*args), what=what)
+    elif stage == "fc1x":
+        rows = torch.tensor(check_rows(B))
+        args = (t["dz1"][rows], t["w1p"][:128], t["pm"][rows], cfg)
+        r64, r32 = f32o_fc1x(*args), f32o_fc1x(*args, F32)
+        got = after["y2"][rows]
+        _held(s, "dy2", got, r32["dy2"], r64["dy2"], what=what)
+        assert (f32_bits(got)[~r64["routed"]] == 0).all(), f"{what}: dy2 is not +0 off the routed quadrant"
+    elif stage == "conv2w":
+        args = (t["y2"][:B], t["a1"][:B])
+        _held(s, "c2part", after["c2part"][:sp["conv2w"]], f32o_conv2w(*args, F32), f32o_conv2w(*args), what=what)
+    elif stage == "conv2x_conv1w":
+        args = (t["y2"][:B], t["w2bwd"][:9], t["a1"][:B])
+        r64, r32 = f32o_conv2x(*args), f32o_conv2x(*args, F32)
+        _held(s, "dx1", after["dx1"][:B], r32["dx1"], r64["dx1"], what=what)
+        assert (f32_bits(after["dx1"][:B])[~r64["mask"]] == 0).all(), f"{what}: dx1 is not +0 where the stored a1 is 0"
+        x, _ = f32_x_rows(t, cfg)
+        _held(s, "c1part", after["c1part"][:1024], f32o_conv1w(after["dx1"][:B], x, F32), f32o_conv1w(after["dx1"][:B], x),
+              what=what)
+    elif stage == "conv_reduce":
+        args = (t["c2part"][:sp["conv2w"]], t["c1part"][:1024])
+        r64, r32 = f32o_conv_reduce(*args), f32o_conv_reduce(*args, F32)
+        gv = f32_params(after["grad"])
+        for k in CONV_NAMES:
+            _held(s, k, gv[k], r32[k], r64[k], what=what)
+    else:
+        raise KeyError(stage)
+    return s
+
+
+def f32_twin(stage, t, cfg, mut=None):
+    """What a launch of ``stage`` leaves, from torch fp32 CPU ops (the oracle functions at dtype F32), written into
+    the buffers ``t`` in place: the CPU proof's stand-in for the kernels, and with ``mut`` one subtly wrong kernel."""
+    B, sp, o = cfg.B, f32_splits(cfg.B), F32_OUT_ROW
+    f = lambda v: v.to(F32)
+    if stage == "prep":
+        for k, v in f32o_prep(t["param"], cfg.train, mut).items():
+            t[k][:v.shape[0]] = v
+    elif stage == "conv1":
+        t["a1"][:B] = f32o_conv1(f32_x_rows(t, cfg)[0], t["param"], F32)
+    elif stage == "conv2":
+        t["y2"][:B] = f32o_conv2(t["a1"][:B], t["w2fwd"][:9], t["param"], F32)
+    elif stage == "pool":
+        r = f32o_pool(t["y2"][:B], cfg, F32, mut)
+        t["p"][:B] = r["p"]
+        if cfg.train:
+            t["pm"][:B] = r["pm"]
+    elif stage == "fc1":
+        t["z1part"][:sp["fc1"] * B] = stage_fc1_partials(t["p"][:B], f32_params(t["param"])["fc1.weight"], sp["fc1"], F32).view(-1, 128)
+    elif stage == "head":
+        y = t["labels"][cfg.rows(t["idx"])].long()
+        r = f32o_head(t["z1part"][:sp["fc1"] * B].view(sp["fc1"], B, 128), t["param"], y, cfg, F32, mut)
+        t["loss_rows"][o:o + B] = r["nll"]
+        if cfg.train:
+            t["h"][:B], t["dz1"][:B], t["dl"][:B] = f(r["h"]), f(r["dz1"]), f(r["dl"])
+        else:
+            t["correct"][o:o + B] = r["correct"]
+    elif stage == "fc_small":
+        r = f32o_fc_small(t["h"][:B], t["dl"][:B], t["dz1"][:B], t["loss_rows"][o:o + B], F32, mut)
+        gv = f32_params(t["grad"])
+        for k in ("fc2.weight", "fc2.bias", "fc1.bias"):
+            gv[k].copy_(r[k])
+        t["loss_log"][cfg.step] = r["loss"]
+    elif stage == "fc1w":
+        f32_params(t["grad"])["fc1.weight"].copy_(f32o_fc1w(t["dz1"][:B], t["p"][:B], F32))
+    elif stage == "fc1x":
+        t["y2"][:B] = f32o_fc1x(t["dz1"][:B], t["w1p"][:128], t["pm"][:B], cfg, F32, mut)["dy2"]
+    elif stage == "conv2w":
+        t["c2part"][:sp["conv2w"]] = f32o_conv2w(t["y2"][:B], t["a1"][:B], F32, mut)
+    elif stage == "conv2x_conv1w":
+        t["dx1"][:B] = f32o_conv2x(t["y2"][:B], t["w2bwd"][:9], t["a1"][:B], F32, mut)["dx1"]
+        t["c1part"][:1024] = f32o_conv1w(t["dx1"][:B], f32_x_rows(t, cfg)[0], F32, mut)
+    elif stage == "conv_reduce":
+        r = f32o_conv_reduce(t["c2part"][:sp["conv2w"]], t["c1part"][:1024], F32, mut, stale=t["c2part"][sp["conv2w"]])
+        gv = f32_params(t["grad"])
+        for k in CONV_NAMES:
+            gv[k].copy_(r[k])
+    else:
+        raise KeyError(stage)
+    if mut == "guard_row_written":
+        for n, ix in f32_owned(stage, cfg):
+            if n not in ("grad", "loss_log"):
+                t[n][ix.stop] = 0
+
+
+class F32Machine:
+    """The buffers of one batch size by F32Step field name (CPU tensors here; the GPU test keeps them on the
+    device) and ``launch(stage)``.  This base class launches the torch-fp32 twin."""
+
+    def __init__(self, cfg, tensors, mut=None, mut_stage=None):
+        self.cfg, self.t, self.mut, self.mut_stage = cfg, tensors, mut, mut_stage
+
+    def launch(self, stage):
+        f32_twin(stage, self.t, self.cfg, self.mut if stage == (self.mut_stage or stage) else None)
+
+    def snapshot(self, names=None):
+        return {k: v.detach().cpu().clone() for k, v in self.t.items() if v is not None and (names is None or k in names)}
+
+    def sentinel(self, names):
+        for k in names:
+            f32_sentinel(self.t[k])
+
+
+def f32_run_stage(m, stage, repeat=True):
+    """The per-launch protocol: sentinel over every buffer the stage writes into, one launch, f32_check on the
+    buffers copied back around it, and (``repeat``) a second launch over fresh sentinels that gives the same bits."""
+    names = sorted({n for n, _ in f32_owned(stage, m.cfg)})
+    m.sentinel(names)
+    before = m.snapshot()
+    m.launch(stage)
+    after = m.snapshot()
+    stats = f32_check(stage, before, after, m.cfg)
+    if repeat:
+        m.sentinel(names)
+        m.launch(stage)
+        again = m.snapshot(names)
+        for k in names:
+            assert torch.equal(f32_bits(again[k]), f32_bits(after[k])), f"f32 {stage} B={m.cfg.B}: {k} differs on a second launch"
+    return stats
+
+
+def f32_dataset(B, hand=False):
+    """(images u8 [N,784], labels i32 [N], idx i32 [N]) with N = 4B + 5: forward_case(B), or for the hand-made
+    cases (no trunk) blank images with random labels."""
+    if not hand:
+        imgs, labels, idx = forward_case(B)
+        return imgs.reshape(-1, 784).contiguous(), labels.to(torch.int32), idx.to(torch.int32)
+    g = torch.Generator().manual_seed(300 + B)
+    N = 4 * B + 5
+    return (torch.zeros(N, 784, dtype=torch.uint8), torch.randint(0, 10, (N,), generator=g).to(torch.int32),
+            torch.randperm(N, generator=g).to(torch.int32))
+
+
+def f32_state(cfg) -> torch.Tensor:
+    """The 24-byte StepState as int64[3]: step | flags << 32, seed, rng_base."""
+    return torch.tensor([cfg.step | (cfg.flags << 32), cfg.seed, cfg.rng_base], dtype=torch.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def f32_hand_case(B: int):
+    """Random fp32 operands of the fc kernels at realistic scales, in the spirit of fc_hand_case: p [B,9216], and
+    pm [B,144,64] with all 16 flag patterns at every feature over 16 consecutive rows."""
+    g = torch.Generator().manual_seed(7100 + B)
+    p = torch.randn(B, 9216, generator=g).relu() * INV_KEEP1_F32
+    pm = ((torch.arange(B).view(-1, 1) + 5 * torch.arange(9216).view(1, -1) + (torch.arange(9216) >> 6)) & 15)
+    return dict(p=p, pm=pm.to(torch.uint8).view(B, 144, 64))
+
+
+F32_TRUNK_STAGES = ("prep", "conv1", "conv2", "pool", "fc1", "head", "fc_small", "fc1w", "fc1x", "conv2w",
+                    "conv2x_conv1w", "conv_reduce")
+F32_HAND_STAGES = ("prep", "fc1", "head", "fc_small", "fc1w", "fc1x")
+F32_EVAL_STAGES = F32_TRUNK_STAGES[:6]
+
+
+@functools.lru_cache(maxsize=None)
+def _f32_trained_flat():
+    return f32_flat_params(trained_net())
+
+
+def f32_make(cfg, hand=False, device="cpu"):
+    """(F32Buffers, {F32Step field: tensor}) on ``device``: the workspace plus dataset, index vector, labels, state,
+    parameters (trained_net), gradient and loss log - every buffer a launch writes filled with the sentinel."""
+    from pytorch_mnist_ddp_amd.ops.functional import F32Buffers
+    buf = F32Buffers.allocate(cfg.B, device, trunk=not hand)
+    data, labels, idx = f32_dataset(cfg.B, hand)
+    t = buf.tensors()
+    for v in t.values():
+        f32_sentinel(v)
+    grad, log = torch.zeros(PARAM_TOTAL, dtype=F32, device=device), torch.zeros(F32_LOG_N, dtype=F32, device=device)
+    f32_sentinel(grad), f32_sentinel(log)
+    t.update(data_u8=data.to(device), labels=labels.to(device), idx=idx.to(device), state=f32_state(cfg).to(device),
+             param=_f32_trained_flat().clone().to(device), grad=grad, loss_log=log)
+    return buf, t
+
+
+def f32_load_hand(t, B, which):
+    """Hand-made operands into the buffers: "fwd" = p and pm (before fc1), "bwd" = h, dl, dz1, loss_rows (after
+    the head: what fc_small / fc1w / fc1x read)."""
+    h = f32_hand_case(B)
+    if which == "fwd":
+        t["p"][:B], t["pm"][:B] = h["p"].to(t["p"].device), h["pm"].to(t["pm"].device)
+        return
+    g = torch.Generator().manual_seed(7200 + B)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    dl = torch.zeros(B, 16)
+    dl[:, :10] = rn(B, 10) * (0.3 / B)
+    dz1 = rn(B, 128) * (torch.rand(B, 128, generator=g) < 0.5).float() * (0.05 / B)
+    for k, v in (("h", rn(B, 128).relu() * 2.0), ("dl", dl), ("dz1", dz1)):
+        t[k][:B] = v.to(t[k].device)
+    t["loss_rows"][F32_OUT_ROW:F32_OUT_ROW + B] = (rn(B).abs() + 0.5).to(t["loss_rows"].device)
+
+
+def f32_run_chain(m, stages, hand=False, report=None, repeat=True):
+    """Every stage of ``stages`` in order through f32_run_stage, each on what the stages before it left."""
+    out = {}
+    for st in stages:
+        if hand and st == "fc1":
+            f32_load_hand(m.t, m.cfg.B, "fwd")
+        if hand and st == "fc_small":
+            f32_load_hand(m.t, m.cfg.B, "bwd")
+        out[st] = f32_run_stage(m, st, repeat)
+        if report:
+            report(st, m.cfg.B, out[st])
+    return out
