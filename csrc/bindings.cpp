@@ -479,6 +479,37 @@ PYBIND11_MODULE(_C, m) {
      py::arg("stream"),
      "acc[i] (+)= the sum of dx[i * ns + s] in ascending s; finish: out = acc * scale [* (x_i - b_i)]");
 
+  // ---------------- minimum-norm adversarial examples (DeepFool) ----------------
+  m.attr("DF_CLASSES") = DF_CLASSES;
+  m.attr("DF_SLACK") = DF_SLACK;
+  m.attr("DF_MAX_M") = DF_MAX_M;
+  m.attr("DF_RUNNING") = (int)DF_RUNNING;
+  m.attr("DF_CROSSED") = (int)DF_CROSSED;
+  m.attr("DF_STUCK") = (int)DF_STUCK;
+  m.def("deepfool_init", [](uintptr_t x_u8, uintptr_t x_f32, uintptr_t rows, uintptr_t x, uintptr_t x0_out,
+                            uintptr_t r_tot, uintptr_t status, uintptr_t iters, uintptr_t norm, int M,
+                            uintptr_t stream) {
+    DeepfoolInitArgs a{P<const uint8_t>(x_u8), P<const float>(x_f32), P<float>(rows), P<float>(x), P<float>(x0_out),
+                       P<float>(r_tot), P<int32_t>(status), P<int32_t>(iters), P<float>(norm)};
+    launch_deepfool_init(a, M, S(stream));
+    check_launch();
+  }, py::arg("x_u8"), py::arg("x_f32"), py::arg("rows"), py::arg("x"), py::arg("x0_out"), py::arg("r_tot"),
+     py::arg("status"), py::arg("iters"), py::arg("norm"), py::arg("M"), py::arg("stream"),
+     "rows[10 i + c] = x[i] = x0_i for c < 10, r_tot = 0, status = iters = 0, norm = 0: the start of a DeepFool run");
+  m.def("deepfool_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t y, uintptr_t x0, uintptr_t r_tot, uintptr_t x,
+                            uintptr_t rows, uintptr_t status, uintptr_t iters, uintptr_t norm, float overshoot,
+                            float lo, float hi, int M, uintptr_t stream) {
+    DeepfoolStepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const int32_t>(y), P<const float>(x0),
+                       P<float>(r_tot), P<float>(x), P<float>(rows), P<int32_t>(status), P<int32_t>(iters),
+                       P<float>(norm), overshoot, lo, hi};
+    launch_deepfool_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("y"), py::arg("x0"), py::arg("r_tot"), py::arg("x"), py::arg("rows"),
+     py::arg("status"), py::arg("iters"), py::arg("norm"), py::arg("overshoot"), py::arg("lo"), py::arg("hi"),
+     py::arg("M"), py::arg("stream"),
+     "one L2 DeepFool step per image from its ten gradient rows and losses: r_tot += the step to the nearest "
+     "linearised boundary, x = rows = clamp(x0 + (1 + overshoot) r_tot, lo, hi); crossed / stuck images freeze");
+
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init([](py::bytes uid, int world, int rank, int device, double init_timeout_s, bool wait) {
@@ -689,6 +720,7 @@ PYBIND11_MODULE(_C, m) {
     preload_adv_train();
     preload_smooth();
     preload_attr();
+    preload_deepfool();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -798,6 +830,7 @@ PYBIND11_MODULE(_C, m) {
     preload_adv_train();
     preload_smooth();
     preload_attr();
+    preload_deepfool();
   }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });

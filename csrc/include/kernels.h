@@ -352,6 +352,53 @@ struct AttrReduceArgs {
 };
 void launch_attr_reduce(const AttrReduceArgs& a, int M, hipStream_t s);
 
+// ---------------- minimum-norm adversarial examples: L2 DeepFool (deepfool.hip) ----------------
+// Image i < M of a chunk owns the DF_CLASSES rows 10 i + c of the fp32 row buffer `rows` (the xin of trunk_fwd, row
+// c labelled c) and of the gradient buffer dx (input_grad's plain output): g_c = d NLL_c / d x, and head_train's
+// loss_rows[10 i + c] = -log p_c.  One workgroup per image, fp32, fixed-tree sums, no atomics.
+// deepfool_init: the ten rows and x[i] = the normalised image x0_i (exactly one of x_u8, normalised in-register,
+// bitwise trunk_fwd's value, and x_f32), r_tot[i] = 0, status[i] = iters[i] = 0, norm[i] = 0; x0_out (required with
+// x_u8, optional with x_f32) receives x0_i: the x0 of the step.
+// deepfool_step, per image with y = y[i] the class being left (f_k = loss_y - loss_k, w_k = g_y - g_k, k != y):
+//   status != 0                                  -> nothing is stored (frozen)
+//   some loss_k < loss_y, or == with k < y       -> status = DF_CROSSED, nothing else stored (head_eval's argmax)
+//   l = the first smallest (|f_k| + DF_SLACK) / sqrt(sum w_k^2) in ascending k, skipping sqrt(..) < PGD_L2_TINY and
+//       NaN ratios; none left: the first k with a NaN ratio (its NaN then fills the image), else status = DF_STUCK
+//       and nothing else stored (a y outside [0, 10) is stuck too)
+//   r_tot += ((|f_l| + DF_SLACK) / sum w_l^2) * w_l;  x_next = min(max(x0 + (1 + overshoot) * r_tot, lo), hi) (a NaN
+//   passes) -> x[i] and the ten rows;  norm[i] = sqrt(sum (x_next - x0)^2);  iters[i] += 1
+// Rows and entries past M are not written.  The fp32 arrays are 16-byte aligned, x_u8 4-byte aligned.
+constexpr int DF_CLASSES = 10;
+constexpr float DF_SLACK = 1e-4f;                        // added to |f_k| (the constant of the authors' code)
+constexpr int DF_MAX_M = (int)(SMOOTH_MAX_ROWS / DF_CLASSES);   // the rows of a chunk stay within SMOOTH_MAX_ROWS
+enum DfStatus { DF_RUNNING = 0, DF_CROSSED = 1, DF_STUCK = 2 };
+struct DeepfoolInitArgs {
+  const uint8_t* x_u8;        // [M][784] raw rows, or null
+  const float* x_f32;         // [M][784] normalised rows, or null
+  float* rows;                // fp32 [10 M][784]
+  float* x;                   // fp32 [M][784] the iterate
+  float* x0_out;              // fp32 [M][784] the normalised image (required with x_u8)
+  float* r_tot;               // fp32 [M][784] the accumulated perturbation
+  int32_t* status;            // [M] DfStatus
+  int32_t* iters;             // [M] updates made
+  float* norm;                // [M] |x - x0|
+};
+void launch_deepfool_init(const DeepfoolInitArgs& a, int M, hipStream_t s);   // M in [1, DF_MAX_M]
+struct DeepfoolStepArgs {
+  const float* dx;            // fp32 [10 M][784] gradient rows
+  const float* loss_rows;     // [10 M] -log p_c of row 10 i + c
+  const int32_t* y;           // [M] the class being left
+  const float* x0;            // fp32 [M][784] the clean normalised image
+  float* r_tot;               // fp32 [M][784]
+  float* x;                   // fp32 [M][784]
+  float* rows;                // fp32 [10 M][784]
+  int32_t* status;            // [M]
+  int32_t* iters;             // [M]
+  float* norm;                // [M]
+  float overshoot, lo, hi;    // overshoot >= 0; valid range in normalised units
+};
+void launch_deepfool_step(const DeepfoolStepArgs& a, int M, hipStream_t s);   // M in [1, DF_MAX_M], overshoot >= 0
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -425,6 +472,7 @@ void preload_attack_step();
 void preload_adv_train();
 void preload_smooth();
 void preload_attr();
+void preload_deepfool();
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

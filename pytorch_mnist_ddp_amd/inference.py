@@ -33,6 +33,8 @@ in eval mode (where noise is drawn: the same distribution, not the same bits):
 * ``smoothed_counts`` / ``certify`` (randomized smoothing: the class counts of Gaussian-noised copies of an image and
   the certified L2 radius they give; ``sigma`` in pixel units): ``ops.smooth.fused_smooth_counts`` / ``torch.randn``
   over the reference forward; the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path;
+* ``minimum_norm`` (L2 DeepFool: the smallest perturbation that leaves the class, per image; radii in pixel units):
+  ``ops.deepfool.fused_minimum_norm`` / ``reference_minimum_norm``;
 * ``attribute`` (integrated gradients and SmoothGrad of log p_y(x): n gradient rows per image, reduced; ``sigma`` and
   scalar baselines in pixel units): ``ops.attribute.fused_attribution`` / ``reference_attribution``.
 
@@ -50,7 +52,8 @@ import torch.nn.functional as F
 from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist  # noqa: F401
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
-from .ops.functional import PGD_L2_TINY, attr_path_reference, attr_reduce_reference, pgd_l2_step_reference
+from .ops.functional import (DF_CLASSES, PGD_L2_TINY, attr_path_reference, attr_reduce_reference,
+                             deepfool_step_reference, pgd_l2_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -101,6 +104,41 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
 
 ATTRIBUTION_METHODS = ("integrated_gradients", "smoothgrad")
 _REF_ROWS = 1000                    # rows per forward / backward (and per generator draw) of the torch paths
+
+
+def reference_minimum_norm(net: Net, x0: torch.Tensor, labels: torch.Tensor, steps: int, overshoot: float,
+                           lo: float, hi: float):
+    """``ops.deepfool.fused_minimum_norm`` in torch float32 on any device: L2 DeepFool with the kernel's formulas
+    (``deepfool_step_reference``: the same selection rule, slack, skip rule and freezing), the ten class gradients
+    and losses of an image from one autograd pass over ``Net.forward_reference`` in eval mode on its ten rows,
+    labelled 0 .. 9 (the net's mode is restored afterwards).  ``x0``: float32 [B, 784] normalised images; same
+    return: ``(x_adv [B, 784], norm [B], iters int32 [B], status int32 [B])``.  The images run in chunks of
+    ``_REF_ROWS`` // 10, each until no image of it is still running or ``steps`` iterations are made.  The CPU /
+    fp32 path of ``Predictor.minimum_norm`` and the reference of its GPU tests."""
+    B, dev = x0.shape[0], x0.device
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(dev)
+    x_adv, norm = x0.clone(), torch.zeros(B, dtype=torch.float32, device=dev)
+    iters = torch.zeros(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    mc = _REF_ROWS // DF_CLASSES
+    with _eval_mode(net):
+        for i0 in range(0, B, mc):
+            c0, yc = x0[i0:i0 + mc], y[i0:i0 + mc]
+            m = c0.shape[0]
+            lab10 = torch.arange(DF_CLASSES, device=dev).repeat(m)
+            state = (torch.zeros_like(c0), c0.clone(), status[i0:i0 + m], iters[i0:i0 + m], norm[i0:i0 + m])
+            for _ in range(int(steps)):
+                rows = state[1].repeat_interleave(DF_CLASSES, dim=0).requires_grad_()
+                with torch.enable_grad():
+                    lp = net.forward_reference(rows.view(DF_CLASSES * m, 1, 28, 28))
+                    g, = torch.autograd.grad(F.nll_loss(lp, lab10, reduction='sum'), rows)
+                loss_rows = -lp.detach()[torch.arange(DF_CLASSES * m, device=dev), lab10]
+                state = deepfool_step_reference(g, loss_rows, yc, c0, *state, overshoot, lo, hi)
+                if not bool((state[2] == 0).any()):
+                    break
+            x_adv[i0:i0 + m], status[i0:i0 + m], iters[i0:i0 + m], norm[i0:i0 + m] = state[1:]
+    return x_adv, norm, iters, status
 
 
 def _smooth_generator_seed(seed: int, image_id: int) -> int:
@@ -348,6 +386,45 @@ class Predictor:
             hits += (lp.argmax(dim=1) == y).sum()
         return float(loss.item()), int(hits.item()), n
 
+    def minimum_norm(self, x: torch.Tensor, labels: torch.Tensor | None = None, steps: int = 50,
+                     overshoot: float = 0.02, check_every: int = 8):
+        """(x_adv, radii, log_probs, found): minimum-norm adversarial examples of ``x`` by L2 DeepFool
+        (Moosavi-Dezfooli, Fawzi, Frossard 2016) - how far the decision boundary is from each image.  ``x_adv``:
+        float32 [B,1,28,28] in NORMALISED units, inside the valid pixel range [0, 1]; ``radii``: float32 [B], the L2
+        norm of ``x_adv - x`` in pixel units on the [0, 1] scale (as every ``eps`` here); ``log_probs``: the
+        predictor's own float32 [B,10] forward of ``x_adv``; ``found``: bool [B], whether that forward no longer
+        gives ``labels``.  An image already misclassified on entry keeps ``x_adv = x``, radius 0 and is found.
+
+        ``labels`` ([B] integers): the class each image is to leave, or the class predicted on the clean input when
+        None.  At most ``steps`` iterations per image: each steps to the nearest boundary of the classifier
+        linearised at the iterate, x_adv = clamp(x + (1 + ``overshoot``) * (the sum of the steps)); an image stops
+        once the iterate has left its class.  ``check_every``: on the GPU, look every that many iterations whether
+        every image has stopped (0: never; the result does not depend on it).  Inference semantics as
+        ``input_gradient``: no dropout; the net's mode, parameters and gradients are untouched.  GPU with
+        ``dtype="bf16"``: the native loop ``ops.deepfool.fused_minimum_norm``; CPU, or ``dtype="fp32"``:
+        ``reference_minimum_norm``.  ``x``: uint8 [B,28,28] / [B,784] images or float [B,1,28,28] normalised input."""
+        B = self._check_input(x)
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"minimum_norm: steps must be a positive integer, got {steps}")
+        if not overshoot >= 0:
+            raise ValueError(f"minimum_norm: overshoot must be >= 0, got {overshoot}")
+        if isinstance(check_every, bool) or check_every != int(check_every) or check_every < 0:
+            raise ValueError(f"minimum_norm: check_every must be a non-negative integer, got {check_every}")
+        if labels is None:
+            labels = self._forward(x)[1]
+        else:
+            labels = self._labels("minimum_norm", labels, B, check_range=True)
+        if self.native:
+            from .ops.deepfool import fused_minimum_norm
+            x_adv, norm, _, _ = fused_minimum_norm(self.net, self._rows_native(x, B), labels, int(steps),
+                                                   float(overshoot), PIXEL_LO, PIXEL_HI, int(check_every))
+        else:
+            x_adv, norm, _, _ = reference_minimum_norm(self.net, _rows_f32(x, B, self.device), labels, int(steps),
+                                                       float(overshoot), PIXEL_LO, PIXEL_HI)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        lp = self._forward(x_adv)[0]
+        return x_adv, norm * MNIST_STD, lp, lp.argmax(dim=1) != labels
+
     # ------------------------------------------------------------------ randomized smoothing
     def smoothed_counts(self, x: torch.Tensor, sigma: float, n: int, seed: int = 0, ids=None,
                         sample_base: int = 0) -> torch.Tensor:
@@ -573,6 +650,17 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--certify-count', type=int, default=None, metavar='M',
                     help='certify the first M images of the split (default: all)')
     ap.add_argument('--certify-seed', type=int, default=0, help='seed of the noise (default: 0)')
+    ap.add_argument('--min-norm', action='store_true', default=False,
+                    help='also report the minimum-norm (L2 DeepFool) adversarial radius of the images against their '
+                         'true labels: how many are found, the median and mean radius in pixel units (default: off)')
+    ap.add_argument('--min-norm-steps', type=int, default=50, metavar='K',
+                    help='most DeepFool iterations per image (default: 50)')
+    ap.add_argument('--min-norm-overshoot', type=float, default=0.02, metavar='O',
+                    help='overshoot past the linearised boundary (default: 0.02)')
+    ap.add_argument('--min-norm-count', type=int, default=None, metavar='M',
+                    help='attack the first M images of the split (default: all)')
+    ap.add_argument('--min-norm-radii', type=_radii, default=(), metavar='R1,R2,...',
+                    help='L2 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
     return ap
 
 
@@ -594,6 +682,24 @@ def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, 
     """The ``Test set:`` line's figures (``utils.logging.test_line``) for the attacked split."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
     return f"Adversarial set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}): {figures}"
+
+
+def minimum_norm_stats(radii: torch.Tensor, found: torch.Tensor, clean: torch.Tensor, at=()):
+    """``(found, median, mean, accuracy_at)`` of per-image DeepFool results: how many images were found; the median
+    and mean radius over the found images that were correct on the clean input (None when there is none; the median
+    of an even count is the mean of the middle two); and per radius R of ``at`` how many images are correct on the
+    clean input and either not found or found only at a radius > R."""
+    r = radii[found & clean].double()
+    median = float(r.quantile(0.5)) if r.numel() else None
+    mean = float(r.mean()) if r.numel() else None
+    return int(found.sum()), median, mean, [int((clean & (~found | (radii > R))).sum()) for R in at]
+
+
+def minimum_norm_line(steps: int, overshoot: float, m: int, found: int, median, mean) -> str:
+    """The ``Minimum-norm set`` line of ``mnist_predict.py --min-norm``."""
+    fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
+    return (f"Minimum-norm set (L2 DeepFool, steps={steps}, overshoot={overshoot:g}): "
+            f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
 def completeness_gap(predictor: "Predictor", attr: torch.Tensor, lp: torch.Tensor, labels: torch.Tensor,
@@ -671,6 +777,25 @@ def predict_main(argv=None) -> int:
                       certify_alpha=args.certify_alpha, certify_seed=args.certify_seed, certify_count=m,
                       certify_radii=list(args.certify_radii), certify_correct=certified,
                       certify_abstained=abstained)
+    if args.min_norm:
+        m = n if args.min_norm_count is None else max(1, min(n, args.min_norm_count))
+        found = torch.empty(m, dtype=torch.bool)
+        clean = torch.empty(m, dtype=torch.bool)
+        radii = torch.empty(m, dtype=torch.float32)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            yb = data.targets[i:j]
+            clean[i:j] = (predictor.predict(images[i:j]).cpu() == yb.long().cpu())
+            _, r, _, fnd = predictor.minimum_norm(images[i:j], yb, args.min_norm_steps, args.min_norm_overshoot)
+            radii[i:j], found[i:j] = r.cpu(), fnd.cpu()
+        stats = minimum_norm_stats(radii, found, clean, args.min_norm_radii)
+        print(minimum_norm_line(args.min_norm_steps, args.min_norm_overshoot, m, *stats[:3]))
+        for r, c in zip(args.min_norm_radii, stats[3]):
+            print(f"Accuracy at radius {r:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
+        record.update(min_norm_steps=args.min_norm_steps, min_norm_overshoot=args.min_norm_overshoot,
+                      min_norm_count=m, min_norm_found=stats[0], min_norm_median_radius=stats[1],
+                      min_norm_mean_radius=stats[2],
+                      min_norm_accuracy_at={f"{r:g}": c for r, c in zip(args.min_norm_radii, stats[3])})
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

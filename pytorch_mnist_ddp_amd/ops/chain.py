@@ -99,6 +99,11 @@ class GradChain:
         C, s, dyc, a1, w2d, c1w = self._ig
         C.input_grad_step(dyc, a1, w2d, c1w, px, px0, pout, alpha, eps, lo, hi, rows, s)
 
+    @property
+    def loss_rows(self) -> int:
+        """The device pointer of the set's ``loss_rows``: after ``run``, row r holds -log p of its label."""
+        return native.ptr(self._buf.loss_rows)
+
     def release(self) -> None:
         buf, self._buf = self._buf, None
         if buf is not None:

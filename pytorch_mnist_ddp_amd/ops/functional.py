@@ -573,6 +573,160 @@ def attr_reduce(dx: torch.Tensor, M: int, ns: int, acc: torch.Tensor | None = No
     return out
 
 
+DF_CLASSES = 10                     # rows per image of the DeepFool kernels (csrc/include/kernels.h)
+DF_SLACK = 1e-4                     # added to |f_k| in the ratio and the step (kernels.h DF_SLACK)
+DF_MAX_M = SMOOTH_MAX_ROWS // DF_CLASSES     # most images one deepfool_init / deepfool_step launch takes (kernels.h)
+DF_RUNNING, DF_CROSSED, DF_STUCK = 0, 1, 2   # the per-image status (kernels.h DfStatus)
+
+
+def deepfool_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0: torch.Tensor,
+                            r_tot: torch.Tensor, x: torch.Tensor, status: torch.Tensor, iters: torch.Tensor,
+                            norm: torch.Tensor, overshoot: float, lo: float, hi: float):
+    """``deepfool_step`` in torch ops on any device, in the dtype of ``dx`` (float32: the CPU / fp32 path of
+    ``Predictor.minimum_norm``; float64: the oracle of the kernel's tests).  Same operands - ``dx`` [10 M, 784],
+    ``loss_rows`` [10 M], ``y`` [M] integers, ``x0`` / ``r_tot`` / ``x`` [M, 784], ``status`` / ``iters`` [M]
+    integers, ``norm`` [M] - none of them modified; returns the new ``(r_tot, x, status, iters, norm)``.  Per image,
+    with f_k = loss_y - loss_k and w_k = g_y - g_k for k != y:
+
+        frozen (status != 0): everything kept;  crossed (some loss_k < loss_y, or == with k < y): status = 1
+        l = the first smallest (|f_k| + DF_SLACK) / |w_k| in ascending k, skipping |w_k| < PGD_L2_TINY and NaN ratios;
+            none left: the first k with a NaN ratio (its NaN fills the image), else status = 2 (stuck)
+        r_tot += ((|f_l| + DF_SLACK) / |w_l|^2) * w_l;  x = clamp(x0 + (1 + overshoot) * r_tot, lo, hi)
+        norm = |x - x0|;  iters += 1
+
+    ``overshoot``, ``lo`` and ``hi`` are rounded to float32 first, as the kernel receives them."""
+    import numpy as np
+    dt, dev = dx.dtype, dx.device
+    M = y.numel()
+    g = dx.reshape(M, DF_CLASSES, 784)
+    loss = loss_rows.reshape(M, DF_CLASSES).to(dt)
+    x0, r_tot, x = x0.reshape(M, 784).to(dt), r_tot.reshape(M, 784).to(dt), x.reshape(M, 784).to(dt)
+    ar = torch.arange(M, device=dev)
+    yl = y.reshape(M).long()
+    inside = (yl >= 0) & (yl < DF_CLASSES)
+    yc = yl.clamp(0, DF_CLASSES - 1)
+    k = torch.arange(DF_CLASSES, device=dev)[None, :]
+    other = k != yc[:, None]
+    ly = loss[ar, yc][:, None]
+    crossed = (other & ((loss < ly) | ((loss == ly) & (k < yc[:, None])))).any(dim=1)
+    f = ly - loss
+    w = g[ar, yc][:, None, :] - g                                        # [M, 10, 784]
+    n2 = w.square().sum(dim=2)
+    n = n2.sqrt()
+    num = f.abs() + torch.tensor(float(np.float32(DF_SLACK)), dtype=dt, device=dev)
+    ratio = num / n
+    nan = ratio != ratio
+    ok = other & ~nan & ~(n < PGD_L2_TINY)
+    l = torch.full((M,), -1, dtype=torch.long, device=dev)
+    l_nan = torch.full((M,), -1, dtype=torch.long, device=dev)
+    best = torch.zeros(M, dtype=dt, device=dev)
+    for c in range(DF_CLASSES):                                          # ascending k, strict <: the first minimum
+        take = ok[:, c] & ((l < 0) | (ratio[:, c] < best))
+        best = torch.where(take, ratio[:, c], best)
+        l = torch.where(take, torch.full_like(l, c), l)
+        l_nan = torch.where(other[:, c] & nan[:, c] & (l_nan < 0), torch.full_like(l_nan, c), l_nan)
+    l = torch.where(l < 0, l_nan, l)
+    active = status.reshape(M).long() == DF_RUNNING
+    cross = active & inside & crossed
+    upd = active & inside & ~crossed & (l >= 0)
+    stuck = active & ~cross & ~upd
+    lc = l.clamp_min(0)
+    scale = num[ar, lc] / n2[ar, lc]
+    r_new = r_tot + scale[:, None] * w[ar, lc]
+    os1 = torch.tensor(1.0, dtype=dt, device=dev) + torch.tensor(float(np.float32(overshoot)), dtype=dt, device=dev)
+    x_new = (x0 + os1 * r_new).clamp(float(np.float32(lo)), float(np.float32(hi)))
+    norm_new = (x_new - x0).square().sum(dim=1).sqrt()
+    u = upd[:, None]
+    st = status.reshape(M).clone()
+    st[cross] = DF_CROSSED
+    st[stuck] = DF_STUCK
+    return (torch.where(u, r_new, r_tot), torch.where(u, x_new, x), st,
+            iters.reshape(M) + upd.to(iters.dtype), torch.where(upd, norm_new, norm.reshape(M).to(dt)))
+
+
+def _df_vec(name: str, what: str, t: torch.Tensor, dtype, count: int, device, at_least: str) -> None:
+    if t.dtype != dtype or not t.is_contiguous() or t.device != device or t.numel() < count:
+        raise ValueError(f"{name}: {what} must be contiguous {str(dtype).split('.')[-1]} with at least {at_least} "
+                         f"entries on the images' device")
+
+
+def deepfool_init(x: torch.Tensor, rows: torch.Tensor | None = None, x_out: torch.Tensor | None = None,
+                  x0_out: torch.Tensor | None = None, r_tot: torch.Tensor | None = None,
+                  status: torch.Tensor | None = None, iters: torch.Tensor | None = None,
+                  norm: torch.Tensor | None = None):
+    """The start of a DeepFool run (``csrc/kernels/deepfool.hip``), one launch: for each of the M images ``x`` (uint8
+    [M, 784] raw rows, normalised in the kernel bit for bit ``data.datasets.PIXEL_LUT[u8]``, or float32 [M, 784]
+    normalised rows) the ten rows ``rows[10 i + c]`` and ``x_out[i]`` = the normalised image, ``r_tot[i]`` = 0,
+    ``status[i]`` = ``iters[i]`` = 0, ``norm[i]`` = 0, and ``x0_out[i]`` = the normalised image (always written with
+    uint8 rows; with float32 rows only when given).  Outputs (float32 [>= 10 M, 784] / [>= M, 784], int32 / float32
+    [>= M]) are allocated when None; nothing past M is written.  Returns ``(rows, x_out, x0, r_tot, status, iters,
+    norm)`` with ``x0`` the buffer the step reads: ``x0_out``, or ``x`` itself for float32 rows without one."""
+    if x.dim() != 2 or x.shape[1] != 784 or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous() \
+            or x.device.type != "cuda":
+        raise ValueError("deepfool_init: x must be contiguous uint8 or float32 [M, 784] on the GPU")
+    M, dev = x.shape[0], x.device
+    if M < 1 or M > DF_MAX_M:
+        raise ValueError(f"deepfool_init: M = {M} images must be in [1, DF_MAX_M = {DF_MAX_M}] a launch")
+    u8 = x.dtype == torch.uint8
+    f32 = dict(dtype=torch.float32, device=dev)
+    rows = torch.empty(DF_CLASSES * M, 784, **f32) if rows is None else rows
+    x_out = torch.empty(M, 784, **f32) if x_out is None else x_out
+    if x0_out is None and u8:
+        x0_out = torch.empty(M, 784, **f32)
+    r_tot = torch.empty(M, 784, **f32) if r_tot is None else r_tot
+    status = torch.empty(M, dtype=torch.int32, device=dev) if status is None else status
+    iters = torch.empty(M, dtype=torch.int32, device=dev) if iters is None else iters
+    norm = torch.empty(M, **f32) if norm is None else norm
+    _f32_rows("deepfool_init", "rows", rows, DF_CLASSES * M, dev, at_least="10 M")
+    _f32_rows("deepfool_init", "x_out", x_out, M, dev, at_least="M")
+    _f32_rows("deepfool_init", "r_tot", r_tot, M, dev, at_least="M")
+    if x0_out is not None:
+        _f32_rows("deepfool_init", "x0_out", x0_out, M, dev, at_least="M")
+    _df_vec("deepfool_init", "status", status, torch.int32, M, dev, "M")
+    _df_vec("deepfool_init", "iters", iters, torch.int32, M, dev, "M")
+    _df_vec("deepfool_init", "norm", norm, torch.float32, M, dev, "M")
+    p = native.ptr
+    _C().deepfool_init(p(x) if u8 else 0, 0 if u8 else p(x), p(rows), p(x_out), p(x0_out), p(r_tot), p(status),
+                       p(iters), p(norm), M, _s())
+    return rows, x_out, (x0_out if x0_out is not None else x), r_tot, status, iters, norm
+
+
+def deepfool_step(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, r_tot: torch.Tensor,
+                  x: torch.Tensor, rows: torch.Tensor, status: torch.Tensor, iters: torch.Tensor, norm: torch.Tensor,
+                  overshoot: float, lo: float, hi: float, M: int | None = None) -> None:
+    """One L2 DeepFool step per image (``csrc/kernels/deepfool.hip``), one launch, in place: from the ten gradient
+    rows ``dx[10 i + c]`` (float32 [>= 10 M, 784], what ``input_grad`` wrote) and losses ``loss_rows[10 i + c]`` =
+    -log p_c (float32 [>= 10 M], what ``head_train`` stored), the class ``y[i]`` being left (int32 [>= M]) and the
+    clean image ``x0[i]``, the update of ``deepfool_step_reference`` on ``r_tot``, ``x`` (float32 [>= M, 784]), the
+    image's ten ``rows`` (float32 [>= 10 M, 784]), ``status``, ``iters`` (int32 [>= M]) and ``norm`` (float32
+    [>= M]).  float32 throughout, the sums a fixed tree: the same operands give the same bits.  An image with
+    ``status`` != 0 is frozen: nothing of it is stored.  ``M``: the images of the launch (default ``y.numel()``);
+    nothing past M is touched."""
+    if dx.dim() != 2 or dx.device.type != "cuda":
+        raise ValueError("deepfool_step: dx must be a float32 [10 M, 784] tensor on the GPU")
+    dev = dx.device
+    M = int(y.numel() if M is None else M)
+    if M < 1 or M > DF_MAX_M:
+        raise ValueError(f"deepfool_step: M = {M} images must be in [1, DF_MAX_M = {DF_MAX_M}] a launch")
+    _f32_rows("deepfool_step", "dx", dx, DF_CLASSES * M, dev, at_least="10 M")
+    _f32_rows("deepfool_step", "rows", rows, DF_CLASSES * M, dev, at_least="10 M")
+    for what, t in (("x0", x0), ("r_tot", r_tot), ("x", x)):
+        _f32_rows("deepfool_step", what, t, M, dev, at_least="M")
+    _df_vec("deepfool_step", "loss_rows", loss_rows, torch.float32, DF_CLASSES * M, dev, "10 M")
+    _df_vec("deepfool_step", "y", y, torch.int32, M, dev, "M")
+    _df_vec("deepfool_step", "status", status, torch.int32, M, dev, "M")
+    _df_vec("deepfool_step", "iters", iters, torch.int32, M, dev, "M")
+    _df_vec("deepfool_step", "norm", norm, torch.float32, M, dev, "M")
+    ptrs = [t.data_ptr() for t in (dx, x0, r_tot, x, rows)]
+    if len(set(ptrs)) != len(ptrs):
+        raise ValueError("deepfool_step: dx, x0, r_tot, x and rows must be five buffers")
+    if not (overshoot >= 0 and lo <= hi):
+        raise ValueError("deepfool_step: need overshoot >= 0 and lo <= hi")
+    p = native.ptr
+    _C().deepfool_step(p(dx), p(loss_rows), p(y), p(x0), p(r_tot), p(x), p(rows), p(status), p(iters), p(norm),
+                       float(overshoot), float(lo), float(hi), M, _s())
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
