@@ -138,6 +138,19 @@ AdadeltaArgs ada_from_dict(const py::dict& d) {
   return a;
 }
 
+// ConvBwdArgs of a stand-alone conv backward launch (the conv_bwd binding and XgmiComm.conv_reduce_fused)
+ConvBwdArgs conv_args(uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t b1c, uintptr_t data_u8,
+                      uintptr_t idx, int64_t idx_stride, uintptr_t state, uintptr_t c1part, uintptr_t w2part,
+                      uintptr_t grad, float grad_scale, int B, uintptr_t xin, uintptr_t c1red) {
+  ConvBwdArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d),
+                P<const float>(w1c), P<const float>(b1c), P<const uint8_t>(data_u8), P<const int32_t>(idx),
+                idx_stride, P<const StepState>(state), P<float>(c1part), P<float>(w2part), P<float>(grad),
+                grad_scale, conv_wgrad_groups(B), P<const float>(xin)};
+  a.c1_rows = conv_dgrad_c1_rows(B);
+  a.c1red = P<float>(c1red);
+  return a;
+}
+
 // F32Step of a stand-alone fp32 launch from caller-owned device pointers (null where a key is absent)
 F32Step f32_from_dict(const py::dict& d, int64_t idx_step_stride, float inv_batch) {
   auto ptr = [&](const char* k) -> uintptr_t { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; };
@@ -271,12 +284,8 @@ PYBIND11_MODULE(_C, m) {
                        uintptr_t w2part, uintptr_t grad, float grad_scale, int B, uintptr_t stream,
                        uintptr_t xin, int stages, uintptr_t c1red, int update, int upd_lo, int upd_hi,
                        py::object ada) {
-    ConvBwdArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d),
-                  P<const float>(w1c), P<const float>(b1c), P<const uint8_t>(data_u8), P<const int32_t>(idx),
-                  idx_stride, P<const StepState>(state), P<float>(c1part), P<float>(w2part), P<float>(grad),
-                  grad_scale, conv_wgrad_groups(B), P<const float>(xin)};
-    a.c1_rows = conv_dgrad_c1_rows(B);
-    a.c1red = P<float>(c1red);
+    const ConvBwdArgs a = conv_args(dyc, a1, w2d, w1c, b1c, data_u8, idx, idx_stride, state, c1part, w2part, grad,
+                                    grad_scale, B, xin, c1red);
     // stages: 1 = dgrad (+ the conv1 pre-reduce with c1red), 2 = wgrad, 4 = reduce (reads c1red when given)
     if (stages <= 0 || stages > 7) throw std::runtime_error("conv_bwd: bad stage mask");
     if (stages & 1) launch_conv_dgrad(a, B, S(stream));
@@ -564,7 +573,12 @@ PYBIND11_MODULE(_C, m) {
       // the communicator's own buffers as DLPack capsules (torch.utils.dlpack.from_dlpack): zero-copy
       // fp32 [numel] views that keep the communicator alive
       .def("dlpack", [](std::shared_ptr<XgmiComm> c, const std::string& which) {
-        if (which != "in" && which != "out") throw std::runtime_error("dlpack: which must be 'in' or 'out'");
+        // "flags" / "stage" (tests): this rank's flag blocks [channels][2][8][512] (int32 bits behind a
+        // float view) and staging slots [channels][2][oneshot_max]
+        if (which == "flags")
+          return dlpack_f32(reinterpret_cast<float*>(c->flags()), (int64_t)c->channels() * XGMI_FLAG_INTS, c->device(), c);
+        if (which == "stage") return dlpack_f32(c->stage(), (int64_t)c->channels() * 2 * c->oneshot_max(), c->device(), c);
+        if (which != "in" && which != "out") throw std::runtime_error("dlpack: which must be 'in', 'out', 'flags' or 'stage'");
         return dlpack_f32(which == "in" ? c->in() : c->out(), c->numel(), c->device(), c);
       })
       .def_property_readonly("ordering", &XgmiComm::ordering)
@@ -590,9 +604,41 @@ PYBIND11_MODULE(_C, m) {
         py::gil_scoped_release nogil;   // one IPC import per peer
         c.connect(v);
       })
-      .def("allreduce", [](XgmiComm& c, int channel, int64_t offset, int64_t count, uintptr_t stream) {
-        c.allreduce(channel, offset, count, S(stream));
-      }, py::arg("channel"), py::arg("offset"), py::arg("count"), py::arg("stream"))
+      // ada (a dict as the adadelta / conv_bwd bindings take; hold pointers, signal_start and the conv
+      // part's wait_* stay null: the engine's) fuses the Adadelta step; max_wg > 0 shrinks the planned grid
+      .def("allreduce", [](XgmiComm& c, int channel, int64_t offset, int64_t count, uintptr_t stream, py::object ada,
+                           int max_wg) {
+        if (ada.is_none()) {
+          c.allreduce(channel, offset, count, S(stream), nullptr, max_wg);
+        } else {
+          const AdadeltaArgs u = ada_from_dict(ada.cast<py::dict>());
+          c.allreduce(channel, offset, count, S(stream), &u, max_wg);
+        }
+        check_launch();
+      }, py::arg("channel"), py::arg("offset"), py::arg("count"), py::arg("stream"), py::arg("ada") = py::none(),
+         py::arg("max_wg") = 0)
+      .def("allreduce_fc_fused", [](XgmiComm& c, int channel, uintptr_t stream, py::dict ada, int max_wg) {
+        c.allreduce_fc_fused(channel, S(stream), ada_from_dict(ada), max_wg);
+        check_launch();
+      }, py::arg("channel"), py::arg("stream"), py::arg("ada"), py::arg("max_wg") = 0)
+      .def("conv_reduce_fused", [](XgmiComm& c, int channel, uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c,
+                                   uintptr_t b1c, uintptr_t data_u8, uintptr_t idx, int64_t idx_stride,
+                                   uintptr_t state, uintptr_t c1part, uintptr_t w2part, uintptr_t grad,
+                                   float grad_scale, int B, uintptr_t stream, py::dict ada, uintptr_t xin,
+                                   uintptr_t c1red, int lo, int hi, int max_wg) {
+        if (lo < 0 || hi > RED_ALL_PARTS || lo >= hi) throw std::runtime_error("conv_reduce_fused: bad reduce parts");
+        XgmiConvPart part;
+        part.lo = lo;
+        part.hi = hi;
+        c.conv_reduce_fused(channel, conv_args(dyc, a1, w2d, w1c, b1c, data_u8, idx, idx_stride, state, c1part,
+                                               w2part, grad, grad_scale, B, xin, c1red),
+                            B, S(stream), ada_from_dict(ada), part, max_wg);
+        check_launch();
+      }, py::arg("channel"), py::arg("dy"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("b1c"),
+         py::arg("data_u8"), py::arg("idx"), py::arg("idx_stride"), py::arg("state"), py::arg("c1part"),
+         py::arg("w2part"), py::arg("grad"), py::arg("grad_scale"), py::arg("B"), py::arg("stream"), py::arg("ada"),
+         py::arg("xin") = 0, py::arg("c1red") = 0, py::arg("lo") = 0, py::arg("hi") = RED_ALL_PARTS,
+         py::arg("max_wg") = 0)
       .def("error", &XgmiComm::error)
       .def("set_timeout_seconds", &XgmiComm::set_timeout_seconds)
       .def("set_fences", &XgmiComm::set_fences)
@@ -808,6 +854,22 @@ PYBIND11_MODULE(_C, m) {
     check_launch();
   }, py::arg("plan"), py::arg("templates"), py::arg("n"), py::arg("out"), py::arg("stream"),
      "render n synthetic images [n, 784] on the device from a host-made plan (generator v3)");
+  // the support kernels of comm_kernels.hip on caller-owned pointers (tests)
+  m.def("scale_copy", [](uintptr_t dst, uintptr_t src, int64_t n, float s, uintptr_t stream) {
+    launch_scale_copy(P<float>(dst), P<const float>(src), n, s, S(stream));
+    check_launch();
+  }, py::arg("dst"), py::arg("src"), py::arg("n"), py::arg("s"), py::arg("stream"));
+  m.def("fill", [](uintptr_t ptr, int64_t nbytes, int value, uintptr_t stream) {
+    launch_fill(P<void>(ptr), nbytes, value, S(stream));
+    check_launch();
+  }, py::arg("ptr"), py::arg("nbytes"), py::arg("value"), py::arg("stream"));
+  m.def("gather_rows", [](uintptr_t src_u8, uintptr_t src_labels, uintptr_t idx, int64_t start, int64_t n,
+                          uintptr_t dst_u8, uintptr_t dst_labels, uintptr_t stream) {
+    launch_gather_rows(P<const uint8_t>(src_u8), P<const int32_t>(src_labels), P<const int32_t>(idx), start, n,
+                       P<uint8_t>(dst_u8), P<int32_t>(dst_labels), S(stream));
+    check_launch();
+  }, py::arg("src_u8"), py::arg("src_labels"), py::arg("idx"), py::arg("start"), py::arg("n"), py::arg("dst_u8"),
+     py::arg("dst_labels"), py::arg("stream"));
   m.def("memset_sync", [](uintptr_t ptr, int value, int64_t nbytes) {
     // setup-time buffer initialisation without a torch fill kernel (whose code object would load on
     // first launch inside the reference timer); synchronous

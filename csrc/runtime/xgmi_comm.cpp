@@ -235,27 +235,33 @@ std::string XgmiComm::ordering() const {
                  : "uncached+sc0sc1 (no fence: xgmi_allreduce.hip R1-R4)";
 }
 
-void XgmiComm::allreduce_fc_fused(int channel, hipStream_t stream, const AdadeltaArgs& ada) {
+namespace {
+// the planned grid, optionally shrunk (never widened) by a caller's max_wg
+inline int shrink(int planned, int max_wg) { return max_wg > 0 && max_wg < planned ? max_wg : planned; }
+}  // namespace
+
+void XgmiComm::allreduce_fc_fused(int channel, hipStream_t stream, const AdadeltaArgs& ada, int max_wg) {
   XgmiArgs a = args(channel, OFF_FC1_W, OFF_CONV1_W - OFF_FC1_W);
   a.fuse_ada = 1;
   a.ada_base = OFF_FC1_W;
   a.ada = ada;
-  a.max_wg = grids_.fc_fused;
+  a.max_wg = shrink(grids_.fc_fused, max_wg);
   launch_xgmi_fc_fused(a, stream);
 }
 
 void XgmiComm::conv_reduce_fused(int channel, const ConvBwdArgs& conv, int B, hipStream_t stream,
-                                 const AdadeltaArgs& ada, const XgmiConvPart& part) {
+                                 const AdadeltaArgs& ada, const XgmiConvPart& part, int max_wg) {
   XgmiArgs a = args(channel, OFF_CONV1_W, PARAM_TOTAL - OFF_CONV1_W);
   if (PARAM_TOTAL - OFF_CONV1_W > oneshot_max_) throw std::runtime_error("xgmi: conv bucket exceeds the staging slots");
   a.fuse_ada = 1;
   a.ada_base = OFF_CONV1_W;
   a.ada = ada;
-  a.max_wg = grids_.conv_fused;
+  a.max_wg = shrink(grids_.conv_fused, max_wg);
   launch_xgmi_conv_reduce_fused(a, conv, B, stream, part);
 }
 
-void XgmiComm::allreduce(int channel, int64_t offset, int64_t count, hipStream_t stream, const AdadeltaArgs* ada) {
+void XgmiComm::allreduce(int channel, int64_t offset, int64_t count, hipStream_t stream, const AdadeltaArgs* ada,
+                         int max_wg) {
   XgmiArgs a = args(channel, offset, count);
   if (count == 0) return;
   if (ada) {
@@ -264,10 +270,10 @@ void XgmiComm::allreduce(int channel, int64_t offset, int64_t count, hipStream_t
     a.ada = *ada;
   }
   if (count <= oneshot_max_) {
-    a.max_wg = grids_.oneshot;
+    a.max_wg = shrink(grids_.oneshot, max_wg);
     launch_xgmi_allreduce_oneshot(a, stream);
   } else {
-    a.max_wg = grids_.twoshot;
+    a.max_wg = shrink(grids_.twoshot, max_wg);
     launch_xgmi_allreduce(a, stream);
   }
 }

@@ -43,15 +43,17 @@ class XgmiComm {
   // floats, multiples of 4.  Graph-capturable (no host work beyond the launch).
   // With `ada` (conv bucket of the engine): the kernel also applies the Adadelta step to the reduced
   // elements (flat parameter index = offset + bucket index) - see XgmiArgs::fuse_ada.
+  // max_wg (all three launches; tests): 0 = the planned grid; > 0 shrinks it to min(planned, max_wg) -
+  // never widens it, and the launchers' own lower bounds still apply.  Every rank passes the same value.
   void allreduce(int channel, int64_t offset, int64_t count, hipStream_t stream,
-                 const AdadeltaArgs* ada = nullptr);
+                 const AdadeltaArgs* ada = nullptr, int max_wg = 0);
   // The engine's fc bucket (flat [0, OFF_CONV1_W)) with the fc Adadelta step and the w1 / w1t bf16
   // shadow refresh fused into the gather phase (launch_xgmi_fc_fused).
-  void allreduce_fc_fused(int channel, hipStream_t stream, const AdadeltaArgs& ada);
+  void allreduce_fc_fused(int channel, hipStream_t stream, const AdadeltaArgs& ada, int max_wg = 0);
   // The engine's conv bucket straight from the conv gradient slabs: slab reduce + one-shot
   // all-reduce + Adadelta + conv2 shadows in one launch (launch_xgmi_conv_reduce_fused).
   void conv_reduce_fused(int channel, const ConvBwdArgs& conv, int B, hipStream_t stream, const AdadeltaArgs& ada,
-                         const XgmiConvPart& part = XgmiConvPart{});
+                         const XgmiConvPart& part = XgmiConvPart{}, int max_wg = 0);
   int channels() const { return channels_; }
   // device error code (0 = ok; else the first stage wait that timed out on this rank:
   // kernel id << 24 | stage << 16 | peer << 12 | workgroup); synchronous read
@@ -85,6 +87,10 @@ class XgmiComm {
   int rank() const { return rank_; }
   float* in() const { return in_; }
   float* out() const { return out_; }
+  // this rank's flag blocks [channels][XGMI_FLAG_INTS] and staging slots [channels][2][oneshot_max] (tests)
+  int* flags() const { return flags_; }
+  float* stage() const { return stage_; }
+  int64_t oneshot_max() const { return oneshot_max_; }
   int64_t numel() const { return numel_; }
   int device() const { return device_; }
 

@@ -736,6 +736,57 @@ def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0
                   p(ms.state) if advance_step else 0, region, True, _s(), grid=grid, wt=wt)
 
 
+def xgmi_allreduce(x, channel: int, offset: int, count: int, ms=None, wt: bool = False,
+                   advance_step: bool = False, max_wg: int = 0) -> None:
+    """``x.out[offset, offset + count)`` = the rank-ordered sum of every rank's ``x.in`` range (one-shot up to the
+    communicator's ``oneshot_max`` floats, two-shot above).  With ``ms`` the Adadelta step of flat elements
+    ``[offset, offset + count)`` is fused on the reduced values (the fp32 step's buckets).  ``max_wg`` > 0 shrinks
+    the planned grid; every rank passes the same value."""
+    x.allreduce(channel, offset, count, _s(), ada=_ada_args(ms, wt, advance_step) if ms is not None else None,
+                max_wg=max_wg)
+
+
+def xgmi_fc_fused(x, channel: int, ms, wt: bool = False, advance_step: bool = False, max_wg: int = 0) -> None:
+    """The fc bucket's all-reduce with the fc Adadelta step and the ``w1`` / ``w1t`` shadows fused.  The kernel does
+    not advance the step counter even with ``advance_step`` (the conv bucket's launch is the end-of-step marker)."""
+    x.allreduce_fc_fused(channel, _s(), _ada_args(ms, wt, advance_step), max_wg=max_wg)
+
+
+def xgmi_conv_reduce_fused(x, channel: int, ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers,
+                           grad_scale: float = 1.0, idx_stride: int = 0, c1red: torch.Tensor | None = None,
+                           lo: int = 0, hi: int = RED_ALL_PARTS, wt: bool = False, advance_step: bool = False,
+                           max_wg: int = 0) -> None:
+    """Reduce parts [lo, hi) of the conv gradient slabs, their all-reduce through the staging slots and the
+    Adadelta step with the conv2 shadows, one launch (operands as ``conv_bwd``'s reduce stage)."""
+    p, w = native.ptr, param_ptrs(ms)
+    x.conv_reduce_fused(channel, p(buf.dyc), p(buf.a1), w.w2d, w.c1w, w.c1b, p(data_u8), p(idx), idx_stride,
+                        p(ms.state), p(buf.c1part), p(buf.w2part), p(ms.grad), grad_scale, buf.B, _s(),
+                        _ada_args(ms, wt, advance_step), c1red=p(c1red), lo=lo, hi=hi, max_wg=max_wg)
+
+
+def scale_copy(dst: torch.Tensor, src: torch.Tensor, n: int, s: float) -> None:
+    """``dst[:n] = src[:n] * float32(s)`` (the DDP bucket copy-in); fp32 views, any 4-byte alignment."""
+    if dst.dtype != torch.float32 or src.dtype != torch.float32 or n < 0 or n > min(dst.numel(), src.numel()):
+        raise ValueError("scale_copy: fp32 tensors of at least n elements")
+    _C().scale_copy(native.ptr(dst), native.ptr(src), n, float(s), _s())
+
+
+def fill_bytes(t: torch.Tensor, nbytes: int, value: int) -> None:
+    """The first ``nbytes`` bytes of the uint8 view ``t`` = ``value`` (the setup buffers' byte fill)."""
+    if t.dtype != torch.uint8 or nbytes < 0 or nbytes > t.numel():
+        raise ValueError("fill_bytes: a uint8 tensor of at least nbytes elements")
+    _C().fill(native.ptr(t), nbytes, value, _s())
+
+
+def gather_rows(src_u8: torch.Tensor, src_labels: torch.Tensor, idx: torch.Tensor, start: int, n: int,
+                dst_u8: torch.Tensor, dst_labels: torch.Tensor) -> None:
+    """Rows [start, start + n) of ``dst_u8`` [., 784] / ``dst_labels`` = the source rows ``idx[start + i]``."""
+    if start < 0 or n < 0 or start + n > min(idx.numel(), dst_u8.shape[0], dst_labels.numel()):
+        raise ValueError("gather_rows: rows out of range")
+    p = native.ptr
+    _C().gather_rows(p(src_u8), p(src_labels), p(idx), start, n, p(dst_u8), p(dst_labels), _s())
+
+
 def train_step(ms, data_u8, labels, idx, buf: StepBuffers, idx_stride: int = 0, grad_scale: float = 1.0,
                loss_log: torch.Tensor | None = None, update: bool = True) -> None:
     """One full fused training step (no DDP): fwd, loss, bwd, optional Adadelta."""

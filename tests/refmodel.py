@@ -1612,3 +1612,397 @@ def f32_run_chain(m, stages, hand=False, report=None, repeat=True):
         if report:
             report(st, m.cfg.B, out[st])
     return out
+
+
+# ---------------------------------------------------------------- xGMI collective kernels
+# numpy stand-ins of the four kernels of csrc/kernels/xgmi_allreduce.hip that walk the kernels' own index sets
+# (shards, workgroup strides, fc units, virtual reduce blocks and LDS slots) over W ranks' buffers, the launchers'
+# grid arithmetic, and the comparators shared by tests/test_xgmi_oracle_cpu.py and tests/test_gpu_xgmi_stages.py.
+# The optimizer state is that of ONE observed rank (it is rank-local); the buffers a peer reads are all W ranks'.
+XG_MAX_WG, XG_UNITS, XG_TILES, XG_TAIL_F4, XG_VB_MAX = 512, 577, 576, 368, 8
+XG_FC_N, XG_CONV_N = OFF_CONV, PARAM_TOTAL - OFF_CONV
+XG_SENTINEL = -7.25                                   # finite: what the tests put where a launch must not write
+XG_MUTATIONS = ("rank_order_reversed", "peer_skipped", "peer_twice", "own_shard_not_updated", "own_shard_twice",
+                "ragged_last_dropped", "stale_slot", "shadows_from_old_param", "w1t_untransposed", "tail_368_written",
+                "ada_base_off", "conv1_part_touches_conv2", "wd_before_sum")
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def xg_grid(kind, W, nvec=0, fuse=False, planned=XG_MAX_WG, max_wg=0, lo=0, hi=RED_ALL_PARTS):
+    """The launchers' grids (clamp_grid): min(natural, cap) raised to the kernel's floor; cap = the planned grid,
+    shrunk by a positive max_wg."""
+    cap = planned if max_wg <= 0 else min(planned, max_wg)
+
+    def clamp(nat, low):
+        return max(1, min(XG_MAX_WG, max(low, min(nat, cap))))
+    if kind == "twoshot":
+        return clamp(min(XG_MAX_WG, max(1, _cdiv(_cdiv(nvec, W), 128 if fuse else 512))), 1)
+    if kind == "oneshot":
+        return clamp(_cdiv(nvec, 256), _cdiv(nvec, 1024))
+    if kind == "fc":
+        return clamp(min(_cdiv(XG_UNITS, W), XG_MAX_WG), 1)
+    assert kind == "conv"
+    return clamp(hi - lo, _cdiv(hi - lo, XG_VB_MAX))
+
+
+def xg_fc_lo(p, W):
+    return p * XG_UNITS // W
+
+
+def xg_fc_f4(u, h, tail=XG_TAIL_F4):
+    """fcu_f4 for all 256 lanes: the bucket float4 index of a lane's h-th float4 of unit u, -1 past the tail."""
+    tid = np.arange(256)
+    if u < XG_TILES:
+        ot, it = divmod(u, 288)
+        return ((64 * ot + (tid >> 2)) * 9216 + 32 * it + (tid & 3) * 8) // 4 + h
+    q = tid + 256 * h
+    return np.where(q < tail, ADA_OFFS["fc1.bias"] // 4 + q, -1)
+
+
+def xg_fc_own_f4(r, W):
+    """Bucket float4 indices of the units of shard r (what xgmi_fc_fused_kernel stores into rank r's out)."""
+    qs = [xg_fc_f4(u, h) for u in range(xg_fc_lo(r, W), xg_fc_lo(r + 1, W)) for h in (0, 1)]
+    q = np.concatenate(qs) if qs else np.zeros(0, np.int64)
+    return np.unique(q[q >= 0])
+
+
+@functools.lru_cache(maxsize=None)
+def xg_conv_sink(bid):
+    """conv_sink_index of reduce block bid: (lane * 4 + nv, flat element) of every value the block sinks."""
+    slots, els = [], []
+    for lane in range(16 if bid < RED_W2_PARTS else 4):
+        for r in range(4):
+            if bid < RED_W2_PARTS:
+                e = 4 * (bid * 16 + lane)
+                if e < 18432:
+                    ln, tile = (e >> 2) & 63, e >> 8
+                    mt, nt = divmod(tile, 18)
+                    el = ADA_OFFS["conv2.weight"] + (16 * mt + 4 * (ln >> 4) + r) * 288 + (16 * (nt & 1) + (ln & 15)) * 9 + (nt >> 1)
+                elif e < 18432 + 64:
+                    el = ADA_OFFS["conv2.bias"] + (e - 18432) + r
+                else:
+                    continue
+            else:
+                ci, kk = divmod(4 * ((bid - RED_W2_PARTS) * 4 + lane) + r, 10)
+                el = ADA_OFFS["conv1.weight"] + ci * 9 + kk if kk < 9 else ADA_OFFS["conv1.bias"] + ci
+            slots.append(lane * 4 + r)
+            els.append(el)
+    return np.array(slots), np.array(els)
+
+
+def _np_bf16(x):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).view(torch.int16).numpy()
+
+
+class XgWorld:
+    """W ranks' in / out / staging buffers of one communicator channel and rank r's optimizer state.  The visit
+    counters n_* take one increment per call and index: within one call the kernels' index sets are disjoint."""
+
+    def __init__(self, W, r, ins, state=None, lr=1.0, wd=0.0, slot_floats=32768, arith=True):
+        self.W, self.r, self.lr, self.wd, self.arith = W, r, lr, wd, arith
+        self.inp = None
+        if ins is not None:
+            self.set_inputs(ins)
+        n = len(self.inp[0]) if arith else PARAM_TOTAL
+        self.out = [np.full(n, XG_SENTINEL, np.float32) for _ in range(W)] if arith else None
+        self.stage = [np.full((2, slot_floats), XG_SENTINEL, np.float32) for _ in range(W)] if arith else None
+        self.calls, self.step = 0, 0
+        self.n_out = np.zeros(n, np.int32)              # stores into rank r's out, per float
+        self.n_upd = np.zeros(PARAM_TOTAL, np.int32)    # Adadelta steps, per flat element
+        self.n_shadow = {k: np.zeros(v.numel(), np.int32) for k, v in shadow_sources().items()}
+        if state is not None:
+            self.st = {k: state[k].numpy().copy() for k in ADA_STATE}
+            self.sh = {k: state[k].reshape(-1).view(torch.int16).numpy().copy() for k in ADA_SHADOWS}
+
+    def set_inputs(self, ins):
+        self.inp = [t.numpy().astype(np.float32, copy=True) for t in ins]
+
+    def snap(self, grad):
+        d = {k: torch.from_numpy(self.st[k].copy()) for k in ADA_STATE}
+        d.update({k: torch.from_numpy(self.sh[k].copy()).view(torch.bfloat16) for k in ADA_SHADOWS})
+        d["grad"] = grad
+        return d
+
+    # ---- buffer access with the descriptor's bounds: loads past the bucket give 0, stores past it are dropped
+    def _ld(self, buf, off, nvec, j):
+        v = np.zeros((len(j), 4), np.float32)
+        ok = (j >= 0) & (j < nvec)
+        v[ok] = buf[off:off + 4 * nvec].reshape(nvec, 4)[j[ok]]
+        return v
+
+    def _st(self, buf, off, nvec, j, v, count=False):
+        ok = (j >= 0) & (j < nvec)
+        buf[off:off + 4 * nvec].reshape(nvec, 4)[j[ok]] = v[ok]
+        if count:
+            self.n_out[(off + 4 * j[ok][:, None] + np.arange(4)).reshape(-1)] += 1
+
+    def _sum(self, vals, E, mut):
+        """Rank-order fp32 sum of the W ranks' values at flat elements E, one rounding per add."""
+        order = list(range(self.W))
+        if mut == "rank_order_reversed":
+            order.reverse()
+        if mut == "peer_skipped" and self.W > 1:
+            order.pop()
+        if mut == "peer_twice" and self.W > 1:
+            order.append(order[-1])
+        if mut == "wd_before_sum":
+            vals = [v + _f32(self.wd) * self.st["param"][E] for v in vals]
+        with np.errstate(all="ignore"):
+            s = vals[order[0]].astype(np.float32, copy=True)
+            for p in order[1:]:
+                s = s + vals[p]
+        return s
+
+    def _upd(self, E, g, mut):
+        """Ada::step on flat elements E (any shape) with gradients g; returns (new, old) param values."""
+        shape = E.shape
+        E = E.reshape(-1) + (4 if mut == "ada_base_off" else 0)
+        self.n_upd[E] += 1
+        if not self.arith:
+            return None, None
+        st, t = self.st, torch.from_numpy
+        old = st["param"][E]
+        P, S, A = stage_adadelta(t(old), t(np.ascontiguousarray(g.reshape(-1))), t(st["square_avg"][E]), t(st["acc_delta"][E]),
+                                 self.lr, ADA_RHO, ADA_EPS, 0.0 if mut == "wd_before_sum" else self.wd, dtype=F32)
+        st["param"][E], st["square_avg"][E], st["acc_delta"][E] = P.numpy(), S.numpy(), A.numpy()
+        return P.numpy().reshape(shape), old.reshape(shape)
+
+    def _conv2_shadow(self, E, P, old, mut):
+        E = E.reshape(-1) + (4 if mut == "ada_base_off" else 0)
+        rel = E - ADA_OFFS["conv2.weight"]
+        m = (rel >= 0) & (rel < 18432)
+        co, rem = np.divmod(rel[m], 288)
+        ci, t = np.divmod(rem, 9)
+        self.n_shadow["w2f"][(co * 9 + t) * 32 + ci] += 1
+        self.n_shadow["w2d"][(t * 32 + ci) * 64 + co] += 1
+        if self.arith:
+            h = _np_bf16((old if mut == "shadows_from_old_param" else P).reshape(-1)[m])
+            self.sh["w2f"][(co * 9 + t) * 32 + ci] = h
+            self.sh["w2d"][(t * 32 + ci) * 64 + co] = h
+
+    def _elems(self, base, j):
+        return base + 4 * j[:, None] + np.arange(4)
+
+    # ---- xgmi_allreduce_kernel<W>: shard q = float4s [q S4, (q + 1) S4), workgroup stride G * 256
+    def twoshot(self, offset, count, G, fuse=False, mut=None):
+        W, r, nvec = self.W, self.r, count // 4
+        S4, step, k0 = _cdiv(nvec, W), G * 256, np.arange(G * 256)
+        self.calls += 1
+        for q in range(W if self.arith else 0):                       # phase 1 of every rank: its shard of the sum
+            for m in range(_cdiv(S4, step)):                          # i and i2 = i + step: together k0 + m step
+                i = q * S4 + k0 + m * step
+                i = i[i < (q + 1) * S4]
+                s = self._sum([self._ld(self.inp[p], offset, nvec, i) for p in range(W)], self._elems(offset, np.minimum(i, nvec - 1)), mut)
+                self._st(self.out[q], offset, nvec, i, s, count=q == r)
+                if fuse and mut == "own_shard_twice" and q == r:
+                    self._upd(self._elems(offset, i[i < nvec]), s[i < nvec], mut)
+        if not self.arith:
+            for m in range(_cdiv(S4, step)):
+                i = r * S4 + k0 + m * step
+                i = i[(i < (r + 1) * S4) & (i < nvec)]
+                self.n_out[self._elems(offset, i).reshape(-1)] += 1
+        for m in range(_cdiv(S4, step)):                              # phase 2 of rank r: the same index set per WG
+            k = k0 + m * step
+            k = k[k < S4]
+            for p in range(W):
+                j = p * S4 + k
+                if fuse:
+                    j = j[j < (nvec - 1 if mut == "ragged_last_dropped" else nvec)]
+                if p != r:
+                    if self.arith:
+                        self._st(self.out[r], offset, nvec, j, self._ld(self.out[p], offset, nvec, j), count=True)
+                    else:
+                        self.n_out[self._elems(offset, j[j < nvec]).reshape(-1)] += 1
+                if fuse and not (mut == "own_shard_not_updated" and p == r):
+                    E = self._elems(offset, j)
+                    P, old = self._upd(E, self._ld(self.out[p], offset, nvec, j) if self.arith else None, mut)
+                    self._conv2_shadow(E, P, old, mut)
+
+    # ---- xgmi_oneshot_kernel<W>: workgroup b owns float4s b 256 + tid + m G 256, m < 4
+    def oneshot(self, offset, count, G, fuse=False, mut=None):
+        W, r, nvec = self.W, self.r, count // 4
+        step, k0 = G * 256, np.arange(G * 256)
+        self.calls += 1
+        slot = self.calls & 1
+        rslot = (self.calls - 1) & 1 if mut == "stale_slot" else slot
+        ks = [k0 + m * step for m in range(4)]
+        ks = [k[k < nvec] for k in ks]
+        if self.arith:
+            for p in range(W):
+                for k in ks:
+                    self._st(self.stage[p][slot], 0, nvec, k, self._ld(self.inp[p], offset, nvec, k))
+        for k in ks:
+            E = self._elems(offset, k)
+            s = None
+            if self.arith:
+                s = self._sum([self._ld(self.inp[p], offset, nvec, k) if p == r else self._ld(self.stage[p][rslot], 0, nvec, k)
+                               for p in range(W)], E, mut)
+            if fuse:
+                P, old = self._upd(E, s, mut)
+                self._conv2_shadow(E, P, old, mut)
+            elif self.arith:
+                self._st(self.out[r], offset, nvec, k, s, count=True)
+            else:
+                self.n_out[E.reshape(-1)] += 1
+
+    # ---- xgmi_fc_fused_kernel<W>: shard p = units [p 577 / W, (p + 1) 577 / W), workgroup b owns lo_p + b + m G
+    def _fc_unit(self, u, src, mut):
+        """Unit u's reduced gradients from the W buffers ``src`` (one buffer: a gathered sum) and its lanes' elements."""
+        nvec = XG_FC_N // 4
+        q = np.stack([xg_fc_f4(u, h, XG_TAIL_F4 + (1 if mut == "tail_368_written" else 0)) for h in (0, 1)], 1)   # [256, 2]
+        live = q >= 0
+        E = 4 * q[:, :, None] + np.arange(4)                          # [256, 2, 4]
+        g = None
+        if self.arith:
+            vals = [self._ld(b, 0, nvec, np.where(live, q, nvec).reshape(-1)).reshape(256, 2, 4) for b in src]
+            g = self._sum(vals, np.where(live[:, :, None], E, 0), mut) if len(src) > 1 or src[0] is self.inp[0] else vals[0]
+        return q, live, E, g
+
+    def _fc_update(self, u, live, E, g, mut):
+        P, old = self._upd(E[live], g[live] if self.arith else None, mut)
+        if u >= XG_TILES:
+            return
+        ot, it = divmod(u, 288)
+        rows, cols = 64 * ot + np.arange(64), 32 * it + np.arange(32)
+        self.n_shadow["w1"][(rows[:, None] * 9216 + cols).reshape(-1)] += 1
+        self.n_shadow["w1t"][(cols[:, None] * 128 + rows).reshape(-1)] += 1
+        if not self.arith:
+            return
+        v8 = np.zeros((256, 2, 4), np.float32)
+        v8[live] = old if mut == "shadows_from_old_param" else P
+        tile = _np_bf16(v8.reshape(64, 32))                           # lane tid: row tid >> 2, columns (tid & 3) 8 ..+7
+        self.sh["w1"].reshape(128, 9216)[np.ix_(rows, cols)] = tile
+        ts = tile.reshape(32, 64) if mut == "w1t_untransposed" else tile.T     # the LDS transpose
+        self.sh["w1t"].reshape(9216, 128)[np.ix_(cols, rows)] = ts
+
+    def fc_fused(self, G, mut=None):
+        W, r, nvec = self.W, self.r, XG_FC_N // 4
+        self.calls += 1
+        for q in range(W):                                            # phase 1 of every rank (the peers' phase-2 source)
+            if q != r and not self.arith:
+                continue
+            for b in range(G):
+                for u in range(xg_fc_lo(q, W) + b, xg_fc_lo(q + 1, W), G):
+                    f4, live, E, g = self._fc_unit(u, self.inp if self.arith else None, mut)
+                    if self.arith:
+                        self._st(self.out[q], 0, nvec, f4[live], g[live], count=q == r)
+                    elif q == r:
+                        self.n_out[E[live].reshape(-1)] += 1
+                    if q == r:
+                        self._fc_update(u, live, E, g, mut)
+        if W == 1:
+            return
+        M = _cdiv(_cdiv(XG_UNITS, W), G)
+        for b in range(G):
+            for j in range((W - 1) * M):                              # items: peer pp' = j mod (W - 1), m = j / (W - 1)
+                pp, m = j % (W - 1), j // (W - 1)
+                p = pp + (1 if pp >= r else 0)
+                u = xg_fc_lo(p, W) + b + m * G
+                if u >= xg_fc_lo(p + 1, W):
+                    continue
+                _, live, E, g = self._fc_unit(u, [self.out[p]] if self.arith else None, mut)
+                self._fc_update(u, live, E, g, mut)
+
+    # ---- xgmi_conv_reduce_fused_kernel<W>: virtual block lo + b + k G, LDS slot k 64 + lane 4 + nv
+    def conv_fused(self, reds, G, lo=0, hi=RED_ALL_PARTS, mut=None):
+        """reds[p]: rank p's conv_grad_reduce result, indexed by flat element - OFF_CONV."""
+        W, r = self.W, self.r
+        self.calls += 1
+        slot = self.calls & 1
+        rslot = (self.calls - 1) & 1 if mut == "stale_slot" else slot
+        blocks = []
+        for b in range(G):
+            nvb = _cdiv(hi - lo - b, G)
+            assert 0 <= nvb <= XG_VB_MAX, "more virtual blocks than LDS slots"
+            idx = np.full(XG_VB_MAX * 64, -1)
+            for k in range(nvb):
+                sl, el = xg_conv_sink(lo + b + k * G)
+                idx[k * 64 + sl] = el - OFF_CONV
+            if mut == "conv1_part_touches_conv2" and lo >= RED_W2_PARTS and b == 0:
+                idx[XG_VB_MAX * 64 - 1] = ADA_OFFS["conv2.weight"] + 7 - OFF_CONV
+            I = idx[idx >= 0]
+            blocks.append(I)
+            for p in range(W if self.arith else 0):
+                self.stage[p][slot][I] = reds[p][I]
+        for I in blocks:
+            g = None
+            if self.arith:
+                g = self._sum([reds[p][I] if p == r else self.stage[p][rslot][I] for p in range(W)], OFF_CONV + I, mut)
+            P, old = self._upd(OFF_CONV + I, g, mut)
+            self._conv2_shadow(OFF_CONV + I, P, old, mut)
+
+
+# ---- the straight references and the comparators of the collective tests
+def xg_ordered_sum(vals):
+    """fp32 sum of the ranks' tensors in rank order, one rounding per add (what every kernel must give, bitwise)."""
+    with np.errstate(all="ignore"):
+        s = vals[0].numpy().astype(np.float32, copy=True)
+        for v in vals[1:]:
+            s = s + v.numpy()
+    return torch.from_numpy(s)
+
+
+def xg_same(a, b):
+    """Per element: the same bits, or both NaN (the payload of a NaN made by inf - inf is the hardware's)."""
+    return (bits(a) == bits(b)) | (torch.isnan(a) & torch.isnan(b))
+
+
+def xg_check_reduce(got, vals, name="allreduce"):
+    """A reduced range: bit for bit the rank-ordered fp32 sum, and within eps of the float64 sum where that is
+    finite (eps = EPS_MARGIN x the ordered fp32 sum's own deviation).  Returns {"sum": (deviation, eps)}."""
+    want = xg_ordered_sum(vals)
+    bad = ~xg_same(got, want)
+    assert not bad.any(), f"{name}: {int(bad.sum())} of {bad.numel()} sums differ from the rank-ordered fp32 sum; first at {int(bad.nonzero()[0])}"
+    r64 = torch.stack([v.to(F64) for v in vals]).sum(0)
+    fin = torch.isfinite(r64) & torch.isfinite(want)
+    if not fin.any():
+        return {"sum": (0.0, 0.0)}
+    eps = stage_eps(want[fin], r64[fin])
+    return {"sum": (assert_within(got[fin], r64[fin], eps, f"{name} sum"), eps)}
+
+
+def xg_check_update(before, after, own, g32, g64, lr, wd, name="xgmi update"):
+    """One fused update of the flat elements in ``own`` from the reduced gradients (g32: the rank-ordered fp32 sum,
+    g64: the float64 sum, both flat): each state tensor within eps = EPS_MARGIN x max |fp32 emulation on g32 -
+    float64 oracle on g64| where the oracle is finite, and bit for bit the emulation everywhere - which also holds a
+    NaN / inf gradient to exactly its elements.  Returns {tensor: (deviation, eps), "mismatch <tensor>": (count, 0)}."""
+    ops = [before[k][own] for k in ADA_STATE]
+    assert all(torch.isfinite(t).all() for t in ops), f"{name}: non-finite state"
+    r64 = stage_adadelta(ops[0], g64[own], ops[1], ops[2], lr, ADA_RHO, ADA_EPS, wd)
+    emu = stage_adadelta(ops[0], g32[own], ops[1], ops[2], lr, ADA_RHO, ADA_EPS, wd, dtype=F32)
+    stats = {}
+    for i, k in enumerate(ADA_STATE):
+        got = after[k][own]
+        fin = torch.isfinite(r64[i]) & torch.isfinite(emu[i])
+        eps = EPS_MARGIN * float((emu[i][fin].to(F64) - r64[i][fin]).abs().max()) if fin.any() else 0.0
+        stats[k] = (assert_within(got[fin], r64[i][fin], eps, f"{name} {k}"), eps)
+        n = int((~xg_same(got, emu[i])).sum())
+        stats[f"mismatch {k}"] = (float(n), 0.0)
+        assert n == 0, f"{name}: {n} elements of {k} differ from the fp32 emulation on the rank-ordered sum"
+    return stats
+
+
+def xg_bucket(seed, case, q, W, n, edges=(), poison=None, poison_at=()):
+    """Rank q's input values for a bucket of n floats: randn at scales 1e-6 .. 1e3, and at every position of
+    ``edges`` (and the first and last element) a 24-element block of +-1e8 / 1 triples whose fp32 sum depends on the
+    order (placement rotated per element), denormals and +-0.  ``poison`` (NaN or inf) goes to ``poison_at`` on
+    rank W - 1 only.  Every rank can build every rank's bucket."""
+    g = torch.Generator().manual_seed(1000003 * seed + 1009 * case + q)
+    v = torch.randn(n, generator=g) * _log_uniform(n, -6, 3, g)
+    tri = (1e8, 1.0, -1e8)
+    for e in sorted({0, max(0, n - 24), *[min(max(0, x - 12), max(0, n - 24)) for x in edges]}):
+        for i in range(min(24, n - e)):
+            role = (q + i) % max(W, 3)
+            kind = i // 8
+            if kind == 0:
+                v[e + i] = tri[role] if role < 3 else v[e + i]
+            elif kind == 1:
+                v[e + i] = (1 - 2 * ((q + i) & 1)) * 1e-40 * (q + 1)
+            else:
+                v[e + i] = -0.0 if (q + i) % 3 == 0 else 0.0
+    if poison is not None and q == W - 1:
+        v[torch.as_tensor(list(poison_at), dtype=torch.long)] = poison
+    return v
