@@ -28,6 +28,23 @@ void tl_dump_xgmi(std::vector<uint64_t>&);
 #endif
 using namespace mnist;
 
+void mnist::preload_all_kernels() {
+  preload_trunk();
+  preload_fc_head();
+  preload_conv_bwd();
+  preload_adadelta();
+  preload_comm();
+  preload_xgmi();
+  preload_f32();
+  preload_input_grad();
+  preload_input_grad_step();
+  preload_attack_step();
+  preload_adv_train();
+  preload_smooth();
+  preload_attr();
+  preload_deepfool();
+}
+
 namespace {
 template <typename T>
 T* P(uintptr_t x) { return reinterpret_cast<T*>(x); }
@@ -80,33 +97,32 @@ py::capsule dlpack_f32(float* data, int64_t n, int device, std::shared_ptr<void>
   });
 }
 
+// the device pointer under key k, null where the key is absent
+uintptr_t dict_ptr(const py::dict& d, const char* k) { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; }
+
 EngineBuffers buffers_from_dict(const py::dict& d) {
   EngineBuffers b;
-  auto get = [&](const char* k) -> uintptr_t {
-    if (!d.contains(k)) return 0;
-    return d[k].cast<uintptr_t>();
-  };
-  b.param = P<float>(get("param"));
-  b.grad = P<float>(get("grad"));
-  b.square_avg = P<float>(get("square_avg"));
-  b.acc_delta = P<float>(get("acc_delta"));
-  b.lr = P<float>(get("lr"));
-  b.w2f = P<uint16_t>(get("w2f"));
-  b.w2d = P<uint16_t>(get("w2d"));
-  b.w1 = P<uint16_t>(get("w1"));
-  b.w1t = P<uint16_t>(get("w1t"));
-  b.state = P<StepState>(get("state"));
-  b.loss_log = P<float>(get("loss_log"));
-  b.train_u8 = P<const uint8_t>(get("train_u8"));
-  b.train_labels = P<const int32_t>(get("train_labels"));
-  b.train_idx = P<const int32_t>(get("train_idx"));
-  b.epoch_u8 = P<uint8_t>(get("epoch_u8"));
-  b.epoch_labels = P<int32_t>(get("epoch_labels"));
-  b.test_u8 = P<const uint8_t>(get("test_u8"));
-  b.test_labels = P<const int32_t>(get("test_labels"));
-  b.test_idx = P<const int32_t>(get("test_idx"));
-  b.test_loss_rows = P<float>(get("test_loss_rows"));
-  b.test_correct = P<int32_t>(get("test_correct"));
+  b.param = P<float>(dict_ptr(d, "param"));
+  b.grad = P<float>(dict_ptr(d, "grad"));
+  b.square_avg = P<float>(dict_ptr(d, "square_avg"));
+  b.acc_delta = P<float>(dict_ptr(d, "acc_delta"));
+  b.lr = P<float>(dict_ptr(d, "lr"));
+  b.w2f = P<uint16_t>(dict_ptr(d, "w2f"));
+  b.w2d = P<uint16_t>(dict_ptr(d, "w2d"));
+  b.w1 = P<uint16_t>(dict_ptr(d, "w1"));
+  b.w1t = P<uint16_t>(dict_ptr(d, "w1t"));
+  b.state = P<StepState>(dict_ptr(d, "state"));
+  b.loss_log = P<float>(dict_ptr(d, "loss_log"));
+  b.train_u8 = P<const uint8_t>(dict_ptr(d, "train_u8"));
+  b.train_labels = P<const int32_t>(dict_ptr(d, "train_labels"));
+  b.train_idx = P<const int32_t>(dict_ptr(d, "train_idx"));
+  b.epoch_u8 = P<uint8_t>(dict_ptr(d, "epoch_u8"));
+  b.epoch_labels = P<int32_t>(dict_ptr(d, "epoch_labels"));
+  b.test_u8 = P<const uint8_t>(dict_ptr(d, "test_u8"));
+  b.test_labels = P<const int32_t>(dict_ptr(d, "test_labels"));
+  b.test_idx = P<const int32_t>(dict_ptr(d, "test_idx"));
+  b.test_loss_rows = P<float>(dict_ptr(d, "test_loss_rows"));
+  b.test_correct = P<int32_t>(dict_ptr(d, "test_correct"));
   if (!b.param || !b.grad || !b.square_avg || !b.acc_delta || !b.lr || !b.w2f || !b.w2d || !b.w1 ||
       !b.w1t || !b.state)
     throw std::runtime_error("engine buffers: missing model/optimizer pointer");
@@ -117,21 +133,20 @@ EngineBuffers buffers_from_dict(const py::dict& d) {
 // pointers and signal_start stay null: the completion holds wait on another stream's counters and
 // belong to the engine.
 AdadeltaArgs ada_from_dict(const py::dict& d) {
-  auto ptr = [&](const char* k) -> uintptr_t { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; };
   AdadeltaArgs a{};
-  a.param = P<float>(ptr("param"));
-  a.grad = P<const float>(ptr("grad"));
-  a.square_avg = P<float>(ptr("square_avg"));
-  a.acc_delta = P<float>(ptr("acc_delta"));
-  a.lr = P<const float>(ptr("lr"));
+  a.param = P<float>(dict_ptr(d, "param"));
+  a.grad = P<const float>(dict_ptr(d, "grad"));
+  a.square_avg = P<float>(dict_ptr(d, "square_avg"));
+  a.acc_delta = P<float>(dict_ptr(d, "acc_delta"));
+  a.lr = P<const float>(dict_ptr(d, "lr"));
   a.rho = d["rho"].cast<float>();
   a.eps = d["eps"].cast<float>();
   a.weight_decay = d["weight_decay"].cast<float>();
-  a.w2f = P<uint16_t>(ptr("w2f"));
-  a.w2d = P<uint16_t>(ptr("w2d"));
-  a.w1 = P<uint16_t>(ptr("w1"));
-  a.w1t = P<uint16_t>(ptr("w1t"));
-  a.state_inc = P<StepState>(ptr("state_inc"));
+  a.w2f = P<uint16_t>(dict_ptr(d, "w2f"));
+  a.w2d = P<uint16_t>(dict_ptr(d, "w2d"));
+  a.w1 = P<uint16_t>(dict_ptr(d, "w1"));
+  a.w1t = P<uint16_t>(dict_ptr(d, "w1t"));
+  a.state_inc = P<StepState>(dict_ptr(d, "state_inc"));
   a.wt = d.contains("wt") && d["wt"].cast<bool>() ? 1 : 0;
   if (!a.param || !a.grad || !a.square_avg || !a.acc_delta || !a.lr || !a.w2f || !a.w2d || !a.w1 || !a.w1t)
     throw std::runtime_error("adadelta arguments: missing model/optimizer pointer");
@@ -153,33 +168,32 @@ ConvBwdArgs conv_args(uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c,
 
 // F32Step of a stand-alone fp32 launch from caller-owned device pointers (null where a key is absent)
 F32Step f32_from_dict(const py::dict& d, int64_t idx_step_stride, float inv_batch) {
-  auto ptr = [&](const char* k) -> uintptr_t { return d.contains(k) ? d[k].cast<uintptr_t>() : 0; };
   F32Step a{};
-  a.data_u8 = P<const uint8_t>(ptr("data_u8"));
-  a.idx = P<const int32_t>(ptr("idx"));
+  a.data_u8 = P<const uint8_t>(dict_ptr(d, "data_u8"));
+  a.idx = P<const int32_t>(dict_ptr(d, "idx"));
   a.idx_step_stride = idx_step_stride;
-  a.labels = P<const int32_t>(ptr("labels"));
-  a.state = P<const StepState>(ptr("state"));
-  a.param = P<const float>(ptr("param"));
-  a.grad = P<float>(ptr("grad"));
-  a.loss_log = P<float>(ptr("loss_log"));
+  a.labels = P<const int32_t>(dict_ptr(d, "labels"));
+  a.state = P<const StepState>(dict_ptr(d, "state"));
+  a.param = P<const float>(dict_ptr(d, "param"));
+  a.grad = P<float>(dict_ptr(d, "grad"));
+  a.loss_log = P<float>(dict_ptr(d, "loss_log"));
   a.inv_batch = inv_batch;
-  a.w2fwd = P<float>(ptr("w2fwd"));
-  a.w2bwd = P<float>(ptr("w2bwd"));
-  a.w1p = P<float>(ptr("w1p"));
-  a.a1 = P<float>(ptr("a1"));
-  a.dx1 = P<float>(ptr("dx1"));
-  a.y2 = P<float>(ptr("y2"));
-  a.p = P<float>(ptr("p"));
-  a.pm = P<uint8_t>(ptr("pm"));
-  a.z1part = P<float>(ptr("z1part"));
-  a.h = P<float>(ptr("h"));
-  a.dz1 = P<float>(ptr("dz1"));
-  a.dl = P<float>(ptr("dl"));
-  a.loss_rows = P<float>(ptr("loss_rows"));
-  a.correct = P<int32_t>(ptr("correct"));
-  a.c2part = P<float>(ptr("c2part"));
-  a.c1part = P<float>(ptr("c1part"));
+  a.w2fwd = P<float>(dict_ptr(d, "w2fwd"));
+  a.w2bwd = P<float>(dict_ptr(d, "w2bwd"));
+  a.w1p = P<float>(dict_ptr(d, "w1p"));
+  a.a1 = P<float>(dict_ptr(d, "a1"));
+  a.dx1 = P<float>(dict_ptr(d, "dx1"));
+  a.y2 = P<float>(dict_ptr(d, "y2"));
+  a.p = P<float>(dict_ptr(d, "p"));
+  a.pm = P<uint8_t>(dict_ptr(d, "pm"));
+  a.z1part = P<float>(dict_ptr(d, "z1part"));
+  a.h = P<float>(dict_ptr(d, "h"));
+  a.dz1 = P<float>(dict_ptr(d, "dz1"));
+  a.dl = P<float>(dict_ptr(d, "dl"));
+  a.loss_rows = P<float>(dict_ptr(d, "loss_rows"));
+  a.correct = P<int32_t>(dict_ptr(d, "correct"));
+  a.c2part = P<float>(dict_ptr(d, "c2part"));
+  a.c1part = P<float>(dict_ptr(d, "c1part"));
   return a;
 }
 }  // namespace
@@ -753,20 +767,7 @@ PYBIND11_MODULE(_C, m) {
     if (hipSetDevice(device) != hipSuccess) throw std::runtime_error("hip_prewarm: hipSetDevice failed");
     (void)hipFree(nullptr);
     const auto t1 = clk::now();
-    preload_trunk();
-    preload_fc_head();
-    preload_conv_bwd();
-    preload_adadelta();
-    preload_comm();
-    preload_xgmi();
-    preload_f32();
-    preload_input_grad();
-    preload_input_grad_step();
-    preload_attack_step();
-    preload_adv_train();
-    preload_smooth();
-    preload_attr();
-    preload_deepfool();
+    preload_all_kernels();
     const auto t2 = clk::now();
     // the runtime's own first-use costs the setup would otherwise pay on the main thread: the blit
     // kernels behind hipMemset and the staging path of pageable host copies (measured on the box:
@@ -878,22 +879,8 @@ PYBIND11_MODULE(_C, m) {
       if (hipStreamSynchronize(nullptr) != hipSuccess) throw std::runtime_error("memset_sync: fill failed");
     }
   }, py::call_guard<py::gil_scoped_release>());
-  m.def("preload_code_objects", []() {
-    preload_trunk();
-    preload_fc_head();
-    preload_conv_bwd();
-    preload_adadelta();
-    preload_comm();
-    preload_xgmi();
-    preload_f32();
-    preload_input_grad();
-    preload_input_grad_step();
-    preload_attack_step();
-    preload_adv_train();
-    preload_smooth();
-    preload_attr();
-    preload_deepfool();
-  }, py::call_guard<py::gil_scoped_release>(), "load every kernel translation unit's code object on the current device");
+  m.def("preload_code_objects", &preload_all_kernels, py::call_guard<py::gil_scoped_release>(),
+        "load every kernel translation unit's code object on the current device");
   m.def("roctx_push", [](const std::string& s) { roctx_push(s.c_str()); });
   m.def("roctx_pop", []() { roctx_pop(); });
 }

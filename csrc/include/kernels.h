@@ -473,6 +473,7 @@ void preload_adv_train();
 void preload_smooth();
 void preload_attr();
 void preload_deepfool();
+void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

@@ -28,29 +28,21 @@
 // threads of a workgroup leave).  16-byte stores, no atomics, no LDS; the grid is exactly B workgroups, so
 // nothing past row B - 1 is written, and a thread's values depend only on (seed, step, b, v): the same
 // bits on any grid, stream and launch.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
-
-#include <stdexcept>
+#include "../runtime/host_logic.h"
+#include "row_ops.h"
 
 namespace mnist {
 
 namespace {
-constexpr int AI_THREADS = 256;
-constexpr int AI_VECS = IMG * IMG / 4;                   // 196 float4 per image
-static_assert(AI_VECS * 4 == IMG * IMG && AI_VECS <= AI_THREADS, "one float4 per thread");
-
 __device__ __forceinline__ float ai_start(float x0, uint32_t w, float eps, float lo, float hi) {
 #pragma clang fp contract(off)
   const float u = (float)(w >> 8) * 0x1p-24f;            // [0, 1), exact
-  float t = x0 + (2.0f * u - 1.0f) * eps;
-  t = t < lo ? lo : t;
-  return t > hi ? hi : t;
+  return clamp_nan_passes(x0 + (2.0f * u - 1.0f) * eps, lo, hi);
 }
 }  // namespace
 
 template <bool IDX>
-__global__ __launch_bounds__(AI_THREADS) void adv_init_kernel(AdvInitArgs a) {
+__global__ __launch_bounds__(ROW_THREADS) void adv_init_kernel(AdvInitArgs a) {
   RW_ENTRY();
   const int b = blockIdx.x, v = threadIdx.x;
   const int step = a.state->step;
@@ -59,23 +51,18 @@ __global__ __launch_bounds__(AI_THREADS) void adv_init_kernel(AdvInitArgs a) {
   int64_t src = row;
   if constexpr (IDX) src = a.idx[row];
   if (v == 0) a.labels_out[b] = a.labels[src];
-  if (v >= AI_VECS) return;
-  const uint32_t px = reinterpret_cast<const uint32_t*>(a.data_u8 + src * (IMG * IMG))[v];   // rows are 784 B
-  float4 c;
-  c.x = normalize_u8_alu(px & 0xffu);
-  c.y = normalize_u8_alu((px >> 8) & 0xffu);
-  c.z = normalize_u8_alu((px >> 16) & 0xffu);
-  c.w = normalize_u8_alu(px >> 24);
+  if (v >= ROW_VECS) return;
+  const float4 c = row_load_u8(a.data_u8, src, v);
   float4 s = c;
   if (a.random_start) {
-    const u32x4 w = philox4x32((uint32_t)b * AI_VECS + v, ADV_PHILOX_DOMAIN, (uint32_t)step, 0u, (uint32_t)seed,
+    const u32x4 w = philox4x32((uint32_t)b * ROW_VECS + v, ADV_PHILOX_DOMAIN, (uint32_t)step, 0u, (uint32_t)seed,
                                (uint32_t)(seed >> 32));
     s.x = ai_start(c.x, w[0], a.eps, a.lo, a.hi);
     s.y = ai_start(c.y, w[1], a.eps, a.lo, a.hi);
     s.z = ai_start(c.z, w[2], a.eps, a.lo, a.hi);
     s.w = ai_start(c.w, w[3], a.eps, a.lo, a.hi);
   }
-  const int64_t v4 = (int64_t)b * AI_VECS + v;
+  const int64_t v4 = (int64_t)b * ROW_VECS + v;
   reinterpret_cast<float4*>(a.x0)[v4] = c;
   reinterpret_cast<float4*>(a.x)[v4] = s;
 }
@@ -84,17 +71,15 @@ void launch_adv_init(const AdvInitArgs& a, int B, hipStream_t s) {
   if (B < 1 || B > ADV_INIT_MAX_B) throw std::runtime_error("adv_init: batch size out of range");
   if (!a.data_u8 || !a.labels || !a.state || !a.x0 || !a.x || !a.labels_out)
     throw std::runtime_error("adv_init: null argument");
-  if ((reinterpret_cast<uintptr_t>(a.x0) | reinterpret_cast<uintptr_t>(a.x)) & 15)
-    throw std::runtime_error("adv_init: x0 and x must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(a.data_u8) & 3)
-    throw std::runtime_error("adv_init: the image rows must be 4-byte aligned");
+  if (misaligned(15, a.x0, a.x)) throw std::runtime_error("adv_init: x0 and x must be 16-byte aligned");
+  if (misaligned(3, a.data_u8)) throw std::runtime_error("adv_init: the image rows must be 4-byte aligned");
   if (a.x0 == a.x) throw std::runtime_error("adv_init: x must not be x0");
   if (a.random_start && !(a.eps >= 0.0f && a.lo <= a.hi))
     throw std::runtime_error("adv_init: need eps >= 0 and lo <= hi");
   if (a.idx)
-    hipLaunchKernelGGL(adv_init_kernel<true>, dim3(B), dim3(AI_THREADS), 0, s, a);
+    hipLaunchKernelGGL(adv_init_kernel<true>, dim3(B), dim3(ROW_THREADS), 0, s, a);
   else
-    hipLaunchKernelGGL(adv_init_kernel<false>, dim3(B), dim3(AI_THREADS), 0, s, a);
+    hipLaunchKernelGGL(adv_init_kernel<false>, dim3(B), dim3(ROW_THREADS), 0, s, a);
 }
 
 void preload_adv_train() {

@@ -23,49 +23,24 @@
 // atomics, nothing depends on the grid, the stream or the launch count: the same operands give the same
 // bits.  x_next may alias x: a thread loads its x, x0 and dx elements before it stores, and it is the only
 // one that touches them.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
-
-#include <stdexcept>
+#include "../runtime/host_logic.h"
+#include "row_ops.h"
 
 namespace mnist {
 
-namespace {
-constexpr int PL_THREADS = 256, PL_WAVES = PL_THREADS / 64;
-constexpr int PL_VECS = IMG * IMG / 4;                   // 196 float4 per image
-static_assert(PL_VECS * 4 == IMG * IMG && PL_VECS <= PL_THREADS && PL_WAVES == 4, "one float4 per thread");
-
-// sum over the workgroup; `part` is this sum's own PL_WAVES words (one barrier, no reuse)
-__device__ __forceinline__ float pl_block_sum(float v, float* part, int wave, int lane) {
+__global__ __launch_bounds__(ROW_THREADS) void pgd_l2_step_kernel(PgdL2StepArgs a) {
 #pragma clang fp contract(off)
-  v = wave_sum(v);
-  if (lane == 0) part[wave] = v;
-  lds_barrier();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-__device__ __forceinline__ float pl_sq4(const float4& v) {
-#pragma clang fp contract(off)
-  return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-}
-__device__ __forceinline__ float pl_clamp(float t, float lo, float hi) {   // a NaN passes
-  t = t < lo ? lo : t;
-  return t > hi ? hi : t;
-}
-}  // namespace
-
-__global__ __launch_bounds__(PL_THREADS) void pgd_l2_step_kernel(PgdL2StepArgs a) {
-#pragma clang fp contract(off)
-  __shared__ float part[2][PL_WAVES];
+  __shared__ float part[2][ROW_WAVES];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const bool own = tid < PL_VECS;
-  const int64_t v4 = (int64_t)blockIdx.x * PL_VECS + (own ? tid : 0);   // (idle threads: a valid address)
+  const bool own = tid < ROW_VECS;
+  const int64_t v4 = (int64_t)blockIdx.x * ROW_VECS + (own ? tid : 0);   // (idle threads: a valid address)
   RW_ENTRY();
   float4 g = reinterpret_cast<const float4*>(a.dx)[v4];
   const float4 x = reinterpret_cast<const float4*>(a.x)[v4];
   const float4 c = reinterpret_cast<const float4*>(a.x0)[v4];
   if (!own) g = float4{0.0f, 0.0f, 0.0f, 0.0f};
 
-  const float n = sqrtf(pl_block_sum(pl_sq4(g), part[0], wave, lane));
+  const float n = sqrtf(row_block_sum(row_sq4(g), part[0], wave, lane));
   const float r = a.alpha / (n < PGD_L2_TINY ? PGD_L2_TINY : n);
   float4 d;
   d.x = (x.x + r * g.x) - c.x;
@@ -74,15 +49,15 @@ __global__ __launch_bounds__(PL_THREADS) void pgd_l2_step_kernel(PgdL2StepArgs a
   d.w = (x.w + r * g.w) - c.w;
   if (!own) d = float4{0.0f, 0.0f, 0.0f, 0.0f};
 
-  const float m = sqrtf(pl_block_sum(pl_sq4(d), part[1], wave, lane));
+  const float m = sqrtf(row_block_sum(row_sq4(d), part[1], wave, lane));
   float sc = a.eps / (m < PGD_L2_TINY ? PGD_L2_TINY : m);
   sc = sc > 1.0f ? 1.0f : sc;
   if (own) {
     float4 o;
-    o.x = pl_clamp(c.x + d.x * sc, a.lo, a.hi);
-    o.y = pl_clamp(c.y + d.y * sc, a.lo, a.hi);
-    o.z = pl_clamp(c.z + d.z * sc, a.lo, a.hi);
-    o.w = pl_clamp(c.w + d.w * sc, a.lo, a.hi);
+    o.x = clamp_nan_passes(c.x + d.x * sc, a.lo, a.hi);
+    o.y = clamp_nan_passes(c.y + d.y * sc, a.lo, a.hi);
+    o.z = clamp_nan_passes(c.z + d.z * sc, a.lo, a.hi);
+    o.w = clamp_nan_passes(c.w + d.w * sc, a.lo, a.hi);
     reinterpret_cast<float4*>(a.x_next)[v4] = o;
   }
 }
@@ -90,11 +65,10 @@ __global__ __launch_bounds__(PL_THREADS) void pgd_l2_step_kernel(PgdL2StepArgs a
 void launch_pgd_l2_step(const PgdL2StepArgs& a, int B, hipStream_t s) {
   if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("pgd_l2_step: batch size out of range");
   if (!a.dx || !a.x || !a.x0 || !a.x_next) throw std::runtime_error("pgd_l2_step: null argument");
-  if ((reinterpret_cast<uintptr_t>(a.dx) | reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.x0) |
-       reinterpret_cast<uintptr_t>(a.x_next)) & 15)
+  if (misaligned(15, a.dx, a.x, a.x0, a.x_next))
     throw std::runtime_error("pgd_l2_step: the four arrays must be 16-byte aligned");
   if (!(a.eps >= 0.0f)) throw std::runtime_error("pgd_l2_step: eps must be >= 0");
-  hipLaunchKernelGGL(pgd_l2_step_kernel, dim3(B), dim3(PL_THREADS), 0, s, a);
+  hipLaunchKernelGGL(pgd_l2_step_kernel, dim3(B), dim3(ROW_THREADS), 0, s, a);
 }
 
 void preload_attack_step() {

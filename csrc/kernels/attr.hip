@@ -30,38 +30,18 @@
 // (the rows of one column are 3136 B apart: AR_AHEAD independent 16-byte loads in flight per thread).  An element
 // of the result depends on that element of the image's rows alone: a NaN reaches only its own element.  No LDS,
 // no atomics, no cross-lane operation.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
-
-#include <stdexcept>
-#include <string>
+#include "../runtime/host_logic.h"
+#include "row_ops.h"
 
 namespace mnist {
 
 namespace {
-constexpr int AP_THREADS = 256;
-constexpr int AT_VECS = IMG * IMG / 4;                   // 196 float4 per image
-static_assert(AT_VECS * 4 == IMG * IMG && AT_VECS <= AP_THREADS, "one float4 per thread");
 constexpr int AR_THREADS = 64;
 constexpr int AR_AHEAD = 8;                              // rows whose loads are in flight before the adds
 
-// the float4 v of image i: the normalised image, and its baseline
-template <bool U8>
-__device__ __forceinline__ float4 at_image(const uint8_t* x_u8, const float* x_f32, int64_t i, int v) {
-  float4 c;
-  if constexpr (U8) {
-    const uint32_t px = reinterpret_cast<const uint32_t*>(x_u8 + i * (IMG * IMG))[v];     // rows are 784 B
-    c.x = normalize_u8_alu(px & 0xffu);
-    c.y = normalize_u8_alu((px >> 8) & 0xffu);
-    c.z = normalize_u8_alu((px >> 16) & 0xffu);
-    c.w = normalize_u8_alu(px >> 24);
-  } else {
-    c = reinterpret_cast<const float4*>(x_f32)[i * AT_VECS + v];
-  }
-  return c;
-}
+// the float4 v of image i's baseline (the image itself: row_load)
 __device__ __forceinline__ float4 at_base(const float* base, float base_value, int64_t i, int v) {
-  if (base) return reinterpret_cast<const float4*>(base)[i * AT_VECS + v];
+  if (base) return reinterpret_cast<const float4*>(base)[i * ROW_VECS + v];
   return make_float4(base_value, base_value, base_value, base_value);
 }
 __device__ __forceinline__ float at_point(float x, float b, float alpha) {
@@ -80,10 +60,10 @@ __device__ __forceinline__ float at_finish(float acc, float scale, float x, floa
 }  // namespace
 
 template <bool U8>
-__global__ __launch_bounds__(AP_THREADS) void attr_path_kernel(AttrPathArgs a) {
+__global__ __launch_bounds__(ROW_THREADS) void attr_path_kernel(AttrPathArgs a) {
   RW_ENTRY();
   const int v = threadIdx.x;
-  if (v >= AT_VECS) return;
+  if (v >= ROW_VECS) return;
   const int64_t r = blockIdx.x;
   const int64_t i = (uint32_t)blockIdx.x / (uint32_t)a.ns;     // rows <= SMOOTH_MAX_ROWS: 32-bit division
   const int s = (int)(r - i * a.ns);
@@ -92,14 +72,14 @@ __global__ __launch_bounds__(AP_THREADS) void attr_path_kernel(AttrPathArgs a) {
 #pragma clang fp contract(off)
     alpha = ((float)(a.sample_base + s) + 0.5f) / (float)a.n_total;
   }
-  const float4 x = at_image<U8>(a.x_u8, a.x_f32, i, v);
+  const float4 x = row_load<U8>(a.x_u8, a.x_f32, i, v);
   const float4 b = at_base(a.base, a.base_value, i, v);
   float4 o;
   o.x = at_point(x.x, b.x, alpha);
   o.y = at_point(x.y, b.y, alpha);
   o.z = at_point(x.z, b.z, alpha);
   o.w = at_point(x.w, b.w, alpha);
-  reinterpret_cast<float4*>(a.out)[r * AT_VECS + v] = o;
+  reinterpret_cast<float4*>(a.out)[r * ROW_VECS + v] = o;
 }
 
 // SRC 0: no image is read (finish none / scale); 1: uint8 rows; 2: fp32 rows (ATTR_FINISH_PATH)
@@ -107,22 +87,22 @@ template <int SRC>
 __global__ __launch_bounds__(AR_THREADS) void attr_reduce_kernel(AttrReduceArgs a, int M) {
   RW_ENTRY();
   const int64_t item = (int64_t)blockIdx.x * AR_THREADS + threadIdx.x;
-  if (item >= (int64_t)M * AT_VECS) return;
-  const int64_t i = (uint32_t)item / (uint32_t)AT_VECS;        // items <= 196 * SMOOTH_MAX_ROWS < 2^32
-  const int v = (int)(item - i * AT_VECS);
+  if (item >= (int64_t)M * ROW_VECS) return;
+  const int64_t i = (uint32_t)item / (uint32_t)ROW_VECS;        // items <= 196 * SMOOTH_MAX_ROWS < 2^32
+  const int v = (int)(item - i * ROW_VECS);
   float4* accp = reinterpret_cast<float4*>(a.acc) + item;
   float4 t = a.accumulate ? *accp : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float4* row = reinterpret_cast<const float4*>(a.dx) + i * a.ns * AT_VECS + v;
+  const float4* row = reinterpret_cast<const float4*>(a.dx) + i * a.ns * ROW_VECS + v;
   int s = 0;
   for (; s + AR_AHEAD <= a.ns; s += AR_AHEAD) {
     float4 g[AR_AHEAD];
 #pragma unroll
-    for (int k = 0; k < AR_AHEAD; ++k) g[k] = row[(int64_t)(s + k) * AT_VECS];
+    for (int k = 0; k < AR_AHEAD; ++k) g[k] = row[(int64_t)(s + k) * ROW_VECS];
 #pragma unroll
     for (int k = 0; k < AR_AHEAD; ++k) { t.x += g[k].x; t.y += g[k].y; t.z += g[k].z; t.w += g[k].w; }
   }
   for (; s < a.ns; ++s) {
-    const float4 g = row[(int64_t)s * AT_VECS];
+    const float4 g = row[(int64_t)s * ROW_VECS];
     t.x += g.x; t.y += g.y; t.z += g.z; t.w += g.w;
   }
   if (a.finish == ATTR_FINISH_NONE) {
@@ -131,7 +111,7 @@ __global__ __launch_bounds__(AR_THREADS) void attr_reduce_kernel(AttrReduceArgs 
   }
   float4 x = t, b = t;                                         // (unused by ATTR_FINISH_SCALE)
   if constexpr (SRC != 0) {
-    x = at_image<SRC == 1>(a.x_u8, a.x_f32, i, v);
+    x = row_load<SRC == 1>(a.x_u8, a.x_f32, i, v);
     b = at_base(a.base, a.base_value, i, v);
   }
   constexpr bool path = SRC != 0;
@@ -143,29 +123,18 @@ __global__ __launch_bounds__(AR_THREADS) void attr_reduce_kernel(AttrReduceArgs 
   reinterpret_cast<float4*>(a.out)[item] = o;
 }
 
-namespace {
-void check_image(const char* who, const uint8_t* x_u8, const float* x_f32, const float* base) {
-  if ((x_u8 != nullptr) == (x_f32 != nullptr))
-    throw std::runtime_error(std::string(who) + ": null argument (exactly one of the uint8 and the fp32 rows)");
-  if (x_u8 ? (reinterpret_cast<uintptr_t>(x_u8) & 3) : (reinterpret_cast<uintptr_t>(x_f32) & 15))
-    throw std::runtime_error(std::string(who) + ": the source rows must be 16-byte aligned (uint8 rows: 4-byte)");
-  if (reinterpret_cast<uintptr_t>(base) & 15)
-    throw std::runtime_error(std::string(who) + ": the baseline rows must be 16-byte aligned");
-}
-}  // namespace
-
 void launch_attr_path(const AttrPathArgs& a, int M, hipStream_t s) {
   if (!a.out) throw std::runtime_error("attr_path: null argument");
   if (M < 1 || a.ns < 1 || (int64_t)M * a.ns > SMOOTH_MAX_ROWS) throw std::runtime_error("attr_path: M * ns out of range");
-  check_image("attr_path", a.x_u8, a.x_f32, a.base);
-  if (reinterpret_cast<uintptr_t>(a.out) & 15) throw std::runtime_error("attr_path: out must be 16-byte aligned");
+  check_row_source("attr_path", a.x_u8, a.x_f32, a.base);
+  if (misaligned(15, a.out)) throw std::runtime_error("attr_path: out must be 16-byte aligned");
   if (a.n_total < 1 || a.n_total > ATTR_MAX_STEPS || a.sample_base < 0 || (int64_t)a.sample_base + a.ns > a.n_total)
     throw std::runtime_error("attr_path: need 0 <= sample_base, sample_base + ns <= n_total <= ATTR_MAX_STEPS");
   const unsigned rows = (unsigned)((int64_t)M * a.ns);
   if (a.x_u8)
-    hipLaunchKernelGGL(attr_path_kernel<true>, dim3(rows), dim3(AP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(attr_path_kernel<true>, dim3(rows), dim3(ROW_THREADS), 0, s, a);
   else
-    hipLaunchKernelGGL(attr_path_kernel<false>, dim3(rows), dim3(AP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(attr_path_kernel<false>, dim3(rows), dim3(ROW_THREADS), 0, s, a);
 }
 
 void launch_attr_reduce(const AttrReduceArgs& a, int M, hipStream_t s) {
@@ -174,11 +143,11 @@ void launch_attr_reduce(const AttrReduceArgs& a, int M, hipStream_t s) {
   if (a.finish != ATTR_FINISH_NONE && a.finish != ATTR_FINISH_SCALE && a.finish != ATTR_FINISH_PATH)
     throw std::runtime_error("attr_reduce: unknown finish form");
   if (a.finish != ATTR_FINISH_NONE && !a.out) throw std::runtime_error("attr_reduce: null argument (finish needs out)");
-  if ((reinterpret_cast<uintptr_t>(a.dx) | reinterpret_cast<uintptr_t>(a.acc) | reinterpret_cast<uintptr_t>(a.out)) & 15)
+  if (misaligned(15, a.dx, a.acc, a.out))
     throw std::runtime_error("attr_reduce: dx, acc and out must be 16-byte aligned");
-  const unsigned grid = (unsigned)(((int64_t)M * AT_VECS + AR_THREADS - 1) / AR_THREADS);
+  const unsigned grid = (unsigned)(((int64_t)M * ROW_VECS + AR_THREADS - 1) / AR_THREADS);
   if (a.finish == ATTR_FINISH_PATH) {
-    check_image("attr_reduce", a.x_u8, a.x_f32, a.base);
+    check_row_source("attr_reduce", a.x_u8, a.x_f32, a.base);
     if (a.x_u8)
       hipLaunchKernelGGL(attr_reduce_kernel<1>, dim3(grid), dim3(AR_THREADS), 0, s, a, M);
     else

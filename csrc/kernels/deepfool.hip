@@ -45,35 +45,22 @@
 // selects: the compiler turned the selects back into a dynamic index and the arrays into 208 B of scratch per lane
 // (45 VGPRs).  So g_y, loss_y and the chosen row are read by address instead - the rows were read a moment before,
 // these are cache hits - and every index into registers is a loop counter of an unrolled loop: no scratch.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
-
-#include <stdexcept>
+#include "../runtime/host_logic.h"
+#include "row_ops.h"
 
 namespace mnist {
 
 namespace {
-constexpr int DF_THREADS = 256, DF_WAVES = DF_THREADS / 64;
-constexpr int DF_VECS = IMG * IMG / 4;                   // 196 float4 per row
 constexpr int DF_OTHERS = DF_CLASSES - 1;                // the classes k != y; class k owns the LDS words j = k - (k > y)
-static_assert(DF_VECS * 4 == IMG * IMG && DF_VECS <= DF_THREADS && DF_WAVES == 4, "one float4 per thread");
 
-__device__ __forceinline__ float df_sq4(const float4& v) {
-#pragma clang fp contract(off)
-  return (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-}
 __device__ __forceinline__ float4 df_sub4(const float4& a, const float4& b) {
 #pragma clang fp contract(off)
   return float4{a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w};
 }
-__device__ __forceinline__ float df_clamp(float t, float lo, float hi) {   // a NaN passes
-  t = t < lo ? lo : t;
-  return t > hi ? hi : t;
-}
 __device__ __forceinline__ float df_next(float c, float os1, float r, float lo, float hi) {
 #pragma clang fp contract(off)
   const float t = os1 * r;
-  return df_clamp(c + t, lo, hi);
+  return clamp_nan_passes(c + t, lo, hi);
 }
 __device__ __forceinline__ float df_acc(float r, float sc, float w) {
 #pragma clang fp contract(off)
@@ -83,7 +70,7 @@ __device__ __forceinline__ float df_acc(float r, float sc, float w) {
 }  // namespace
 
 template <bool U8>
-__global__ __launch_bounds__(DF_THREADS) void deepfool_init_kernel(DeepfoolInitArgs a) {
+__global__ __launch_bounds__(ROW_THREADS) void deepfool_init_kernel(DeepfoolInitArgs a) {
   RW_ENTRY();
   const int v = threadIdx.x;
   const int64_t i = blockIdx.x;
@@ -92,31 +79,24 @@ __global__ __launch_bounds__(DF_THREADS) void deepfool_init_kernel(DeepfoolInitA
     a.iters[i] = 0;
     a.norm[i] = 0.0f;
   }
-  if (v >= DF_VECS) return;
-  float4 c;
-  if constexpr (U8) {
-    const uint32_t px = reinterpret_cast<const uint32_t*>(a.x_u8 + i * (IMG * IMG))[v];   // rows are 784 B
-    c.x = normalize_u8_alu(px & 0xffu);
-    c.y = normalize_u8_alu((px >> 8) & 0xffu);
-    c.z = normalize_u8_alu((px >> 16) & 0xffu);
-    c.w = normalize_u8_alu(px >> 24);
-  } else {
-    c = reinterpret_cast<const float4*>(a.x_f32)[i * DF_VECS + v];
-  }
-  const int64_t at = i * DF_VECS + v;
+  if (v >= ROW_VECS) return;
+  float4 c;                                              // (fp32 rows: read here, not through row_load - row_ops.h)
+  if constexpr (U8) c = row_load_u8(a.x_u8, i, v);
+  else c = reinterpret_cast<const float4*>(a.x_f32)[i * ROW_VECS + v];
+  const int64_t at = i * ROW_VECS + v;
   reinterpret_cast<float4*>(a.x)[at] = c;
   if (a.x0_out) reinterpret_cast<float4*>(a.x0_out)[at] = c;
   reinterpret_cast<float4*>(a.r_tot)[at] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-  float4* row = reinterpret_cast<float4*>(a.rows) + i * (DF_CLASSES * DF_VECS) + v;
+  float4* row = reinterpret_cast<float4*>(a.rows) + i * (DF_CLASSES * ROW_VECS) + v;
 #pragma unroll
-  for (int k = 0; k < DF_CLASSES; ++k) row[k * DF_VECS] = c;
+  for (int k = 0; k < DF_CLASSES; ++k) row[k * ROW_VECS] = c;
 }
 
-__global__ __launch_bounds__(DF_THREADS) void deepfool_step_kernel(DeepfoolStepArgs a) {
+__global__ __launch_bounds__(ROW_THREADS) void deepfool_step_kernel(DeepfoolStepArgs a) {
 #pragma clang fp contract(off)
-  __shared__ float part[DF_OTHERS + 1][DF_WAVES];        // the nine class sums (36 words), then the norm's
+  __shared__ float part[DF_OTHERS + 1][ROW_WAVES];        // the nine class sums (36 words), then the norm's
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const bool own = tid < DF_VECS;
+  const bool own = tid < ROW_VECS;
   const int64_t i = blockIdx.x;
   RW_ENTRY();
   if (a.status[i] != DF_RUNNING) return;                 // 1. frozen
@@ -138,14 +118,14 @@ __global__ __launch_bounds__(DF_THREADS) void deepfool_step_kernel(DeepfoolStepA
     return;
   }
 
-  const int64_t at = i * DF_VECS + (own ? tid : 0);      // (idle threads: a valid address)
-  const float4* grow = reinterpret_cast<const float4*>(a.dx) + i * (DF_CLASSES * DF_VECS) + (own ? tid : 0);
-  const float4 gy = grow[y * DF_VECS];                   // by address: every index into registers stays static
+  const int64_t at = i * ROW_VECS + (own ? tid : 0);      // (idle threads: a valid address)
+  const float4* grow = reinterpret_cast<const float4*>(a.dx) + i * (DF_CLASSES * ROW_VECS) + (own ? tid : 0);
+  const float4 gy = grow[y * ROW_VECS];                   // by address: every index into registers stays static
 #pragma unroll
   for (int k = 0; k < DF_CLASSES; ++k) {                 // 4. class k != y owns the words j = k - (k > y)
     if (k == y) continue;
-    const float4 w = df_sub4(gy, grow[k * DF_VECS]);
-    const float s = wave_sum(own ? df_sq4(w) : 0.0f);
+    const float4 w = df_sub4(gy, grow[k * ROW_VECS]);
+    const float s = wave_sum(own ? row_sq4(w) : 0.0f);
     if (lane == 0) part[k - (k > y ? 1 : 0)][wave] = s;
   }
   lds_barrier();
@@ -155,9 +135,8 @@ __global__ __launch_bounds__(DF_THREADS) void deepfool_step_kernel(DeepfoolStepA
 #pragma unroll
   for (int k = 0; k < DF_CLASSES; ++k) {
     if (k == y) continue;
-    const float* pj = part[k - (k > y ? 1 : 0)];
     const float f = ly - loss[k];
-    const float n2 = (pj[0] + pj[1]) + (pj[2] + pj[3]);
+    const float n2 = row_waves_sum(part[k - (k > y ? 1 : 0)]);
     const float n = sqrtf(n2);
     const float num = fabsf(f) + DF_SLACK;
     const float ratio = num / n;
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(DF_THREADS) void deepfool_step_kernel(DeepfoolStepA
     }
     l = l_nan; num_l = num_nan; n2_l = n2_nan;
   }
-  const float4 w = df_sub4(gy, grow[l * DF_VECS]);       // (the chosen row again: a cache hit, not a register array)
+  const float4 w = df_sub4(gy, grow[l * ROW_VECS]);       // (the chosen row again: a cache hit, not a register array)
   const float sc = num_l / n2_l;                         // 6.
   float4 r = reinterpret_cast<const float4*>(a.r_tot)[at];
   const float4 c = reinterpret_cast<const float4*>(a.x0)[at];
@@ -192,51 +171,46 @@ __global__ __launch_bounds__(DF_THREADS) void deepfool_step_kernel(DeepfoolStepA
   if (own) {                                             // 8.
     reinterpret_cast<float4*>(a.r_tot)[at] = r;
     reinterpret_cast<float4*>(a.x)[at] = o;
-    float4* row = reinterpret_cast<float4*>(a.rows) + i * (DF_CLASSES * DF_VECS) + tid;
+    float4* row = reinterpret_cast<float4*>(a.rows) + i * (DF_CLASSES * ROW_VECS) + tid;
 #pragma unroll
-    for (int k = 0; k < DF_CLASSES; ++k) row[k * DF_VECS] = o;
+    for (int k = 0; k < DF_CLASSES; ++k) row[k * ROW_VECS] = o;
   } else {
     d = float4{0.0f, 0.0f, 0.0f, 0.0f};
   }
-  const float m = wave_sum(df_sq4(d));                   // 9.
+  const float m = wave_sum(row_sq4(d));                  // 9.
   if (lane == 0) part[DF_OTHERS][wave] = m;
   lds_barrier();
   if (tid == 0) {
-    a.norm[i] = sqrtf((part[DF_OTHERS][0] + part[DF_OTHERS][1]) + (part[DF_OTHERS][2] + part[DF_OTHERS][3]));
+    a.norm[i] = sqrtf(row_waves_sum(part[DF_OTHERS]));
     a.iters[i] = a.iters[i] + 1;                         // 10.
   }
 }
 
-namespace {
-inline uintptr_t up(const void* p) { return reinterpret_cast<uintptr_t>(p); }
-}  // namespace
-
 void launch_deepfool_init(const DeepfoolInitArgs& a, int M, hipStream_t s) {
   if (M < 1 || M > DF_MAX_M) throw std::runtime_error("deepfool_init: image count out of range");
-  if ((a.x_u8 != nullptr) == (a.x_f32 != nullptr))
-    throw std::runtime_error("deepfool_init: null argument (exactly one of the uint8 and the fp32 rows)");
+  check_one_row_source("deepfool_init", a.x_u8, a.x_f32);
   if (!a.rows || !a.x || !a.r_tot || !a.status || !a.iters || !a.norm || (a.x_u8 && !a.x0_out))
     throw std::runtime_error("deepfool_init: null argument");
-  if ((up(a.x_f32) | up(a.rows) | up(a.x) | up(a.x0_out) | up(a.r_tot)) & 15)
+  if (misaligned(15, a.x_f32, a.rows, a.x, a.x0_out, a.r_tot))
     throw std::runtime_error("deepfool_init: the fp32 row arrays must be 16-byte aligned");
-  if ((up(a.x_u8) | up(a.status) | up(a.iters) | up(a.norm)) & 3)
+  if (misaligned(3, a.x_u8, a.status, a.iters, a.norm))
     throw std::runtime_error("deepfool_init: the uint8 rows and the per-image vectors must be 4-byte aligned");
   if (a.x_u8)
-    hipLaunchKernelGGL(deepfool_init_kernel<true>, dim3(M), dim3(DF_THREADS), 0, s, a);
+    hipLaunchKernelGGL(deepfool_init_kernel<true>, dim3(M), dim3(ROW_THREADS), 0, s, a);
   else
-    hipLaunchKernelGGL(deepfool_init_kernel<false>, dim3(M), dim3(DF_THREADS), 0, s, a);
+    hipLaunchKernelGGL(deepfool_init_kernel<false>, dim3(M), dim3(ROW_THREADS), 0, s, a);
 }
 
 void launch_deepfool_step(const DeepfoolStepArgs& a, int M, hipStream_t s) {
   if (M < 1 || M > DF_MAX_M) throw std::runtime_error("deepfool_step: image count out of range");
   if (!a.dx || !a.loss_rows || !a.y || !a.x0 || !a.r_tot || !a.x || !a.rows || !a.status || !a.iters || !a.norm)
     throw std::runtime_error("deepfool_step: null argument");
-  if ((up(a.dx) | up(a.x0) | up(a.r_tot) | up(a.x) | up(a.rows)) & 15)
+  if (misaligned(15, a.dx, a.x0, a.r_tot, a.x, a.rows))
     throw std::runtime_error("deepfool_step: the fp32 row arrays must be 16-byte aligned");
-  if ((up(a.loss_rows) | up(a.y) | up(a.status) | up(a.iters) | up(a.norm)) & 3)
+  if (misaligned(3, a.loss_rows, a.y, a.status, a.iters, a.norm))
     throw std::runtime_error("deepfool_step: the per-image vectors must be 4-byte aligned");
   if (!(a.overshoot >= 0.0f)) throw std::runtime_error("deepfool_step: overshoot must be >= 0");
-  hipLaunchKernelGGL(deepfool_step_kernel, dim3(M), dim3(DF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(deepfool_step_kernel, dim3(M), dim3(ROW_THREADS), 0, s, a);
 }
 
 void preload_deepfool() {

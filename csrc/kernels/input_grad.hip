@@ -25,8 +25,7 @@
 // an L-inf signed-gradient ascent (FGSM / PGD) instead, and s itself only when asked:
 //   t = x + alpha * sgn(s);  t = min(max(t, x0 - eps), x0 + eps);  x_next = min(max(t, lo), hi)
 // (launch_input_grad_step).  Its x / x0 loads are issued before stage 2 and land under the 288 fmas.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
+#include "row_ops.h"
 
 #include <stdexcept>
 
@@ -87,13 +86,9 @@ struct IgProjectedStep {
     // torch.sign, except that a NaN gradient stays a NaN (every comparison below is false for it, so it
     // passes both clamps): a broken gradient is not turned into "no step"
     const float sg = s > 0.0f ? 1.0f : s < 0.0f ? -1.0f : s == s ? 0.0f : s;
-    float t = v.x + alpha * sg;                            // alpha * sg is exact: contraction cannot change it
+    const float t = v.x + alpha * sg;                           // alpha * sg is exact: contraction cannot change it
     const float el = v.x0 - eps, eh = v.x0 + eps;          // rounded to fp32 first, as the torch formula does
-    t = t < el ? el : t;
-    t = t > eh ? eh : t;
-    t = t < lo ? lo : t;
-    t = t > hi ? hi : t;
-    x_next[e] = t;
+    x_next[e] = clamp_nan_passes(clamp_nan_passes(t, el, eh), lo, hi);
   }
 };
 

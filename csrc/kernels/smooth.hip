@@ -47,17 +47,12 @@
 // row holding a NaN votes for nothing.  A thread keeps its ten bins in registers, a wave sums them by shuffles,
 // the four waves meet in LDS: integer adds only, so the order is irrelevant.  accumulate adds to the counts
 // already there (the samples of one image may arrive in several launches); rows of counts past M are untouched.
-#include "../include/device_utils.h"
-#include "../include/kernels.h"
-
-#include <stdexcept>
+#include "../runtime/host_logic.h"
+#include "row_ops.h"
 
 namespace mnist {
 
 namespace {
-constexpr int SN_THREADS = 256;
-constexpr int SN_VECS = IMG * IMG / 4;                   // 196 float4 per image
-static_assert(SN_VECS * 4 == IMG * IMG && SN_VECS <= SN_THREADS, "one float4 per thread");
 constexpr int SV_THREADS = 256, SV_WAVES = SV_THREADS / 64;
 
 // one Box-Muller pair from two Philox words
@@ -78,10 +73,10 @@ __device__ __forceinline__ float sn_add(float x0, float sigma, float z) {
 
 // SRC 0: uint8 rows; 1: fp32 rows; 2: the step form (fp32 rows x0, counters from the StepState)
 template <int SRC>
-__global__ __launch_bounds__(SN_THREADS) void smooth_noise_kernel(SmoothNoiseArgs a) {
+__global__ __launch_bounds__(ROW_THREADS) void smooth_noise_kernel(SmoothNoiseArgs a) {
   RW_ENTRY();
   const int v = threadIdx.x;
-  if (v >= SN_VECS) return;
+  if (v >= ROW_VECS) return;
   const int64_t r = blockIdx.x;
   int64_t i;
   uint32_t c0, c2;
@@ -97,16 +92,9 @@ __global__ __launch_bounds__(SN_THREADS) void smooth_noise_kernel(SmoothNoiseArg
     c0 = a.sample_base + (uint32_t)(r - i * a.n);
     c2 = a.id_base + (uint32_t)i;
   }
-  float4 c;
-  if constexpr (SRC == 0) {
-    const uint32_t px = reinterpret_cast<const uint32_t*>(a.x_u8 + i * (IMG * IMG))[v];   // rows are 784 B
-    c.x = normalize_u8_alu(px & 0xffu);
-    c.y = normalize_u8_alu((px >> 8) & 0xffu);
-    c.z = normalize_u8_alu((px >> 16) & 0xffu);
-    c.w = normalize_u8_alu(px >> 24);
-  } else {
-    c = reinterpret_cast<const float4*>(a.x_f32)[i * SN_VECS + v];
-  }
+  float4 c;                                              // (fp32 rows: read here, not through row_load - row_ops.h)
+  if constexpr (SRC == 0) c = row_load_u8(a.x_u8, i, v);
+  else c = reinterpret_cast<const float4*>(a.x_f32)[i * ROW_VECS + v];
   const u32x4 w = philox4x32(c0, SMOOTH_PHILOX_DOMAIN, c2, (uint32_t)v, (uint32_t)seed, (uint32_t)(seed >> 32));
   float z0, z1, z2, z3;
   sn_pair(w[0], w[1], z0, z1);
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(SN_THREADS) void smooth_noise_kernel(SmoothNoiseArg
   o.y = sn_add(c.y, a.sigma, z1);
   o.z = sn_add(c.z, a.sigma, z2);
   o.w = sn_add(c.w, a.sigma, z3);
-  reinterpret_cast<float4*>(a.out)[r * SN_VECS + v] = o;
+  reinterpret_cast<float4*>(a.out)[r * ROW_VECS + v] = o;
 }
 
 __global__ __launch_bounds__(SV_THREADS) void smooth_vote_kernel(SmoothVoteArgs a) {
@@ -163,42 +151,38 @@ void check_noise_common(const SmoothNoiseArgs& a, const void* src, int64_t rows)
   if (!src || !a.out) throw std::runtime_error("smooth_noise: null argument");
   if (rows < 1 || rows > SMOOTH_MAX_ROWS) throw std::runtime_error("smooth_noise: M * n out of range");
   if (!(a.sigma >= 0.0f)) throw std::runtime_error("smooth_noise: need sigma >= 0");
-  if (reinterpret_cast<uintptr_t>(a.out) & 15) throw std::runtime_error("smooth_noise: out must be 16-byte aligned");
+  if (misaligned(15, a.out)) throw std::runtime_error("smooth_noise: out must be 16-byte aligned");
 }
 }  // namespace
 
 void launch_smooth_noise(const SmoothNoiseArgs& a, int M, hipStream_t s) {
-  if ((a.x_u8 != nullptr) == (a.x_f32 != nullptr))
-    throw std::runtime_error("smooth_noise: null argument (exactly one of the uint8 and the fp32 rows)");
+  check_one_row_source("smooth_noise", a.x_u8, a.x_f32);
   if (M < 1 || a.n < 1) throw std::runtime_error("smooth_noise: M * n out of range");
   const int64_t rows = (int64_t)M * a.n;
   check_noise_common(a, a.x_u8 ? static_cast<const void*>(a.x_u8) : a.x_f32, rows);
-  if (a.x_u8 ? (reinterpret_cast<uintptr_t>(a.x_u8) & 3) : (reinterpret_cast<uintptr_t>(a.x_f32) & 15))
-    throw std::runtime_error("smooth_noise: the source rows must be 16-byte aligned (uint8 rows: 4-byte)");
+  check_row_source_aligned("smooth_noise", a.x_u8, a.x_f32);
   if ((uint64_t)a.sample_base + (uint64_t)a.n > (1ull << 32))
     throw std::runtime_error("smooth_noise: sample_base + n must not exceed 2^32");
   if ((uint64_t)a.id_base + (uint64_t)M > (1ull << 32))
     throw std::runtime_error("smooth_noise: id_base + M must not exceed 2^32");
   if (a.x_u8)
-    hipLaunchKernelGGL(smooth_noise_kernel<0>, dim3((unsigned)rows), dim3(SN_THREADS), 0, s, a);
+    hipLaunchKernelGGL(smooth_noise_kernel<0>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, s, a);
   else
-    hipLaunchKernelGGL(smooth_noise_kernel<1>, dim3((unsigned)rows), dim3(SN_THREADS), 0, s, a);
+    hipLaunchKernelGGL(smooth_noise_kernel<1>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, s, a);
 }
 
 void launch_smooth_noise_step(const StepState* state, const float* x0, float* x, float sigma, int B, hipStream_t s) {
   SmoothNoiseArgs a{nullptr, x0, x, state, sigma, 0, 0u, 0u, 1};
   if (!state) throw std::runtime_error("smooth_noise: null argument");
   check_noise_common(a, x0, B);
-  if (reinterpret_cast<uintptr_t>(x0) & 15)
-    throw std::runtime_error("smooth_noise: the source rows must be 16-byte aligned (uint8 rows: 4-byte)");
-  hipLaunchKernelGGL(smooth_noise_kernel<2>, dim3((unsigned)B), dim3(SN_THREADS), 0, s, a);
+  check_row_source_aligned("smooth_noise", nullptr, x0);
+  hipLaunchKernelGGL(smooth_noise_kernel<2>, dim3((unsigned)B), dim3(ROW_THREADS), 0, s, a);
 }
 
 void launch_smooth_vote(const SmoothVoteArgs& a, int M, hipStream_t s) {
   if (!a.logp || !a.counts) throw std::runtime_error("smooth_vote: null argument");
   if (M < 1 || a.n < 1 || (int64_t)M * a.n > SMOOTH_MAX_ROWS) throw std::runtime_error("smooth_vote: M * n out of range");
-  if ((reinterpret_cast<uintptr_t>(a.logp) | reinterpret_cast<uintptr_t>(a.counts)) & 3)
-    throw std::runtime_error("smooth_vote: logp and counts must be 4-byte aligned");
+  if (misaligned(3, a.logp, a.counts)) throw std::runtime_error("smooth_vote: logp and counts must be 4-byte aligned");
   hipLaunchKernelGGL(smooth_vote_kernel, dim3(M), dim3(SV_THREADS), 0, s, a);
 }
 

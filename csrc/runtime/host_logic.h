@@ -4,7 +4,8 @@
 //   * the engine's workspace carve (offsets of every activation buffer for a batch capacity);
 //   * the xGMI IPC export record: encode / decode / validation against this communicator;
 //   * the residency planner's grid fitting;
-//   * the DDP gradient scaling constants the engine hands its kernels.
+//   * the DDP gradient scaling constants the engine hands its kernels;
+//   * the pointer checks the row kernels' launchers share (alignment, the uint8-or-fp32 image source).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -216,6 +217,35 @@ inline XgmiRecord decode_record(const std::vector<uint8_t>& bytes, int q, int wo
   if (strncmp(my_host, r.host, sizeof(r.host)) != 0)
     throw std::runtime_error("xgmi: ranks span more than one node (peer on " + std::string(r.host) + ")");
   return r;
+}
+
+// ---------------------------------------------------------------------------- launcher argument checks
+// Does any of the pointers have a bit under `mask` set (mask 15: 16-byte alignment, 3: 4-byte)?  A null
+// pointer counts as aligned: whether it may be null is the caller's own check.
+template <class... Ps>
+inline bool misaligned(uintptr_t mask, const Ps*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & mask) != 0;
+}
+
+// The image source of a row kernel is uint8 rows (read four pixels at a time) or normalised fp32 rows (read as
+// float4), never both.  `who` is the launcher's name as its messages begin.  The two halves are separate because
+// some launchers check their sizes in between, and which error a doubly wrong call gets is part of the interface.
+inline void check_one_row_source(const char* who, const uint8_t* x_u8, const float* x_f32) {
+  if ((x_u8 != nullptr) == (x_f32 != nullptr))
+    throw std::runtime_error(std::string(who) + ": null argument (exactly one of the uint8 and the fp32 rows)");
+}
+inline void check_row_source_aligned(const char* who, const uint8_t* x_u8, const float* x_f32) {
+  if (x_u8 ? misaligned(3, x_u8) : misaligned(15, x_f32))
+    throw std::runtime_error(std::string(who) + ": the source rows must be 16-byte aligned (uint8 rows: 4-byte)");
+}
+inline void check_row_source(const char* who, const uint8_t* x_u8, const float* x_f32) {
+  check_one_row_source(who, x_u8, x_f32);
+  check_row_source_aligned(who, x_u8, x_f32);
+}
+// ... with the optional fp32 baseline rows of the attribution kernels
+inline void check_row_source(const char* who, const uint8_t* x_u8, const float* x_f32, const float* base) {
+  check_row_source(who, x_u8, x_f32);
+  if (misaligned(15, base)) throw std::runtime_error(std::string(who) + ": the baseline rows must be 16-byte aligned");
 }
 
 // ---------------------------------------------------------------------------- residency planner

@@ -7,7 +7,8 @@
 //     unterminated records, plus random byte soup (must throw, never read out of bounds);
 //   * the residency planner's grid fitting;
 //   * the engine's step plan (plan_step) for every schedule, batch class and switch, and the values
-//     of the named device counters.
+//     of the named device counters;
+//   * the row kernels' pointer checks (misaligned, check_row_source) and their exact messages.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -268,7 +269,56 @@ static void test_fit() {
   CHECK(threw);
 }
 
+// the message a check throws, "" when it passes
+template <class F>
+static std::string thrown(F f) {
+  try {
+    f();
+  } catch (const std::runtime_error& e) {
+    return e.what();
+  }
+  return "";
+}
+
+// the row kernels' pointer checks: the predicate, and the launchers' messages word for word
+static void test_row_checks() {
+  alignas(16) static unsigned char mem[64];
+  const uint8_t* u0 = mem;
+  const float* f0 = reinterpret_cast<const float*>(mem);
+  const float* f4 = reinterpret_cast<const float*>(mem + 4);   // 4-byte aligned only
+  const float* fnull = nullptr;
+  CHECK(!misaligned(15, fnull) && !misaligned(3, fnull) && !misaligned(15));   // null counts as aligned
+  CHECK(!misaligned(3, f4) && misaligned(15, f4) && !misaligned(15, f0) && misaligned(3, u0 + 1));
+  CHECK(misaligned(15, f0, fnull, f4) && misaligned(15, f4, f0) && !misaligned(15, f0, fnull, u0 + 16));   // the OR
+  CHECK(misaligned(3, f0, u0 + 2, f4) && !misaligned(3, f0, u0, f4));
+
+  const std::string one = "smooth_noise: null argument (exactly one of the uint8 and the fp32 rows)";
+  const std::string src = "smooth_noise: the source rows must be 16-byte aligned (uint8 rows: 4-byte)";
+  CHECK(thrown([&] { check_row_source("smooth_noise", nullptr, nullptr); }) == one);
+  CHECK(thrown([&] { check_row_source("smooth_noise", u0, f0); }) == one);
+  CHECK(thrown([&] { check_row_source("smooth_noise", u0 + 1, nullptr); }) == src);
+  CHECK(thrown([&] { check_row_source("smooth_noise", u0 + 2, nullptr); }) == src);
+  CHECK(thrown([&] { check_row_source("smooth_noise", nullptr, f4); }) == src);
+  CHECK(thrown([&] { check_row_source("smooth_noise", u0 + 4, nullptr); }) == "");   // uint8 rows: 4 bytes suffice
+  CHECK(thrown([&] { check_row_source("smooth_noise", nullptr, f0); }) == "");
+  CHECK(thrown([&] { check_one_row_source("deepfool_init", u0, f0); }) ==
+        "deepfool_init: null argument (exactly one of the uint8 and the fp32 rows)");
+  CHECK(thrown([&] { check_one_row_source("deepfool_init", u0 + 1, nullptr); }) == "");   // alignment is the other half
+  CHECK(thrown([&] { check_row_source_aligned("smooth_noise", nullptr, f4); }) == src);
+
+  CHECK(thrown([&] { check_row_source("attr_path", nullptr, nullptr, f0); }) ==
+        "attr_path: null argument (exactly one of the uint8 and the fp32 rows)");
+  CHECK(thrown([&] { check_row_source("attr_reduce", u0 + 1, nullptr, f4); }) ==   // the source is checked first
+        "attr_reduce: the source rows must be 16-byte aligned (uint8 rows: 4-byte)");
+  CHECK(thrown([&] { check_row_source("attr_path", u0, nullptr, f4); }) == "attr_path: the baseline rows must be 16-byte aligned");
+  CHECK(thrown([&] { check_row_source("attr_reduce", nullptr, f0, f4); }) ==
+        "attr_reduce: the baseline rows must be 16-byte aligned");
+  CHECK(thrown([&] { check_row_source("attr_path", u0 + 4, nullptr, nullptr); }) == "");   // no baseline rows: a scalar
+  CHECK(thrown([&] { check_row_source("attr_path", nullptr, f0, f0 + 4); }) == "");
+}
+
 int main() {
+  test_row_checks();
   test_workspace();
   test_records();
   test_fit();

@@ -197,10 +197,7 @@ def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.T
     what the conv backward reads (``buf.dyc`` after ``fc_bwd``, ``buf.a1``, the conv weights).  Every
     element of ``out`` is written; it needs no zeroing."""
     B = buf.B
-    if out is None:
-        out = torch.empty(B, 784, dtype=torch.float32, device=buf.dyc.device)
-    else:
-        _f32_rows("input_grad", "out", out, B, buf.dyc.device)
+    out = _out_rows("input_grad", "out", out, B, buf.dyc.device)
     p, w = native.ptr, param_ptrs(ms)
     _C().input_grad(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(out), B, _s())
     return out.view(B, 784)
@@ -212,6 +209,26 @@ def _f32_rows(name: str, what: str, t: torch.Tensor, B: int, device, at_least: s
             (t.numel() < B * 784 if at_least else t.numel() != B * 784):
         shape = f"with at least {at_least} rows of 784" if at_least else "[B, 784]"
         raise ValueError(f"{name}: {what} must be contiguous float32 {shape} on the buffers' device")
+
+
+def _out_rows(name: str, what: str, out: torch.Tensor | None, rows: int, device,
+              at_least: str | None = None) -> torch.Tensor:
+    """The output ``out`` of a row kernel: a new float32 [rows, 784] when None, else checked as ``_f32_rows`` does."""
+    if out is None:
+        return torch.empty(rows, 784, dtype=torch.float32, device=device)
+    _f32_rows(name, what, out, rows, device, at_least)
+    return out
+
+
+def _src_ptrs(x: torch.Tensor) -> tuple[int, int]:
+    """(uint8 pointer, float32 pointer) of the image rows ``x``: the one it is, and 0."""
+    return (native.ptr(x), 0) if x.dtype == torch.uint8 else (0, native.ptr(x))
+
+
+def _check_rows(name: str, expr: str, rows: int) -> None:
+    """A launch takes at most ``SMOOTH_MAX_ROWS`` rows; ``expr`` is the caller's name for ``rows``."""
+    if rows > SMOOTH_MAX_ROWS:
+        raise ValueError(f"{name}: {expr} = {rows} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
 
 
 def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
@@ -228,10 +245,7 @@ def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps
     B, dev = buf.B, buf.dyc.device
     _f32_rows("input_grad_step", "x", x, B, dev)
     _f32_rows("input_grad_step", "x0", x0, B, dev)
-    if out is None:
-        out = torch.empty(B, 784, dtype=torch.float32, device=dev)
-    else:
-        _f32_rows("input_grad_step", "out", out, B, dev)
+    out = _out_rows("input_grad_step", "out", out, B, dev)
     if out.data_ptr() == x0.data_ptr():
         raise ValueError("input_grad_step: out must not be x0 (the centre of the eps ball is read, not written)")
     if dx is not None:
@@ -278,10 +292,7 @@ def pgd_l2_step(dx: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, eps: float,
     _f32_rows("pgd_l2_step", "x", x, B, dev)
     _f32_rows("pgd_l2_step", "x0", x0, B, dev)
     _f32_rows("pgd_l2_step", "dx", dx, B, dev)
-    if out is None:
-        out = torch.empty(B, 784, dtype=torch.float32, device=dev)
-    else:
-        _f32_rows("pgd_l2_step", "out", out, B, dev)
+    out = _out_rows("pgd_l2_step", "out", out, B, dev)
     if out.data_ptr() in (x0.data_ptr(), dx.data_ptr()):
         raise ValueError("pgd_l2_step: out must not be x0 or dx (both are read, not written)")
     if not (eps >= 0 and lo <= hi and alpha == alpha):
@@ -317,14 +328,10 @@ def adv_init(data_u8: torch.Tensor, labels: torch.Tensor, idx: torch.Tensor | No
         raise ValueError("adv_init: labels and idx must be int32")
     if B < 1:
         raise ValueError("adv_init: B must be positive")
-    if x0 is None:
-        x0 = torch.empty(B, 784, dtype=torch.float32, device=dev)
-    if x is None:
-        x = torch.empty(B, 784, dtype=torch.float32, device=dev)
+    x0 = _out_rows("adv_init", "x0", x0, B, dev, at_least="B")
+    x = _out_rows("adv_init", "x", x, B, dev, at_least="B")
     if labels_out is None:
         labels_out = torch.empty(B, dtype=torch.int32, device=dev)
-    _f32_rows("adv_init", "x0", x0, B, dev, at_least="B")
-    _f32_rows("adv_init", "x", x, B, dev, at_least="B")
     if labels_out.dtype != torch.int32 or labels_out.numel() < B or labels_out.device != dev:
         raise ValueError("adv_init: labels_out must be int32 with at least B entries")
     if x0.data_ptr() == x.data_ptr():
@@ -359,18 +366,13 @@ def smooth_noise(x: torch.Tensor, sigma: float, n: int, seed: int, sample_base: 
     M, n = x.shape[0], int(n)
     if M < 1 or n < 1:
         raise ValueError("smooth_noise: M and n must be positive")
-    if M * n > SMOOTH_MAX_ROWS:
-        raise ValueError(f"smooth_noise: M * n = {M * n} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    _check_rows("smooth_noise", "M * n", M * n)
     if not sigma >= 0:
         raise ValueError(f"smooth_noise: sigma must be >= 0, got {sigma}")
     if sample_base < 0 or sample_base + n > 1 << 32 or id_base < 0 or id_base + M > 1 << 32:
         raise ValueError("smooth_noise: sample_base + n and id_base + M must not exceed 2**32")
-    if out is None:
-        out = torch.empty(M * n, 784, dtype=torch.float32, device=x.device)
-    _f32_rows("smooth_noise", "out", out, M * n, x.device, at_least="M * n")
-    p = native.ptr
-    u8 = x.dtype == torch.uint8
-    _C().smooth_noise(p(x) if u8 else 0, 0 if u8 else p(x), p(out), float(sigma), int(seed) & (2 ** 64 - 1),
+    out = _out_rows("smooth_noise", "out", out, M * n, x.device, at_least="M * n")
+    _C().smooth_noise(*_src_ptrs(x), native.ptr(out), float(sigma), int(seed) & (2 ** 64 - 1),
                       int(sample_base), int(id_base), M, n, _s())
     return out
 
@@ -383,13 +385,10 @@ def smooth_noise_step(state: torch.Tensor, x0: torch.Tensor, sigma: float, B: in
     most ``SMOOTH_MAX_ROWS`` = 2**23 (``ValueError`` beyond)."""
     if x0.dtype != torch.float32 or not x0.is_contiguous() or x0.numel() < B * 784 or B < 1:
         raise ValueError("smooth_noise_step: x0 must be contiguous float32 with at least B >= 1 rows of 784")
-    if B > SMOOTH_MAX_ROWS:
-        raise ValueError(f"smooth_noise_step: B = {B} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    _check_rows("smooth_noise_step", "B", B)
     if not sigma >= 0:
         raise ValueError(f"smooth_noise_step: sigma must be >= 0, got {sigma}")
-    if x is None:
-        x = torch.empty(B, 784, dtype=torch.float32, device=x0.device)
-    _f32_rows("smooth_noise_step", "x", x, B, x0.device, at_least="B")
+    x = _out_rows("smooth_noise_step", "x", x, B, x0.device, at_least="B")
     p = native.ptr
     _C().smooth_noise_step(p(state), p(x0), p(x), float(sigma), B, _s())
     return x
@@ -404,8 +403,7 @@ def smooth_vote(logp: torch.Tensor, M: int, n: int, counts: torch.Tensor | None 
     ``SMOOTH_MAX_ROWS`` = 2**23 rows M * n (``ValueError`` beyond; accumulate over several launches)."""
     if logp.dtype != torch.float32 or not logp.is_contiguous() or M < 1 or n < 1 or logp.numel() < M * n * NCLS:
         raise ValueError("smooth_vote: logp must be contiguous float32 with at least M * n >= 1 rows of 10")
-    if M * n > SMOOTH_MAX_ROWS:
-        raise ValueError(f"smooth_vote: M * n = {M * n} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    _check_rows("smooth_vote", "M * n", M * n)
     if counts is None:
         if accumulate:
             raise ValueError("smooth_vote: accumulate needs counts")
@@ -486,15 +484,13 @@ def _attr_image_args(name: str, x: torch.Tensor, base, M: int):
     """(x_u8, x_f32, base pointer, base value) of an image / baseline pair, checked."""
     if x.dim() != 2 or x.shape != (M, 784) or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous():
         raise ValueError(f"{name}: x must be contiguous uint8 or float32 [M, 784]")
-    p = native.ptr
-    u8 = x.dtype == torch.uint8
     if isinstance(base, torch.Tensor):
         if base.shape != (M, 784) or base.dtype != torch.float32 or not base.is_contiguous() or base.device != x.device:
             raise ValueError(f"{name}: a baseline tensor must be contiguous float32 [M, 784] on x's device")
-        return (p(x) if u8 else 0, 0 if u8 else p(x), p(base), 0.0)
+        return (*_src_ptrs(x), native.ptr(base), 0.0)
     if not isinstance(base, (int, float)) or base != base:
         raise ValueError(f"{name}: the baseline must be a float or a float32 [M, 784] tensor")
-    return (p(x) if u8 else 0, 0 if u8 else p(x), 0, float(base))
+    return (*_src_ptrs(x), 0, float(base))
 
 
 def attr_path(x: torch.Tensor, n_total: int, sample_base: int = 0, ns: int | None = None, base=0.0,
@@ -515,14 +511,11 @@ def attr_path(x: torch.Tensor, n_total: int, sample_base: int = 0, ns: int | Non
     ns = n_total - sample_base if ns is None else int(ns)
     if M < 1 or ns < 1:
         raise ValueError("attr_path: M and ns must be positive")
-    if M * ns > SMOOTH_MAX_ROWS:
-        raise ValueError(f"attr_path: M * ns = {M * ns} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    _check_rows("attr_path", "M * ns", M * ns)
     if n_total > ATTR_MAX_STEPS or sample_base < 0 or sample_base + ns > n_total:
         raise ValueError("attr_path: need 0 <= sample_base and sample_base + ns <= n_total <= ATTR_MAX_STEPS")
     img = _attr_image_args("attr_path", x, base, M)
-    if out is None:
-        out = torch.empty(M * ns, 784, dtype=torch.float32, device=x.device)
-    _f32_rows("attr_path", "out", out, M * ns, x.device, at_least="M * ns")
+    out = _out_rows("attr_path", "out", out, M * ns, x.device, at_least="M * ns")
     _C().attr_path(*img, native.ptr(out), sample_base, n_total, M, ns, _s())
     return out
 
@@ -540,18 +533,15 @@ def attr_reduce(dx: torch.Tensor, M: int, ns: int, acc: torch.Tensor | None = No
     returned, ``acc`` is then left as it was (unless it is ``out``).  Rows past M are not written.  At most
     ``SMOOTH_MAX_ROWS`` rows a launch (``ValueError`` beyond)."""
     M, ns = int(M), int(ns)
-    if M * ns > SMOOTH_MAX_ROWS:
-        raise ValueError(f"attr_reduce: M * ns = {M * ns} rows exceed SMOOTH_MAX_ROWS = {SMOOTH_MAX_ROWS} a launch")
+    _check_rows("attr_reduce", "M * ns", M * ns)
     if dx.dtype != torch.float32 or not dx.is_contiguous() or M < 1 or ns < 1 or dx.numel() < M * ns * 784:
         raise ValueError("attr_reduce: dx must be contiguous float32 with at least M * ns >= 1 rows of 784")
     if dx.device.type != "cuda":
         raise ValueError("attr_reduce: dx must be on the GPU")
     dev = dx.device
-    if acc is None:
-        if accumulate:
-            raise ValueError("attr_reduce: accumulate needs acc")
-        acc = torch.empty(M, 784, dtype=torch.float32, device=dev)
-    _f32_rows("attr_reduce", "acc", acc, M, dev, at_least="M")
+    if acc is None and accumulate:
+        raise ValueError("attr_reduce: accumulate needs acc")
+    acc = _out_rows("attr_reduce", "acc", acc, M, dev, at_least="M")
     if out is not None:
         _f32_rows("attr_reduce", "out", out, M, dev, at_least="M")
     p = native.ptr
@@ -667,27 +657,19 @@ def deepfool_init(x: torch.Tensor, rows: torch.Tensor | None = None, x_out: torc
     M, dev = x.shape[0], x.device
     if M < 1 or M > DF_MAX_M:
         raise ValueError(f"deepfool_init: M = {M} images must be in [1, DF_MAX_M = {DF_MAX_M}] a launch")
-    u8 = x.dtype == torch.uint8
-    f32 = dict(dtype=torch.float32, device=dev)
-    rows = torch.empty(DF_CLASSES * M, 784, **f32) if rows is None else rows
-    x_out = torch.empty(M, 784, **f32) if x_out is None else x_out
-    if x0_out is None and u8:
-        x0_out = torch.empty(M, 784, **f32)
-    r_tot = torch.empty(M, 784, **f32) if r_tot is None else r_tot
+    rows = _out_rows("deepfool_init", "rows", rows, DF_CLASSES * M, dev, at_least="10 M")
+    x_out = _out_rows("deepfool_init", "x_out", x_out, M, dev, at_least="M")
+    r_tot = _out_rows("deepfool_init", "r_tot", r_tot, M, dev, at_least="M")
+    if x0_out is not None or x.dtype == torch.uint8:
+        x0_out = _out_rows("deepfool_init", "x0_out", x0_out, M, dev, at_least="M")
     status = torch.empty(M, dtype=torch.int32, device=dev) if status is None else status
     iters = torch.empty(M, dtype=torch.int32, device=dev) if iters is None else iters
-    norm = torch.empty(M, **f32) if norm is None else norm
-    _f32_rows("deepfool_init", "rows", rows, DF_CLASSES * M, dev, at_least="10 M")
-    _f32_rows("deepfool_init", "x_out", x_out, M, dev, at_least="M")
-    _f32_rows("deepfool_init", "r_tot", r_tot, M, dev, at_least="M")
-    if x0_out is not None:
-        _f32_rows("deepfool_init", "x0_out", x0_out, M, dev, at_least="M")
+    norm = torch.empty(M, dtype=torch.float32, device=dev) if norm is None else norm
     _df_vec("deepfool_init", "status", status, torch.int32, M, dev, "M")
     _df_vec("deepfool_init", "iters", iters, torch.int32, M, dev, "M")
     _df_vec("deepfool_init", "norm", norm, torch.float32, M, dev, "M")
     p = native.ptr
-    _C().deepfool_init(p(x) if u8 else 0, 0 if u8 else p(x), p(rows), p(x_out), p(x0_out), p(r_tot), p(status),
-                       p(iters), p(norm), M, _s())
+    _C().deepfool_init(*_src_ptrs(x), p(rows), p(x_out), p(x0_out), p(r_tot), p(status), p(iters), p(norm), M, _s())
     return rows, x_out, (x0_out if x0_out is not None else x), r_tot, status, iters, norm
 
 
