@@ -11,7 +11,7 @@ What changes versus the reference loop, and why (MI355X-first):
 * DDP: the fc gradient bucket (98.4 % of bytes) is all-reduced on the comm stream while the conv
   backward runs, then its Adadelta update runs on that stream too; the conv bucket follows.  The
   transport - RCCL or the direct xGMI kernels - is chosen by validating and timing each one's
-  production schedule at startup.  Averaging (1/W) is folded into the head's loss gradient;
+  production schedule at startup (``transport.py``).  Averaging (1/W) is folded into the head's loss gradient;
 * evaluation (rank 0 only, SequentialSampler over the test set) is one captured graph per epoch
   with per-row losses / hits reduced once on the host side.
 
@@ -29,29 +29,10 @@ import torch
 from ..data.datasets import MNISTData
 from ..ops import native
 from ..utils.profiling import PhaseTimes
+from . import transport
 from .state import FLAG_NO_DROPOUT, ModelState
-
-
-# startup validation: timed replays of the chunk per candidate transport; host watchdog of the RCCL
-# schedule's replays (its first collectives also set up RCCL's channels and proxies)
-# with two candidate transports ("auto" at world > 1) the validation replay is followed by this many
-# timed replays (the choice's measure, without first-replay costs); a single candidate is timed on
-# its validation replay alone (the startup inside the reference timer: each 50-step replay is ~15 ms
-# at world 2 in the one-GPU rehearsal)
-VALIDATE_TIMED = 1
-
-
-def rccl_watchdog_s() -> float:
-    """Host watchdog of the RCCL schedule's startup replays (``MNIST_AMD_RCCL_WATCHDOG``, s)."""
-    return float(os.environ.get("MNIST_AMD_RCCL_WATCHDOG", "120"))
-
-
-# after ncclCommAbort, how long the streams may take to drain (the engine's own device-counter holds
-# time out after 60 s, so a chunk whose RCCL kernels returned always drains within that)
-RCCL_DRAIN_S = 90.0
-
-
-from ..parallel.distributed import _fault_delay  # noqa: E402  (MNIST_AMD_FAULT=kind:rank:seconds, tests)
+from .transport import (RCCL_DRAIN_S, VALIDATE_TIMED, StartupValidationError, TransportHang,  # noqa: F401
+                        rccl_watchdog_s)                     # (this module's names for driver, bench, tools)
 
 
 @dataclass
@@ -88,23 +69,6 @@ class EvalHandle:
                 self.event.synchronize()
                 self._res = (float(self.rows.double().sum()), int(self.hits.sum()), self.n)
         return self._res
-
-
-class TransportHang(RuntimeError):
-    """A startup replay of the RCCL schedule did not complete within its host watchdog: a collective
-    is stuck on the device (a peer never arrived) and cannot be cancelled - the caller reports and
-    exits the process (``fatal``) instead of waiting for the process group's 10-minute timeout."""
-    fatal = True
-
-
-class StartupValidationError(RuntimeError):
-    """No candidate transport passed: carries every candidate's report and the trainer's setup
-    phases so far (bench.py puts both into its failure JSON)."""
-
-    def __init__(self, msg: str, transport_report: dict, setup: PhaseTimes):
-        super().__init__(msg)
-        self.transport_report = transport_report
-        self.setup = setup
 
 
 _ENGINE_STREAMS: dict[int, tuple] = {}
@@ -228,7 +192,7 @@ class FusedTrainer:
     training (``transport_report``).  "auto" validates the direct xGMI transport first and keeps it
     without ever waiting for RCCL (``rccl_pending``, a ``PendingRcclComm``, is cancelled, or - deferred -
     never started); RCCL is brought up only when xGMI is unavailable or fails.  "fastest" validates and
-    times both and keeps the faster (see ``_setup_ddp``).  ``hooks``: engine variants for A/B runs
+    times both and keeps the faster (see ``transport.py``).  ``hooks``: engine variants for A/B runs
     (``HOOKS``).
     ``overlap`` (single GPU): the OVERLAP schedule (optimizer work on the comm stream) when the two
     streams pass the hand-off probe, else SERIAL.  ``xgmi_fuse``: the xGMI kernels apply Adadelta
@@ -471,172 +435,8 @@ class FusedTrainer:
     def _use_graph_set(self, name: str) -> None:
         self._graphs = self._graph_sets.setdefault(name, {})
 
-    def _rccl_candidate(self, comm, pending):
-        """The RCCL communicator: ``comm`` as given, else ``pending``'s (started now if it was deferred,
-        then waited for).  Returns (comm or None, why-not): an init that fails or times out drops RCCL,
-        it never ends the run by itself (the caller decides whether any transport is left)."""
-        if comm is not None or pending is None:
-            return comm, None
-        with self.setup.phase("rccl_comm_wait"):
-            try:
-                comm = pending.result()
-            except Exception as e:  # noqa: BLE001 - reported as the candidate's failure
-                comm = None
-                why = f"rank {self.rank}: RCCL communicator init failed ({type(e).__name__}: {e})"
-            else:
-                why = None
-        self.setup.add_info("rccl_comm_init_thread_s", round(pending.seconds or 0.0, 4))
-        # collective: a communicator is usable only when every rank has one
-        from ..parallel.distributed import gather_strings
-        msgs = [m for m in gather_strings(why or "", self.world) if m]
-        if msgs and comm is not None:
-            comm.abort()
-            comm = None
-        return comm, "; ".join(msgs) or None
-
     def _setup_ddp(self, comm, allreduce: str, two_buckets: bool, probe_world1: bool, train) -> None:
-        """Build the candidate transports, validate + time their production schedules, keep one.
-
-        * ``xgmi`` / ``rccl``: that transport only (an RCCL communicator that fails to initialise is
-          the run's error).
-        * ``auto`` (default): the direct xGMI kernels first (one node); once their production schedule
-          has validated on every rank they are kept and RCCL is never waited for - a pending RCCL init
-          is cancelled, a deferred one never starts - so RCCL's bootstrap and validation replays never
-          sit inside the reference's timer.  Only when xGMI cannot be built or fails its validation is
-          RCCL brought up and validated (its init error, timeout or stuck replay then fails the run).
-        * ``fastest``: both validated and timed, the faster kept (an RCCL init that fails drops RCCL).
-        """
-        from ..parallel.distributed import create_xgmi_comm, release_xgmi_comm
-        C = self.C
-        self.overlap = False
-        pending, self._rccl_pending = self._rccl_pending, None
-        have_r = comm is not None or pending is not None
-        want_x = allreduce == "xgmi" or (allreduce in ("auto", "fastest") and two_buckets
-                                         and (self.world > 1 or probe_world1))
-        x = None
-        xpend, self._xgmi_pending = self._xgmi_pending, None
-        if xpend is not None and not want_x:        # started by the caller, not a candidate after all
-            with self.setup.phase("xgmi_comm"):
-                x = xpend.result()
-                if x is not None:
-                    release_xgmi_comm(x, self.world)
-                x = None
-        if want_x:
-            with self.setup.phase("xgmi_comm"):   # (with a pending setup: the wait for its helper thread)
-                if xpend is not None:
-                    x = xpend.result()
-                    sub = dict(xpend.timings, helper_thread_s=round(xpend.seconds or 0.0, 4))
-                else:
-                    sub = {}
-                    x = create_xgmi_comm(self.world, self.rank, self.device, self.ms.grad.numel(), timings=sub)
-                self.setup.add_info("xgmi_comm_steps_s", sub)
-        # compute / comm streams on distinct hardware queues: the device-counter hand-offs of the
-        # XGMI schedule and of the RCCL schedule's fc update need it (one probe, every rank; after
-        # the xGMI setup, whose self-test keeps three more streams busy - with few hardware queues per
-        # process, as in the one-GPU rehearsals, the two would share queues)
-        handoff = self._probe_streams() if (x is not None or (have_r and two_buckets)) else False
-        self.engine.set_rccl_handoff(handoff)
-        if want_x:
-            if x is not None and not handoff:
-                if self.rank == 0:
-                    print("[engine] compute/comm streams share a hardware queue: no xGMI schedule", flush=True)
-                release_xgmi_comm(x, self.world)
-                x = None
-            if x is None:
-                self.transport_report["xgmi"] = {"ok": False, "validation": "setup, self-test or stream probe failed"}
-        if x is None and allreduce != "xgmi":
-            # no xGMI transport: RCCL is the only candidate left (its init is waited for only now)
-            comm, why = self._rccl_candidate(comm, pending)
-            pending = None
-            if comm is None and have_r:
-                self.transport_report["rccl"] = {"ok": False, "validation": why or "no communicator"}
-            if comm is not None:
-                self.comm = comm
-                self.engine.attach_comm(comm)
-        # DDP construction semantics: rank 0's parameters everywhere BEFORE the validations (they
-        # compare the ranks' parameters after replaying the same steps)
-        if x is not None or self.comm is not None or not self.transport_report:
-            self.broadcast_params(x)
-        if x is not None:
-            self.engine.attach_xgmi(x)
-            self.engine.set_schedule(C.SCHED_XGMI)
-            self.xgmi = x
-            self._use_graph_set("xgmi")
-            both = allreduce == "fastest" and have_r   # two candidates: time each beyond its first replay
-            ok, why, us = self._validate("xgmi", train, timed=both)
-            if not ok and "differ" in why:
-                # wrong sums, no timeout: retry with system-scope release / acquire fences around every
-                # stage flag (the ordering rules R1-R4 of xgmi_allreduce.hip assume a memory model the
-                # fences make explicit); graphs captured without them are dropped
-                if self.rank == 0:
-                    print(f"[xgmi] startup validation failed ({why}): retrying with fences", flush=True)
-                x.set_fences(True)
-                self._graph_sets["xgmi"] = {}
-                self._use_graph_set("xgmi")
-                ok, why2, us = self._validate("xgmi", train, timed=both)
-                why = why2 if ok else f"{why}; fenced: {why2}"
-            self.transport_report["xgmi"] = {"ok": ok, "validation": why, "us_per_step": us,
-                                             "ordering": x.ordering}
-            self.xgmi_validation = why
-            if not ok and self.rank == 0:
-                print(f"[xgmi] startup validation failed ({why})", flush=True)
-            self.engine.attach_xgmi(None)           # detached while RCCL is evaluated (re-attached below)
-            if not ok:
-                release_xgmi_comm(x, self.world)
-                x = self.xgmi = None
-            if ok and allreduce == "auto":
-                # validated on every rank (collective verdict): RCCL is not needed - every rank drops
-                # its (pending or deferred) communicator, nobody's bootstrap waits for a peer
-                if pending is not None:
-                    pending.cancel()
-                    self.transport_report["rccl"] = {"ok": None, "validation": "not needed: the xGMI "
-                                                     f"transport validated first (RCCL init {pending.status})"}
-                    pending = None
-                elif comm is not None:
-                    self.transport_report["rccl"] = {"ok": None, "validation": "not needed: the xGMI "
-                                                     "transport validated first"}
-                comm = None
-            elif allreduce in ("auto", "fastest") and comm is None and pending is not None:
-                comm, why = self._rccl_candidate(None, pending)   # xGMI failed (auto) / both timed
-                pending = None
-                if comm is None:
-                    self.transport_report["rccl"] = {"ok": False, "validation": why or "no communicator"}
-                else:
-                    self.comm = comm
-                    self.engine.attach_comm(comm)
-        want_r = comm is not None and allreduce in ("rccl", "auto", "fastest") and \
-            not (allreduce == "auto" and self.transport_report.get("xgmi", {}).get("ok"))
-        if want_r:
-            self.engine.set_schedule(C.SCHED_RCCL)
-            self._use_graph_set("rccl")
-            ok, why, us = self._validate("rccl", train, timed=x is not None)
-            self.transport_report["rccl"] = {"ok": ok, "validation": why, "us_per_step": us}
-        valid = {k: v["us_per_step"] for k, v in self.transport_report.items() if v.get("ok")}
-        self.allreduce_timings = {k: round(v["us_per_step"], 2) for k, v in self.transport_report.items()
-                                  if v.get("us_per_step") is not None}
-        if not valid:
-            msg = "; ".join(f"{k}: {v.get('validation')}" for k, v in self.transport_report.items())
-            hint = "" if have_r else " (no RCCL communicator: rerun with --allreduce rccl or auto)"
-            raise StartupValidationError(f"world size {self.world}: no gradient all-reduce passed its startup "
-                                         f"validation ({msg or 'no candidate'}){hint}", self.transport_report,
-                                         self.setup)
-        pick = min(valid, key=valid.get)
-        if pick == "xgmi":
-            if self.comm is not None and allreduce != "fastest":
-                self.engine.attach_comm(None)
-                self.comm = None
-            self.engine.attach_xgmi(x)
-            self.engine.set_schedule(C.SCHED_XGMI)
-        else:
-            if x is not None:
-                release_xgmi_comm(x, self.world)
-                x = self.xgmi = None
-            self.engine.set_schedule(C.SCHED_RCCL)
-        self._use_graph_set(pick)
-        self.allreduce = pick
-        # the all-reduced gradients (xGMI: the communicator's output buffer; the inputs are written
-        # to its input buffer instead of mstate.grad while it is attached)
-        self.grad_out = self.xgmi.grad_out if self.xgmi is not None else None
+        transport.Selection(self, comm, allreduce, two_buckets, probe_world1, train).run()
 
     def broadcast_params(self, x=None) -> None:
         """DDP construction (reference mnist_ddp.py:173): rank 0's parameters to every rank, over the
@@ -651,193 +451,11 @@ class FusedTrainer:
                 xgmi_broadcast_(x, self.ms.param, 0)
             elif self.comm is not None:
                 self.engine.broadcast_params(0)
-                self._wait_compute(rccl_watchdog_s(), "RCCL parameter broadcast")
+                transport.wait_compute(self, rccl_watchdog_s(), "RCCL parameter broadcast")
             else:
                 broadcast_(self.ms.param, 0)
             self.engine.refresh_shadows()
             torch.cuda.synchronize(self.device)
-
-    def _drain(self, timeout_s: float) -> bool:
-        """Both streams idle within ``timeout_s`` (events polled; never a blocking sync)."""
-        evs = []
-        for st in (self.compute, self.comm_stream):
-            ev = torch.cuda.Event()
-            ev.record(st)
-            evs.append(ev)
-        t0 = time.perf_counter()
-        while not all(ev.query() for ev in evs):
-            if time.perf_counter() - t0 > timeout_s:
-                return False
-            time.sleep(0.001)
-        return True
-
-    def _abort_rccl(self, hang: "TransportHang | None" = None) -> float:
-        """Drop the RCCL candidate: ncclCommAbort (RCCL's device-side waits return), release an
-        injected test stall, wait for the streams to drain.  Returns the seconds that took; re-raises
-        ``hang`` (fatal) when the streams do not drain - then something is stuck for good."""
-        t0 = time.perf_counter()
-        if self.comm is not None:
-            self.comm.abort()
-        if self._fault_stall:
-            self.engine.fault_release(int(self._fault_stream.cuda_stream))
-            self._fault_stall = False
-        if not self._drain(RCCL_DRAIN_S):
-            if hang is not None:
-                raise hang
-            raise TransportHang(f"rank {self.rank}: the streams did not drain within {RCCL_DRAIN_S:.0f} s of "
-                                "aborting the RCCL communicator")
-        return time.perf_counter() - t0
-
-    def _drop_rccl(self) -> None:
-        """After a failed RCCL candidate: the engine no longer holds the (aborted) communicator and
-        the graphs captured with its collectives are never replayed."""
-        self.engine.attach_comm(None)
-        self.comm = None
-        self._graph_sets.pop("rccl", None)
-
-    def _wait_compute(self, timeout_s: float, what: str) -> None:
-        """Host watchdog on the compute stream (every chunk and step joins the comm stream into it)."""
-        ev = torch.cuda.Event()
-        ev.record(self.compute)
-        t0 = time.perf_counter()
-        while not ev.query():
-            if time.perf_counter() - t0 > timeout_s:
-                raise TransportHang(f"rank {self.rank}: {what} did not complete within {timeout_s:.0f} s "
-                                    "(a collective is stuck on the device)")
-            time.sleep(0.0002)
-
-    # ------------------------------------------------------------------ startup validation
-    def _validate(self, name: str, train: MNISTData, timed: bool = True) -> tuple[bool, str, float | None]:
-        """Run the selected production schedule before training starts: the captured chunk graph of
-        ``graph_steps`` steps that training replays (cached for training; eager steps when graphs are
-        off), dropout off, on the live state, which is restored bit for bit afterwards.  Passes when
-        no rank timed out (xGMI: STARTUP_TIMEOUT_S stage waits, read from device memory so the cached
-        graph picks up the run timeout afterwards; RCCL: a host watchdog of ``rccl_watchdog_s()``)
-        and every rank holds the same parameters afterwards.  A stuck RCCL replay is aborted
-        (ncclCommAbort: RCCL's device-side waits return, the streams drain) and the candidate dropped
-        on every rank - only streams that do not drain after that raise TransportHang (fatal).  Then
-        (``timed``: two candidates) the chunk is replayed ``VALIDATE_TIMED`` more times and timed: the
-        transport's µs per step (max over ranks) is the "auto" choice's measure; a single candidate is
-        timed on its validation replay.  The verdict is collective and names every
-        failing rank.  Fault injection for tests: ``MNIST_AMD_FAULT=validate_delay:R:S`` holds rank
-        R's replay back S seconds; ``rccl_stall:R:S`` puts a device-side hold of up to S seconds in
-        front of rank R's first RCCL replay."""
-        from ..parallel.distributed import (RUN_TIMEOUT_S, STARTUP_TIMEOUT_S, _max_over_ranks, gather_strings,
-                                            params_fingerprint_equal)
-        _t0 = time.perf_counter()
-        ms, eng = self.ms, self.engine
-        n = self.graph_steps if self.use_graphs else 3
-        n = max(1, min(n, self.steps_per_epoch))
-        keys = ("param", "square_avg", "acc_delta", "state")
-        torch.cuda.synchronize(self.device)
-        snap = {k: getattr(ms, k).clone() for k in keys}
-        idx = torch.arange(n * self.B, dtype=torch.int64) % max(1, len(train))
-        delay = _fault_delay("validate_delay", self.rank)
-        rccl = name == "rccl"
-        # MNIST_AMD_FAULT=rccl_stall:R:S (tests): rank R's first RCCL replay sits behind a device-side
-        # hold of up to S seconds - a collective that never completes, as seen by the host watchdog
-        stall = _fault_delay("rccl_stall", self.rank) if rccl else 0.0
-        if self.xgmi is not None and not rccl:
-            self.xgmi.set_timeout_seconds(STARTUP_TIMEOUT_S)
-        why, us, result = "", None, None
-
-        def run_chunk():
-            eng.begin_epoch(self.seed, 0, 0, FLAG_NO_DROPOUT)
-            if stall and not self._fault_stall and not hung:
-                self._fault_stall = True
-                self._fault_stream = torch.cuda.Stream(device=self.device)
-                eng.fault_hold(stall)
-            if self.use_graphs:
-                eng.replay(self._graph(n, self.B))
-            else:
-                eng.train_steps(n, self.B, self.B)
-
-        def wait():
-            if rccl:
-                self._wait_compute(rccl_watchdog_s(), "RCCL schedule validation")
-            eng.synchronize()                        # raises on a stage / hand-off timeout
-
-        hung = False                                 # this rank's RCCL replay was stuck and aborted
-        try:
-            self.upload_indices(idx)
-            if self.use_graphs:
-                self._graph(n, self.B)               # captured (and cached) before the clock
-            torch.cuda.synchronize(self.device)
-            if delay:
-                time.sleep(delay)
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record(self.compute)
-            run_chunk()
-            ev1.record(self.compute)
-            wait()
-            us = ev0.elapsed_time(ev1) * 1000.0 / n
-            result = ms.param.cpu()                  # (host checks: no torch GPU kernel at startup)
-            if not torch.isfinite(result).all():
-                why = f"rank {self.rank}: non-finite parameters"
-        except TransportHang as e:
-            if not rccl:
-                raise
-            # a stuck RCCL replay is no longer fatal: abort the communicator, let the streams drain,
-            # and report the candidate as failed (the xGMI candidate, validated first, stays usable)
-            took = self._abort_rccl(e)
-            hung = True
-            why = (f"rank {self.rank}: replay stuck for {rccl_watchdog_s():.0f} s, communicator aborted "
-                   f"after {rccl_watchdog_s() + took:.1f} s")
-        except RuntimeError as e:
-            why = f"rank {self.rank}: {e} (after {time.perf_counter() - _t0:.1f} s)"
-        msgs = gather_strings(why, self.world)       # collective: every rank stops here together
-        why = "; ".join(m for m in msgs if m)
-        if why and rccl and not hung:                # a peer's replay failed: this communicator goes too
-            self._abort_rccl()
-            hung = True
-        if not why and self.world > 1 and not params_fingerprint_equal(result, world=self.world):
-            why = "parameters differ across ranks after the validation chunk"
-        if not why and not timed:
-            us = _max_over_ranks(us, world=self.world)
-        elif not why:
-            # timed replays of the same chunk (state need not be restored in between: the numbers do
-            # not matter, the schedule's time does)
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            try:
-                torch.cuda.synchronize(self.device)
-                ev0.record(self.compute)
-                for _ in range(VALIDATE_TIMED):
-                    run_chunk()
-                ev1.record(self.compute)
-                wait()
-                us = ev0.elapsed_time(ev1) * 1000.0 / (VALIDATE_TIMED * n)
-            except TransportHang as e:
-                if not rccl:
-                    raise
-                took = self._abort_rccl(e)
-                hung = True
-                why = (f"rank {self.rank}: timed replay stuck for {rccl_watchdog_s():.0f} s, communicator aborted "
-                       f"after {rccl_watchdog_s() + took:.1f} s")
-            except RuntimeError as e:
-                why = f"rank {self.rank}: timed replay: {e}"
-            why = "; ".join(m for m in gather_strings(why, self.world) if m)
-            if why and rccl and not hung:
-                self._abort_rccl()
-                hung = True
-            if not why:
-                us = _max_over_ranks(us, world=self.world)
-        with torch.no_grad():
-            for k in keys:
-                getattr(ms, k).copy_(snap[k])
-        torch.cuda.synchronize(self.device)
-        eng.refresh_shadows()
-        eng.reset_counters()                         # (an aborted chunk leaves the hand-offs unpaired)
-        if self.xgmi is not None and not rccl:
-            self.xgmi.set_timeout_seconds(RUN_TIMEOUT_S)
-        torch.cuda.synchronize(self.device)
-        self.setup.add(f"validate.{name}", time.perf_counter() - _t0)
-        if hung:
-            self._drop_rccl()
-        if why:
-            return False, why, None
-        how = f"graph replay of the {n}-step training chunk" if self.use_graphs else f"{n} eager steps"
-        clock = f"{VALIDATE_TIMED} timed replay(s)" if timed else "timed on the validation replay"
-        return True, f"ok ({how}, ranks bitwise equal, {clock})", us
 
     def reset_model(self, module) -> None:
         """Start over from ``module``'s parameters with fresh optimizer state (zero Adadelta
