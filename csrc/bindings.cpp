@@ -408,23 +408,26 @@ PYBIND11_MODULE(_C, m) {
     return d;
   }, py::arg("B"), py::arg("cus") = 256, "items, rounds and grid of input_grad at batch B (pure; no GPU needed)");
   m.def("input_grad", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t dx, int B,
-                         uintptr_t stream) {
+                         uintptr_t stream, int grid) {
     InputGradArgs a{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d), P<const float>(w1c),
                     P<float>(dx)};
-    launch_input_grad(a, B, S(stream));
+    if (grid < 0) throw py::value_error("input_grad: grid must not be negative");
+    launch_input_grad(a, B, S(stream), grid);
     check_launch();
-  }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("dx"), py::arg("B"), py::arg("stream"));
+  }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("dx"), py::arg("B"), py::arg("stream"),
+     py::arg("grid") = 0);
   m.def("input_grad_step", [](uintptr_t dyc, uintptr_t a1, uintptr_t w2d, uintptr_t w1c, uintptr_t x, uintptr_t x0,
                               uintptr_t x_next, float alpha, float eps, float lo, float hi, int B,
-                              uintptr_t stream, uintptr_t dx) {
+                              uintptr_t stream, uintptr_t dx, int grid) {
     InputGradStepArgs a{{P<const uint8_t>(dyc), P<const uint16_t>(a1), P<const uint16_t>(w2d), P<const float>(w1c),
                          P<float>(dx)},
                         P<const float>(x), P<const float>(x0), P<float>(x_next), alpha, eps, lo, hi};
-    launch_input_grad_step(a, B, S(stream));
+    if (grid < 0) throw py::value_error("input_grad_step: grid must not be negative");
+    launch_input_grad_step(a, B, S(stream), grid);
     check_launch();
   }, py::arg("dyc"), py::arg("a1"), py::arg("w2d"), py::arg("w1c"), py::arg("x"), py::arg("x0"), py::arg("x_next"),
      py::arg("alpha"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
-     py::arg("dx") = 0,
+     py::arg("dx") = 0, py::arg("grid") = 0,
      "input_grad with the projected-step epilogue: x_next = clamp(clamp(x + alpha sgn(dx), x0 -+ eps), lo, hi)");
   m.attr("PGD_L2_TINY") = PGD_L2_TINY;
   m.def("pgd_l2_step", [](uintptr_t dx, uintptr_t x, uintptr_t x0, uintptr_t x_next, float alpha, float eps,

@@ -225,7 +225,9 @@ inline InputGradPlan input_grad_plan(int B, int cus) {
   return p;
 }
 constexpr int INPUT_GRAD_MAX_B = 1 << 20;   // 32-bit item index
-void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s);
+// grid: 0 = the plan; a positive value only shrinks the planned grid (the tests' any-grid proof; no caller in
+// the package passes it); negative: std::invalid_argument
+void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s, int grid = 0);
 // The same kernel body with a projected-step epilogue (L-inf FGSM / PGD on the normalised image): the
 // thread that owns dx element e = s writes, instead of s,
 //   t = x[e] + alpha * sgn(s);  t = min(max(t, x0[e] - eps), x0[e] + eps);  x_next[e] = min(max(t, lo), hi)
@@ -238,7 +240,7 @@ struct InputGradStepArgs {
   float* x_next;              // fp32 [B][784]
   float alpha, eps, lo, hi;   // step size, radius, valid range: all in normalised units
 };
-void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s);
+void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s, int grid = 0);
 
 // L2 projected-gradient step (attack_step.hip; L2 PGD on the normalised image), one workgroup per image:
 //   n = sqrt(sum dx^2);  t = x + (alpha / max(n, TINY)) * dx;  d = t - x0;  m = sqrt(sum d^2)

@@ -263,19 +263,26 @@ static int input_grad_cus() {
   return cus;
 }
 
-void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s) {
-  if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("input_grad: batch size out of range");
-  if (!a.dyc || !a.a1 || !a.w2d || !a.w1c || !a.dx) throw std::runtime_error("input_grad: null argument");
+// the planned grid, or `grid` workgroups where that is fewer (0: the plan)
+static int input_grad_grid(int B, int grid) {
+  if (grid < 0) throw std::invalid_argument("input_grad: grid must not be negative");
   const InputGradPlan p = input_grad_plan(B, input_grad_cus());
-  hipLaunchKernelGGL(input_grad_kernel<IgStoreGrad>, dim3(p.grid), dim3(IG_THREADS), 0, s, a, B, IgStoreGrad{});
+  return grid > 0 && grid < p.grid ? grid : p.grid;
 }
 
-void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s) {
+void launch_input_grad(const InputGradArgs& a, int B, hipStream_t s, int grid) {
+  if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("input_grad: batch size out of range");
+  if (!a.dyc || !a.a1 || !a.w2d || !a.w1c || !a.dx) throw std::runtime_error("input_grad: null argument");
+  const int G = input_grad_grid(B, grid);
+  hipLaunchKernelGGL(input_grad_kernel<IgStoreGrad>, dim3(G), dim3(IG_THREADS), 0, s, a, B, IgStoreGrad{});
+}
+
+void launch_input_grad_step(const InputGradStepArgs& a, int B, hipStream_t s, int grid) {
   if (B < 1 || B > INPUT_GRAD_MAX_B) throw std::runtime_error("input_grad_step: batch size out of range");
   if (!a.g.dyc || !a.g.a1 || !a.g.w2d || !a.g.w1c || !a.x || !a.x0 || !a.x_next)
     throw std::runtime_error("input_grad_step: null argument");   // (g.dx is optional)
-  const InputGradPlan p = input_grad_plan(B, input_grad_cus());
-  hipLaunchKernelGGL(input_grad_kernel<IgProjectedStep>, dim3(p.grid), dim3(IG_THREADS), 0, s, a.g, B,
+  const int G = input_grad_grid(B, grid);
+  hipLaunchKernelGGL(input_grad_kernel<IgProjectedStep>, dim3(G), dim3(IG_THREADS), 0, s, a.g, B,
                      IgProjectedStep{a.x, a.x0, a.x_next, a.alpha, a.eps, a.lo, a.hi});
 }
 

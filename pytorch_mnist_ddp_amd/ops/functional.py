@@ -192,14 +192,23 @@ def conv_bwd(ms, data_u8: torch.Tensor, idx: torch.Tensor, buf: StepBuffers, gra
                   ada=_ada_args(ms, wt, advance_step) if form else None)
 
 
-def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None) -> torch.Tensor:
+def _grid_kw(name: str, grid: int) -> dict:
+    """The ``grid`` keyword of the two input_grad launches: absent for 0 (the plan), refused when negative."""
+    if grid < 0:
+        raise ValueError(f"{name}: grid must not be negative")
+    return {"grid": int(grid)} if grid else {}
+
+
+def input_grad(ms, buf: StepBuffers, out: torch.Tensor | None = None, grid: int = 0) -> torch.Tensor:
     """Gradient wrt the normalised input, float32 [B, 784], from one launch of ``input_grad.hip`` on
     what the conv backward reads (``buf.dyc`` after ``fc_bwd``, ``buf.a1``, the conv weights).  Every
-    element of ``out`` is written; it needs no zeroing."""
+    element of ``out`` is written; it needs no zeroing.  ``grid`` (the tests'): 0 = the planned grid; a
+    positive value only shrinks it - the same bits on any grid."""
     B = buf.B
+    kw = _grid_kw("input_grad", grid)
     out = _out_rows("input_grad", "out", out, B, buf.dyc.device)
     p, w = native.ptr, param_ptrs(ms)
-    _C().input_grad(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(out), B, _s())
+    _C().input_grad(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(out), B, _s(), **kw)
     return out.view(B, 784)
 
 
@@ -233,7 +242,7 @@ def _check_rows(name: str, expr: str, rows: int) -> None:
 
 def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
                     lo: float, hi: float, out: torch.Tensor | None = None,
-                    dx: torch.Tensor | None = None) -> torch.Tensor:
+                    dx: torch.Tensor | None = None, grid: int = 0) -> torch.Tensor:
     """One projected signed-gradient step on the normalised image from one launch of ``input_grad.hip``
     in its step form: with ``g`` what ``input_grad`` returns on the same buffers,
 
@@ -241,8 +250,9 @@ def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps
 
     elementwise in float32 (a NaN in ``g`` reaches ``out``).  ``x``, ``x0``, ``out``: float32 [B, 784];
     ``out`` may be ``x`` itself (in place) and is allocated when None.  ``dx`` (optional, float32
-    [B, 784], no overlap with the others) also receives ``g``."""
+    [B, 784], no overlap with the others) also receives ``g``.  ``grid``: as ``input_grad``'s."""
     B, dev = buf.B, buf.dyc.device
+    kw = _grid_kw("input_grad_step", grid)
     _f32_rows("input_grad_step", "x", x, B, dev)
     _f32_rows("input_grad_step", "x0", x0, B, dev)
     out = _out_rows("input_grad_step", "out", out, B, dev)
@@ -256,7 +266,7 @@ def input_grad_step(ms, buf: StepBuffers, x: torch.Tensor, x0: torch.Tensor, eps
         raise ValueError("input_grad_step: need eps >= 0, alpha >= 0 and lo <= hi")
     p, w = native.ptr, param_ptrs(ms)
     _C().input_grad_step(p(buf.dyc), p(buf.a1), w.w2d, w.c1w, p(x), p(x0), p(out), alpha, eps, lo, hi, B, _s(),
-                         dx=p(dx))
+                         dx=p(dx), **kw)
     return out.view(B, 784)
 
 

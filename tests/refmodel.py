@@ -716,6 +716,100 @@ def check_conv_reduce(slabs, c1rows, grad_scale, grads, name="conv_grad_reduce")
     return stats
 
 
+# ---- input_grad (csrc/kernels/input_grad.hip): the oracle, its comparator and the mutations that
+# tests/test_input_grad_oracle_cpu.py proves the comparator on
+IG_SENT_BITS = 0x7FC00000                     # what torch.full(.., nan) holds: the sentinel of dx and its guard row
+IG_MUTATIONS = ("da1_bf16", "relu_geq", "denormal_off", "halo_zero_1", "halo_zero_2", "halo_zero_3", "row25_dropped",
+                "pad_leak", "planes_swapped", "odd_by_even", "conv2_taps_transposed", "conv1_taps_transposed",
+                "prev_image_mask", "pixel_27_27_zeroed", "corner_scaled", "guard_row_written")
+
+
+def ig_ring() -> torch.Tensor:
+    """bool [28,28]: rows and columns 0, 1, 26, 27 - the 208 pixels that fewer than nine conv1 taps reach."""
+    m = torch.zeros(28, 28, dtype=torch.bool)
+    m[[0, 1, 26, 27], :] = True
+    m[:, [0, 1, 26, 27]] = True
+    return m
+
+
+def ig_support(py: int, px: int) -> torch.Tensor:
+    """bool [28,28]: the dx pixels that the one pooled record (py, px) can reach - its 2 x 2 window of dy, widened by
+    two rows and columns by each of the two 3 x 3 transposed convolutions."""
+    m = torch.zeros(28, 28, dtype=torch.bool)
+    m[2 * py:2 * py + 6, 2 * px:2 * px + 6] = True
+    return m
+
+
+def stage_input_grad(dy_bf16, w2_bf16, a1_bf16, w1c, dtype=F64, mut=None):
+    """input_grad on dense dy [B,64,24,24], the bf16 conv2 weight [64,32,3,3], the stored a1 NCHW [B,32,26,26] and the
+    fp32 conv1 weight [32,1,3,3]: dx [B,1,28,28] = conv_transpose2d(conv_transpose2d(dy, w2) * (a1 > 0), w1c).
+    da1 stays in ``dtype`` throughout (the kernel does not round it to bf16: its contract); the mask is the stored
+    a1, an operand, so the decision is exact and needs no margin.  ``mut``: one of IG_MUTATIONS that acts on the
+    dense operands (the CPU test's; ``planes_swapped`` / ``odd_by_even`` act on the records and
+    ``guard_row_written`` on the buffer, in that test's stand-in)."""
+    B = dy_bf16.shape[0]
+    dy, w2, w1 = dy_bf16.to(dtype), w2_bf16.to(dtype), w1c.to(dtype).reshape(32, 1, 3, 3)
+    if mut == "conv2_taps_transposed":
+        w2 = w2.transpose(2, 3)
+    if mut == "conv1_taps_transposed":
+        w1 = w1.transpose(2, 3)
+    if mut == "pad_leak":                     # a dy tile without its zero columns: column -1 of row y + 1 is (y, 23)
+        pad = F.pad(dy, (2, 2))
+        pad[:, :, 1:, 1] = dy[:, :, :-1, 23]
+        da1 = F.conv_transpose2d(pad, w2)[..., 2:28]
+    else:
+        da1 = F.conv_transpose2d(dy, w2)
+    a1 = a1_bf16.to(F32)
+    mask = a1 >= 0 if mut == "relu_geq" else a1 >= 2.0 ** -126 if mut == "denormal_off" else a1 > 0
+    if mut == "prev_image_mask":
+        mask = torch.roll(mask, 1, 0)
+    da1 = da1 * mask
+    if mut == "da1_bf16":
+        da1 = bf16_round(da1).to(dtype)
+    if mut == "row25_dropped":
+        da1[:, :, 25] = 0
+    dx = F.conv_transpose2d(da1, w1)
+    if mut in ("halo_zero_1", "halo_zero_2", "halo_zero_3"):       # strip s computes its 7 rows without da1 row 7 s - 2
+        y0 = 7 * int(mut[-1])
+        cut = da1.clone()
+        cut[:, :, y0 - 2] = 0
+        dx[:, :, y0:y0 + 7] = F.conv_transpose2d(cut, w1)[:, :, y0:y0 + 7]
+    if mut == "pixel_27_27_zeroed":
+        dx[B - 1, 0, 27, 27] = 0
+    if mut == "corner_scaled":
+        dx[B - 1, 0, 0, 0] *= 1.5
+    return dx
+
+
+def check_input_grad(dy, w2_bf16, a1_nchw, w1c, dx, guard=None, name="input_grad"):
+    """dx f32 [B,784] (or [B,1,28,28]) element by element, under the eps rule (f32_eps: 8 x max |torch fp32 on the
+    CPU - float64| on the same operands, not below 4 fp32 ulps of the largest reference value) taken over three
+    sets, each asserted: the whole launch; each image alone (images are independent in this kernel, and the hand case
+    gives them gradient scales of 1e-6 .. 1e2: one eps over the launch would be the largest image's); the border ring
+    alone.  ``guard``: the row after dx as it is after the launch - it must still hold the NaN sentinel's bits.
+    The per-image entry of the result is the image whose deviation / eps is largest."""
+    args = (dy, w2_bf16, a1_nchw, w1c)
+    r64, r32 = stage_input_grad(*args), stage_input_grad(*args, dtype=F32)
+    B = r64.shape[0]
+    dx = dx.reshape(B, 1, 28, 28)
+    stats = {}
+    eps, _ = f32_eps(r32, r64)
+    stats["dx"] = (assert_within(dx, r64, eps, f"{name} dx"), eps)
+    worst = (0.0, 0.0)
+    for b in range(B):
+        e, _ = f32_eps(r32[b], r64[b])
+        dev = assert_within(dx[b], r64[b], e, f"{name} dx image {b}")
+        if dev / max(e, 1e-300) >= worst[0] / max(worst[1], 1e-300):
+            worst = (dev, e)
+    stats["dx image"] = worst
+    ring = ig_ring()
+    e, _ = f32_eps(r32[..., ring], r64[..., ring])
+    stats["dx ring"] = (assert_within(dx[..., ring], r64[..., ring], e, f"{name} dx ring"), e)
+    if guard is not None:
+        assert (f32_bits(guard) == IG_SENT_BITS).all(), f"{name}: the guard row after dx was written"
+    return stats
+
+
 # ---- hand-made operands of the backward tests (shared by the CPU and the GPU test)
 BWD_STEP = 3
 FC_REAL_B, FC_HAND_B = (1, 5, 31, 32, 33, 127, 128), (1024, 1025, 2047, 2048, 2049)
@@ -774,6 +868,44 @@ def conv_hand_case(B: int):
     a1 = bf16_round(torch.randn(B, 26, 26, 32, generator=g).relu())
     imgs = forward_case(B)[0][:B]
     return dict(g=gr, code=code, a1=a1, imgs=imgs, x=normalize_u8(imgs).reshape(B, 784))
+
+
+# a1 edge values (bf16 bits), cycled over the 32 channels at each of IG_EDGE_AT in every image: -0.0 and +0.0 (mask
+# off), the smallest positive normal and two positive denormals (mask on: the kernel compares as int16 > 0), the
+# largest finite value (mask on; only the sign and zero-ness of a1 reach dx)
+IG_EDGE_BITS = (0x8000, 0x0000, 0x0080, 0x0001, 0x0040, 0x7F7F)
+# (row, column) of a1: an interior pixel, the four corners, both sides of the strip boundaries 6 | 7, 13 | 14, 20 | 21
+# (and the halo rows 5, 12, 19 above them), and the last row 25
+IG_EDGE_AT = ((12, 9), (0, 0), (0, 25), (25, 0), (25, 25), (5, 3), (6, 3), (7, 3), (12, 17), (13, 17), (14, 17),
+              (19, 24), (20, 24), (21, 24), (25, 13))
+IG_ZERO_IMAGE, IG_CORNER_IMAGE, IG_ORIGIN_IMAGE = 1, 2, 3      # the special images (B >= 5 only)
+
+
+@functools.lru_cache(maxsize=None)
+def input_grad_hand_case(B: int):
+    """conv_hand_case(B)'s dense records and a1 with, in addition: per-image gradient scales 1e2 .. 1e-6
+    (torch.logspace over the batch, the pgd_l2_step test's span, falling: the last image is the one a norm over the
+    launch sees least; image b's gradients are about 2e-3 x its scale); the
+    a1 edge values IG_EDGE_BITS at IG_EDGE_AT in every image; and, from B = 5 (a smaller batch has no room for them
+    beside an ordinary first and last image), image 1 all zero (every record byte 0), image 2 with the pooled corner
+    record (11, 11) alone and image 3 with record (0, 0) alone, whose dx is zero outside ig_support.  Returns g bf16
+    [B,9216], code [B,9216], a1 bf16 NHWC [B,26,26,32], scale [B]."""
+    h = conv_hand_case(B)
+    scale = torch.logspace(2, -6, B)
+    g = bf16_round(h["g"].float() * (B * scale.view(B, 1)))
+    code = h["code"].clone()
+    a1 = h["a1"].clone()
+    edge = torch.tensor(IG_EDGE_BITS * 6, dtype=torch.int32)[:32].to(torch.int16).view(torch.bfloat16)
+    for k, (y, x) in enumerate(IG_EDGE_AT):
+        a1[:, y, x, :] = torch.roll(edge, k)
+    if B >= 5:
+        g3, c3 = g.view(B, 64, 144), code.view(B, 64, 144)
+        g3[IG_ZERO_IMAGE], c3[IG_ZERO_IMAGE] = 0, 0
+        for b, pos in ((IG_CORNER_IMAGE, 143), (IG_ORIGIN_IMAGE, 0)):
+            keep = torch.zeros(144, dtype=torch.bool)
+            keep[pos] = True
+            g3[b, :, ~keep], c3[b, :, ~keep] = 0, 0
+    return dict(g=g, code=code, a1=a1, scale=scale)
 
 
 # ---------------------------------------------------------------- optimizer-stage oracle
