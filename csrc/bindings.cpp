@@ -43,6 +43,7 @@ void mnist::preload_all_kernels() {
   preload_smooth();
   preload_attr();
   preload_deepfool();
+  preload_apgd();
 }
 
 namespace {
@@ -535,6 +536,23 @@ PYBIND11_MODULE(_C, m) {
      py::arg("M"), py::arg("stream"),
      "one L2 DeepFool step per image from its ten gradient rows and losses: r_tot += the step to the nearest "
      "linearised boundary, x = rows = clamp(x0 + (1 + overshoot) r_tot, lo, hi); crossed / stuck images freeze");
+
+  // ---------------- Auto-PGD ----------------
+  m.def("apgd_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t x0, uintptr_t x, uintptr_t x_old, uintptr_t x_best,
+                        uintptr_t g_best, uintptr_t fstate, uintptr_t istate, float sign, float eps, float lo, float hi,
+                        bool l2, bool first, bool last, int window, int M, uintptr_t stream) {
+    ApgdStepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const float>(x0), P<float>(x), P<float>(x_old),
+                   P<float>(x_best), P<float>(g_best), P<float>(fstate), P<int32_t>(istate), sign, eps, lo, hi,
+                   first ? 1 : 0, last ? 1 : 0, window};
+    launch_apgd_step(a, M, l2, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("x0"), py::arg("x"), py::arg("x_old"), py::arg("x_best"),
+     py::arg("g_best"), py::arg("fstate"), py::arg("istate"), py::arg("sign"), py::arg("eps"), py::arg("lo"),
+     py::arg("hi"), py::arg("l2"), py::arg("first"), py::arg("last"), py::arg("window"), py::arg("M"),
+     py::arg("stream"),
+     "one Auto-PGD iteration per image: counters and best point, checkpoint (halve eta, restart from the best), "
+     "momentum step; fstate [M][4] = eta, loss_best, loss_prev, loss_check; istate [M][4] = n_up, reduced, iters, "
+     "restarted");
 
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")

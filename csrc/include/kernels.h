@@ -401,6 +401,40 @@ struct DeepfoolStepArgs {
 };
 void launch_deepfool_step(const DeepfoolStepArgs& a, int M, hipStream_t s);   // M in [1, DF_MAX_M], overshoot >= 0
 
+// ---------------- Auto-PGD (apgd.hip; Croce & Hein 2020) ----------------
+// One iteration's per-image update in one launch, one workgroup per image, fp32, no atomics: dx / loss_rows are the
+// gradient chain's outputs at the iterate x (input_grad's plain form, head_train's -log p_label).  With L = sign *
+// loss_rows[i] and g = sign * dx[i]: the counters and the best point are brought up to date (n_up += L > loss_prev;
+// L > loss_best: x_best = x, g_best = dx), a launch that closes a checkpoint window of k iterations halves eta and
+// restarts from (x_best, g_best) when 4 n_up <= 3 k or (reduced == 0 and loss_check >= loss_best), and the momentum
+// step z = Proj(src + step(eta, gs)); x = Proj(src + a (z - src) + (1 - a) (src - x_old)); x_old = src is made
+// (a = 0.75; first launch: a = 1, no x_old term).  The exact form, the NaN rules and the one deliberate difference
+// from the authors' code (the first comparison is against the start point's loss) are in apgd.hip.
+// PER-IMAGE SCALARS, two 16-byte records an image (both arrays 16-byte aligned):
+//   fstate[i] = {eta, loss_best, loss_prev, loss_check}   (fp32; the losses carry `sign`)
+//   istate[i] = {n_up, reduced, iters, restarted}         (int32; restarted: 1 when the last update started from
+//                                                          x_best, 0 when from x)
+// first: reads no record and no x_old / x_best / g_best, writes all of them.  last: only loss_prev, n_up and the best
+// point (loss_best, x_best, g_best) are brought up to date; x, x_old and the rest keep their values; window is
+// ignored.  Rows and records past M are untouched.
+struct ApgdStepArgs {
+  const float* dx;            // fp32 [M][784] d NLL / d x at the iterate
+  const float* loss_rows;     // [M] -log p_label at the iterate
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* x;                   // fp32 [M][784] the iterate (the xin of the next chain run)
+  float* x_old;               // fp32 [M][784] the point the last update started from
+  float* x_best;              // fp32 [M][784] the point of the highest sign * loss so far
+  float* g_best;              // fp32 [M][784] its dx row, stored raw (without sign)
+  float* fstate;              // [M][4]
+  int32_t* istate;            // [M][4]
+  float sign;                 // +1 untargeted (ascent), -1 targeted (the labels' NLL is descended)
+  float eps, lo, hi;          // radius (of the norm), valid range: normalised units
+  int first, last;            // flags: launch 0 / the launch after the last update
+  int window;                 // k > 0: this launch closes a checkpoint window of k iterations; else 0
+};
+// M in [1, INPUT_GRAD_MAX_B], eps >= 0, sign +-1, window >= 0, not first and last at once; l2: the L2 form
+void launch_apgd_step(const ApgdStepArgs& a, int M, bool l2, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -475,6 +509,7 @@ void preload_adv_train();
 void preload_smooth();
 void preload_attr();
 void preload_deepfool();
+void preload_apgd();
 void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

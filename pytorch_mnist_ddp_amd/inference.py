@@ -30,6 +30,8 @@ in eval mode (where noise is drawn: the same distribution, not the same bits):
 * ``adversarial`` / ``robust_evaluate`` (L-inf or L2 FGSM / PGD, untargeted or targeted; ``eps`` and ``step_size`` in
   pixel units on the [0, 1] scale): ``ops.attack.fused_adversarial`` / ``reference_adversarial``; the returned
   log-probabilities are the predictor's own forward (above) of the adversarial images;
+* ``auto_pgd`` / ``robust_evaluate_apgd`` (Auto-PGD, Croce & Hein 2020: PGD without a step size to tune; the same
+  norms, units and targeted form): ``ops.apgd.fused_auto_pgd`` / ``reference_auto_pgd``;
 * ``smoothed_counts`` / ``certify`` (randomized smoothing: the class counts of Gaussian-noised copies of an image and
   the certified L2 radius they give; ``sigma`` in pixel units): ``ops.smooth.fused_smooth_counts`` / ``torch.randn``
   over the reference forward; the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path;
@@ -52,8 +54,9 @@ import torch.nn.functional as F
 from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist  # noqa: F401
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
-from .ops.functional import (DF_CLASSES, PGD_L2_TINY, attr_path_reference, attr_reduce_reference,
-                             deepfool_step_reference, pgd_l2_step_reference)
+from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, PGD_L2_TINY, apgd_checkpoints, apgd_step_reference,
+                             attr_path_reference, attr_reduce_reference, deepfool_step_reference,
+                             pgd_l2_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -100,6 +103,36 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
                 t = torch.min(torch.max(t, x0 - eps), x0 + eps)
                 x_adv = t.clamp(lo, hi)
     return x_adv
+
+
+def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int, lo: float,
+                       hi: float, x_init: torch.Tensor | None = None, norm: str = "linf", targeted: bool = False):
+    """``ops.apgd.fused_auto_pgd`` in torch float32 on any device: the same ``steps + 1`` rounds - the per-row NLL of
+    ``labels`` and its gradient by autograd over ``Net.forward_reference`` in eval mode (no dropout; the net's mode
+    is restored afterwards), then ``apgd_step_reference`` with the same ``first`` / ``last`` flags and the windows
+    of ``apgd_checkpoints``.  Same arguments (float32 [B, 784] normalised images, normalised units), same return:
+    ``(x_best [B, 784], loss_best [B])``, the loss as the NLL of ``labels``.  The CPU / fp32 path of
+    ``Predictor.auto_pgd`` and the reference of its GPU tests."""
+    if steps < 1:
+        raise ValueError("reference_auto_pgd: steps must be at least 1")
+    B, steps = x0.shape[0], int(steps)
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(x0.device)
+    window = dict(apgd_checkpoints(steps))
+    sign = -1 if targeted else 1
+    state = ((x0 if x_init is None else x_init.detach().reshape(B, 784).to(torch.float32)).clone(),
+             None, None, None, None, None)
+    with _eval_mode(net):
+        for j in range(steps + 1):
+            xg = state[0].clone().requires_grad_()
+            with torch.enable_grad():
+                lp = net.forward_reference(xg.view(B, 1, 28, 28))
+                g, = torch.autograd.grad(F.nll_loss(lp, y, reduction='sum'), xg)
+            loss_rows = F.nll_loss(lp.detach(), y, reduction='none')
+            state = apgd_step_reference(g, loss_rows, x0, *state, sign, eps, lo, hi, norm=norm, first=j == 0,
+                                        last=j == steps, window=window.get(j, 0))
+    loss_best = state[4][:, APGD_LOSS_BEST]
+    return state[2], (-loss_best if targeted else loss_best.clone())
 
 
 ATTRIBUTION_METHODS = ("integrated_gradients", "smoothgrad")
@@ -227,6 +260,22 @@ def adversarial_units(eps: float, steps: int, step_size: float | None):
     return eps / MNIST_STD, step_size / MNIST_STD, PIXEL_LO, PIXEL_HI
 
 
+def _random_start(x0: torch.Tensor, eps_n: float, lo: float, hi: float, norm: str, generator, device) -> torch.Tensor:
+    """The random start of ``Predictor.adversarial`` / ``auto_pgd`` around the float32 [B, 784] rows ``x0``, drawn
+    with torch from ``generator`` (on its device, or on ``device`` without one) - L-inf: ``x0 + U(-eps, eps)``; L2:
+    uniform in the ball (a normal direction scaled to radius ``eps * u^(1/784)``) - clamped to [lo, hi]."""
+    B = x0.shape[0]
+    draw = dict(generator=generator, dtype=torch.float32,
+                device=generator.device if generator is not None else device)
+    if norm == "linf":
+        u = torch.rand(B, 784, **draw).to(device)
+        return (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
+    g = torch.randn(B, 784, **draw).to(device)
+    u = torch.rand(B, 1, **draw).to(device)
+    radius = eps_n * u.pow(1.0 / 784.0)
+    return (x0 + g * (radius / g.square().sum(dim=1, keepdim=True).sqrt().clamp_min(PGD_L2_TINY))).clamp_(lo, hi)
+
+
 class Predictor:
     def __init__(self, net: Net, dtype: str = "bf16"):
         if dtype not in ("bf16", "fp32"):
@@ -341,19 +390,7 @@ class Predictor:
         else:
             labels = self._labels("adversarial", labels, B, check_range=True)
         eps_n, alpha_n, lo, hi = adversarial_units(eps, steps, step_size)
-        x_init = None
-        if random_start:
-            draw = dict(generator=generator, dtype=torch.float32,
-                        device=generator.device if generator is not None else self.device)
-            if norm == "linf":
-                u = torch.rand(B, 784, **draw).to(self.device)
-                x_init = (x0 + (2.0 * u - 1.0) * eps_n).clamp_(lo, hi)
-            else:
-                g = torch.randn(B, 784, **draw).to(self.device)
-                u = torch.rand(B, 1, **draw).to(self.device)
-                radius = eps_n * u.pow(1.0 / 784.0)
-                x_init = (x0 + g * (radius / g.square().sum(dim=1, keepdim=True).sqrt().clamp_min(PGD_L2_TINY))
-                          ).clamp_(lo, hi)
+        x_init = _random_start(x0, eps_n, lo, hi, norm, generator, self.device) if random_start else None
         if self.native:
             from .ops.attack import fused_adversarial
             x_adv = fused_adversarial(self.net, x0, labels, eps_n, int(steps), alpha_n, lo, hi, x_init,
@@ -382,6 +419,88 @@ class Predictor:
         for i in range(0, n, batch_size):
             y = lab[i:i + batch_size]
             _, lp = self.adversarial(images_u8[i:i + batch_size], y, eps, steps, step_size, norm=norm)
+            loss += F.nll_loss(lp, y, reduction='none').double().sum()
+            hits += (lp.argmax(dim=1) == y).sum()
+        return float(loss.item()), int(hits.item()), n
+
+    def auto_pgd(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1, steps: int = 100,
+                 norm: str = "linf", targeted: bool = False, random_start: bool = False, restarts: int = 1,
+                 generator=None):
+        """(x_adv, log_probs, loss_best): Auto-PGD (Croce & Hein 2020, the gradient attack of AutoAttack) adversarial
+        examples of ``x`` - PGD with a momentum step, a per-image step size that starts at ``2 eps`` and is halved at
+        scheduled checkpoints when the loss stops rising, and a restart from the best point found so far; there is
+        no step size to choose.  ``x_adv``: float32 [B,1,28,28] in NORMALISED units, the point of the highest loss
+        among the ``steps + 1`` iterates (``targeted``: the lowest), inside both the ``eps`` ball around ``x`` and
+        the valid pixel range [0, 1]; ``log_probs``: the predictor's own float32 [B,10] forward of ``x_adv``;
+        ``loss_best``: float32 [B], the NLL of ``labels`` at ``x_adv`` as the attack's own forward computed it.
+
+        Whether an image was broken is read from ``log_probs`` (``log_probs.argmax(1) != labels``): the attack keeps
+        the highest-loss point, it has no arg-max of the iterates and so does not keep "the first misclassified
+        point" apart as the authors' code does; the loss used is the NLL (cross-entropy), not the DLR loss.
+
+        ``norm``, ``eps`` (pixel units on the [0, 1] scale), ``labels`` (None: the class predicted on the clean
+        input), ``targeted`` (``labels`` required: the classes to reach, their NLL is descended), ``random_start``
+        and ``generator``: as ``adversarial``, the same draw.  ``restarts`` > 1 (needs ``random_start``): that many
+        runs from consecutive draws; per image the run with the highest ``loss_best`` (``targeted``: the lowest) is
+        kept, the first of equals.  Inference semantics as ``input_gradient``: no dropout; the net's mode, dropout
+        modules, parameters and gradients are untouched.  GPU with ``dtype="bf16"``: the native loop
+        ``ops.apgd.fused_auto_pgd``; CPU, or ``dtype="fp32"``: ``reference_auto_pgd``.  ``x``: uint8 [B,28,28] /
+        [B,784] images or float [B,1,28,28] already-normalised input."""
+        B = self._check_input(x)
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"auto_pgd: norm must be 'linf' or 'l2', got {norm!r}")
+        if targeted and labels is None:
+            raise ValueError("auto_pgd: a targeted attack needs labels (the target classes)")
+        if not eps >= 0:
+            raise ValueError(f"auto_pgd: eps must be >= 0, got {eps}")
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"auto_pgd: steps must be a positive integer, got {steps}")
+        if isinstance(restarts, bool) or restarts != int(restarts) or restarts < 1:
+            raise ValueError(f"auto_pgd: restarts must be a positive integer, got {restarts}")
+        if restarts > 1 and not random_start:
+            raise ValueError("auto_pgd: restarts > 1 needs random_start (every run would be the same)")
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels("auto_pgd", labels, B, check_range=True)
+        eps_n, _, lo, hi = adversarial_units(eps, int(steps), None)
+        if self.native:
+            from .ops.apgd import fused_auto_pgd as attack
+        else:
+            attack = reference_auto_pgd
+        x_adv = loss_best = None
+        for _ in range(int(restarts)):
+            x_init = _random_start(x0, eps_n, lo, hi, norm, generator, self.device) if random_start else None
+            xr, lr = attack(self.net, x0, labels, eps_n, int(steps), lo, hi, x_init, norm=norm, targeted=targeted)
+            if x_adv is None:
+                x_adv, loss_best = xr, lr
+            else:
+                better = (lr < loss_best) if targeted else (lr > loss_best)
+                x_adv = torch.where(better[:, None], xr, x_adv)
+                loss_best = torch.where(better, lr, loss_best)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        return x_adv, self._forward(x_adv)[0], loss_best
+
+    def robust_evaluate_apgd(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
+                             batch_size: int = 1000, norm: str = "linf", restarts: int = 1, generator=None):
+        """(loss_sum, correct, n) as ``robust_evaluate``, with Auto-PGD as the attack: the images after an untargeted
+        ``auto_pgd`` against their true labels, ``batch_size`` images at a time; ``restarts`` > 1: that many runs
+        from random starts drawn from ``generator``, else one run from the clean image.  There is no step size."""
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"robust_evaluate_apgd: norm must be 'linf' or 'l2', got {norm!r}")
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("robust_evaluate_apgd: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("robust_evaluate_apgd: batch_size must be positive")
+        lab = labels.long().to(self.device)
+        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        hits = torch.zeros((), dtype=torch.int64, device=self.device)
+        for i in range(0, n, batch_size):
+            y = lab[i:i + batch_size]
+            _, lp, _ = self.auto_pgd(images_u8[i:i + batch_size], y, eps, steps, norm=norm,
+                                     random_start=restarts > 1, restarts=restarts, generator=generator)
             loss += F.nll_loss(lp, y, reduction='none').double().sum()
             hits += (lp.argmax(dim=1) == y).sum()
         return float(loss.item()), int(hits.item()), n
@@ -636,6 +755,16 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack step in pixel units (default: E for one step, 2.5 * E / K otherwise)')
     ap.add_argument('--attack-norm', choices=('linf', 'l2'), default='linf',
                     help='norm of the attack radius E and of its steps (default: linf)')
+    ap.add_argument('--apgd-eps', type=float, default=None, metavar='E',
+                    help='also report loss and accuracy under an Auto-PGD attack (no step size to tune) of radius E, '
+                         'in pixel units on the [0, 1] scale (default: off)')
+    ap.add_argument('--apgd-steps', type=int, default=100, metavar='N', help='Auto-PGD iterations (default: 100)')
+    ap.add_argument('--apgd-norm', choices=('linf', 'l2'), default='linf',
+                    help='norm of the Auto-PGD radius E (default: linf)')
+    ap.add_argument('--apgd-restarts', type=int, default=1, metavar='R',
+                    help='Auto-PGD runs per image; more than one: each from a random start (default: 1, from the '
+                         'clean image)')
+    ap.add_argument('--apgd-seed', type=int, default=0, help='seed of the random starts (default: 0)')
     ap.add_argument('--certify-sigma', type=float, default=None, metavar='S',
                     help='also report certified accuracy under randomized smoothing with Gaussian noise of standard '
                          'deviation S, in pixel units on the [0, 1] scale (default: off)')
@@ -682,6 +811,12 @@ def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, 
     """The ``Test set:`` line's figures (``utils.logging.test_line``) for the attacked split."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
     return f"Adversarial set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}): {figures}"
+
+
+def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: int, n: int, norm: str = "linf") -> str:
+    """The ``Auto-PGD set`` line of ``mnist_predict.py --apgd-eps``, in the number formats of ``adversarial_line``."""
+    figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
+    return f"Auto-PGD set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}, restarts={restarts}): {figures}"
 
 
 def minimum_norm_stats(radii: torch.Tensor, found: torch.Tensor, clean: torch.Tensor, at=()):
@@ -796,6 +931,15 @@ def predict_main(argv=None) -> int:
                       min_norm_count=m, min_norm_found=stats[0], min_norm_median_radius=stats[1],
                       min_norm_mean_radius=stats[2],
                       min_norm_accuracy_at={f"{r:g}": c for r, c in zip(args.min_norm_radii, stats[3])})
+    if args.apgd_eps is not None:
+        gen = torch.Generator().manual_seed(args.apgd_seed) if args.apgd_restarts > 1 else None
+        ap_loss, ap_correct, _ = predictor.robust_evaluate_apgd(images, data.targets, args.apgd_eps, args.apgd_steps,
+                                                                args.batch_size, norm=args.apgd_norm,
+                                                                restarts=args.apgd_restarts, generator=gen)
+        print(auto_pgd_line(args.apgd_eps, args.apgd_steps, args.apgd_restarts, ap_loss / n, ap_correct, n,
+                            args.apgd_norm))
+        record.update(apgd_eps=args.apgd_eps, apgd_steps=args.apgd_steps, apgd_norm=args.apgd_norm,
+                      apgd_restarts=args.apgd_restarts, apgd_loss=ap_loss / n, apgd_correct=ap_correct)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

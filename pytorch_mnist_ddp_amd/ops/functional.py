@@ -719,6 +719,163 @@ def deepfool_step(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0
                        float(overshoot), float(lo), float(hi), M, _s())
 
 
+APGD_MOMENTUM = 0.75                # a of the momentum step after the first update (csrc/kernels/apgd.hip)
+APGD_RHO = (3, 4)                   # a window of k iterations oscillates when 4 n_up <= 3 k (rho = 0.75, in integers)
+APGD_MAX_M = 1 << 20                # most images one apgd_step launch takes (kernels.h INPUT_GRAD_MAX_B)
+# columns of the per-image records (kernels.h ApgdStepArgs)
+APGD_ETA, APGD_LOSS_BEST, APGD_LOSS_PREV, APGD_LOSS_CHECK = 0, 1, 2, 3        # fstate, float32 [M, 4]
+APGD_N_UP, APGD_REDUCED, APGD_ITERS, APGD_RESTARTED = 0, 1, 2, 3              # istate, int32 [M, 4]
+
+
+def apgd_checkpoints(steps: int) -> tuple:
+    """The checkpoint schedule of Auto-PGD (Croce & Hein 2020, the authors' code) for ``steps`` iterations: a tuple
+    of ``(iteration, k)`` - after ``iteration`` updates (1-based) a window of ``k`` iterations closes.  k starts at
+    max(int(0.22 N), 1) and shrinks by max(int(0.03 N), 1) a window, not below max(int(0.06 N), 1); the last
+    checkpoint is <= N.  N = 100: iterations 22, 41, 57, 70, 80, 87, 93, 99."""
+    n = int(steps)
+    if n < 1:
+        raise ValueError("apgd_checkpoints: steps must be at least 1")
+    k, k_min, decr = max(int(0.22 * n), 1), max(int(0.06 * n), 1), max(int(0.03 * n), 1)
+    out, at = [], 0
+    while at + k <= n:
+        at += k
+        out.append((at, k))
+        k = max(k - decr, k_min)
+    return tuple(out)
+
+
+def apgd_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: torch.Tensor,
+                        x_old: torch.Tensor | None, x_best: torch.Tensor | None, g_best: torch.Tensor | None,
+                        fstate: torch.Tensor | None, istate: torch.Tensor | None, sign: float, eps: float,
+                        lo: float, hi: float, norm: str = "linf", first: bool = False, last: bool = False,
+                        window: int = 0):
+    """``apgd_step`` in torch ops on any device, in the dtype of ``dx`` (float32: the CPU / fp32 path of
+    ``Predictor.auto_pgd``; float64: the oracle of the kernel's tests).  Same operands - ``dx``, ``x0``, ``x``,
+    ``x_old``, ``x_best``, ``g_best`` [M, 784], ``loss_rows`` [M], ``fstate`` [M, 4] (eta, loss_best, loss_prev,
+    loss_check), ``istate`` integers [M, 4] (n_up, reduced, iters, restarted) - none of them modified; returns the new
+    ``(x, x_old, x_best, g_best, fstate, istate)``.  With ``first`` the last five inputs are not read (None will do).
+    Per image, with L = sign * loss and g = sign * dx:
+
+        first:   eta = 2 eps; loss_best = loss_prev = loss_check = L; x_best = x; g_best = dx; n_up = 0; reduced = 1;
+                 iters = 0; restarted = 0; a = 1; (src, gs) = (x, g)
+        else:    n_up += L > loss_prev; loss_prev = L;  L > loss_best: loss_best = L, x_best = x, g_best = dx
+                 last: stop here
+                 (src, gs) = (x, g); a = 0.75; restarted = 0
+                 window k > 0: r = 4 n_up <= 3 k or (reduced == 0 and loss_check >= loss_best); reduced = r;
+                               loss_check = loss_best; n_up = 0; r: eta /= 2, (src, gs) = (x_best, sign g_best),
+                               restarted = 1
+        linf:    z = C(B(src + eta sgn(gs)));  x = C(B((src + a (z - src)) + (1 - a) (src - x_old)))
+        l2:      z = P(src + (eta / max(|gs|, TINY)) gs);  x = P((src + a (z - src)) + (1 - a) (src - x_old))
+                 B(t) = min(max(t, x0 - eps), x0 + eps); C = clamp(., lo, hi); P(t) = C(x0 + d min(1, eps / max(|d|, TINY)))
+        x_old = src; iters += 1                   (first: no (1 - a) term)
+
+    ``eps``, ``lo`` and ``hi`` are rounded to float32 first, as the kernel receives them."""
+    import numpy as np
+    if norm not in ("linf", "l2"):
+        raise ValueError(f"apgd_step_reference: norm must be 'linf' or 'l2', got {norm!r}")
+    if sign not in (1, -1) or (first and last) or window < 0:
+        raise ValueError("apgd_step_reference: sign is +1 or -1, window >= 0, and a launch is not first and last")
+    dt, dev = dx.dtype, dx.device
+    M = dx.shape[0]
+    eps, lo, hi = (float(np.float32(v)) for v in (eps, lo, hi))
+    tiny = float(np.float32(PGD_L2_TINY))
+    sgn = float(sign)
+    x0, x = x0.reshape(M, 784).to(dt), x.reshape(M, 784).to(dt)
+    L = sgn * loss_rows.reshape(M).to(dt)
+    i32 = dict(dtype=torch.int32, device=dev)
+    if first:
+        eta = torch.full((M,), 2.0 * eps, dtype=dt, device=dev)
+        loss_best, loss_prev, loss_check = L.clone(), L.clone(), L.clone()
+        n_up, reduced, iters = torch.zeros(M, **i32), torch.ones(M, **i32), torch.zeros(M, **i32)
+        restarted = torch.zeros(M, **i32)
+        xb, gb = x.clone(), dx.clone()
+        improved = torch.ones(M, dtype=torch.bool, device=dev)
+    else:
+        eta, loss_best, loss_prev, loss_check = fstate.reshape(M, 4).to(dt).unbind(dim=1)
+        n_up, reduced, iters, restarted = istate.reshape(M, 4).to(torch.int32).unbind(dim=1)
+        n_up = n_up + (L > loss_prev).to(torch.int32)
+        loss_prev = L
+        improved = L > loss_best
+        loss_best = torch.where(improved, L, loss_best)
+        xb = torch.where(improved[:, None], x, x_best.reshape(M, 784).to(dt))
+        gb = torch.where(improved[:, None], dx, g_best.reshape(M, 784).to(dt))
+    pack = lambda: (torch.stack((eta, loss_best, loss_prev, loss_check), dim=1),             # noqa: E731
+                    torch.stack((n_up, reduced, iters, restarted), dim=1))
+    if last:
+        return (x.clone(), x_old.reshape(M, 784).to(dt).clone(), xb, gb, *pack())
+    restart = torch.zeros(M, dtype=torch.bool, device=dev)
+    if not first:
+        restarted = torch.zeros(M, **i32)
+        if window > 0:
+            osc = APGD_RHO[1] * n_up <= APGD_RHO[0] * int(window)
+            stall = (reduced == 0) & (loss_check >= loss_best)
+            restart = osc | stall
+            restarted = reduced = restart.to(torch.int32)
+            loss_check = loss_best.clone()
+            n_up = torch.zeros(M, **i32)
+            eta = torch.where(restart, 0.5 * eta, eta)
+    src = torch.where(restart[:, None], xb, x)
+    gs = sgn * torch.where(restart[:, None], gb, dx)
+    a = 1.0 if first else APGD_MOMENTUM
+    e = eta[:, None]
+
+    def mix(z):
+        t = src + a * (z - src)
+        return t if first else t + (1.0 - a) * (src - x_old.reshape(M, 784).to(dt))
+
+    if norm == "linf":
+        el, eh = x0 - eps, x0 + eps
+        box = lambda t: torch.min(torch.max(t, el), eh).clamp(lo, hi)                            # noqa: E731
+        sg = torch.where(gs != gs, gs, torch.sign(gs))       # a NaN gradient stays a NaN
+        x_new = box(mix(box(src + e * sg)))
+    else:
+        def proj(t):
+            d = t - x0
+            m = d.square().sum(dim=1, keepdim=True).sqrt()
+            return (x0 + d * (eps / m.clamp_min(tiny)).clamp_max(1.0)).clamp(lo, hi)
+        n = gs.square().sum(dim=1, keepdim=True).sqrt()
+        x_new = proj(mix(proj(src + (e / n.clamp_min(tiny)) * gs)))
+    iters = iters + 1
+    return (x_new, src, xb, gb, *pack())
+
+
+def apgd_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: torch.Tensor, x_old: torch.Tensor,
+              x_best: torch.Tensor, g_best: torch.Tensor, fstate: torch.Tensor, istate: torch.Tensor, sign: float,
+              eps: float, lo: float, hi: float, norm: str = "linf", first: bool = False, last: bool = False,
+              window: int = 0, M: int | None = None) -> None:
+    """One Auto-PGD iteration per image (``csrc/kernels/apgd.hip``), one launch, in place: from the gradient rows
+    ``dx`` (float32 [>= M, 784], what ``input_grad`` wrote) and losses ``loss_rows`` (float32 [>= M], what
+    ``head_train`` stored) at the iterate ``x``, and the clean images ``x0``, the update of ``apgd_step_reference`` on
+    ``x``, ``x_old``, ``x_best``, ``g_best`` (float32 [>= M, 784]), ``fstate`` (float32 [>= M, 4]) and ``istate``
+    (int32 [>= M, 4]).  float32 throughout, the L2 sums a fixed tree: the same operands give the same bits.
+    ``first``: no state is read, all of it is written; ``last``: only loss_prev, n_up and the best point are brought
+    up to date; ``window``: k > 0 when this launch closes a checkpoint window of k iterations.  ``M``: the images of
+    the launch (default ``x.shape[0]``); nothing past M is touched."""
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("apgd_step: x must be a float32 [M, 784] tensor on the GPU")
+    if norm not in ("linf", "l2"):
+        raise ValueError(f"apgd_step: norm must be 'linf' or 'l2', got {norm!r}")
+    dev = x.device
+    M = int(x.shape[0] if M is None else M)
+    if M < 1 or M > APGD_MAX_M:
+        raise ValueError(f"apgd_step: M = {M} images must be in [1, APGD_MAX_M = {APGD_MAX_M}] a launch")
+    rows = (("dx", dx), ("x0", x0), ("x", x), ("x_old", x_old), ("x_best", x_best), ("g_best", g_best))
+    for what, t in rows:
+        _f32_rows("apgd_step", what, t, M, dev, at_least="M")
+    _df_vec("apgd_step", "loss_rows", loss_rows, torch.float32, M, dev, "M")
+    _df_vec("apgd_step", "fstate", fstate, torch.float32, 4 * M, dev, "4 M")
+    _df_vec("apgd_step", "istate", istate, torch.int32, 4 * M, dev, "4 M")
+    ptrs = [t.data_ptr() for _, t in rows]
+    if len(set(ptrs)) != len(ptrs):
+        raise ValueError("apgd_step: dx, x0, x, x_old, x_best and g_best must be six buffers")
+    if not (eps >= 0 and lo <= hi) or sign not in (1, -1) or int(window) < 0 or (first and last):
+        raise ValueError("apgd_step: need eps >= 0, lo <= hi, sign +1 or -1, window >= 0, and not first and last")
+    p = native.ptr
+    _C().apgd_step(p(dx), p(loss_rows), p(x0), p(x), p(x_old), p(x_best), p(g_best), p(fstate), p(istate),
+                   float(sign), float(eps), float(lo), float(hi), norm == "l2", bool(first), bool(last), int(window),
+                   M, _s())
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
