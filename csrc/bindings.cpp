@@ -44,6 +44,7 @@ void mnist::preload_all_kernels() {
   preload_attr();
   preload_deepfool();
   preload_apgd();
+  preload_square();
 }
 
 namespace {
@@ -553,6 +554,35 @@ PYBIND11_MODULE(_C, m) {
      "one Auto-PGD iteration per image: counters and best point, checkpoint (halve eta, restart from the best), "
      "momentum step; fstate [M][4] = eta, loss_best, loss_prev, loss_check; istate [M][4] = n_up, reduced, iters, "
      "restarted");
+
+  // ---------------- Square Attack ----------------
+  m.attr("SQUARE_PHILOX_DOMAIN") = SQUARE_PHILOX_DOMAIN;
+  m.def("square_init", [](uintptr_t x0, uintptr_t x_cand, float eps, float lo, float hi, uint64_t seed,
+                          int64_t id_base, int M, uintptr_t stream) {
+    if (id_base < 0 || id_base > 0xFFFFFFFFll) throw std::runtime_error("square_init: id_base must fit 32 bits");
+    SquareInitArgs a{P<const float>(x0), P<float>(x_cand), eps, lo, hi, seed, (uint32_t)id_base};
+    launch_square_init(a, M, S(stream));
+    check_launch();
+  }, py::arg("x0"), py::arg("x_cand"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("seed"),
+     py::arg("id_base"), py::arg("M"), py::arg("stream"),
+     "x_cand = clamp(x0 +- eps, lo, hi) in vertical stripes drawn from Philox: the candidate of query 0 of a Square "
+     "Attack");
+  m.def("square_step", [](uintptr_t logp, uintptr_t y, uintptr_t x0, uintptr_t x_best, uintptr_t x_cand,
+                          uintptr_t state, float eps, float lo, float hi, uint64_t seed, int64_t q, int64_t id_base,
+                          int side, bool first, bool last, bool targeted, int M, uintptr_t stream) {
+    if (q < 0 || q > 0xFFFFFFFFll || id_base < 0 || id_base > 0xFFFFFFFFll)
+      throw std::runtime_error("square_step: q and id_base must fit 32 bits");
+    SquareStepArgs a{P<const float>(logp), P<const int32_t>(y), P<const float>(x0), P<float>(x_best), P<float>(x_cand),
+                     P<void>(state), eps, lo, hi, seed, (uint32_t)q, (uint32_t)id_base, side, first ? 1 : 0,
+                     last ? 1 : 0, targeted ? 1 : 0};
+    launch_square_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("logp"), py::arg("y"), py::arg("x0"), py::arg("x_best"), py::arg("x_cand"), py::arg("state"),
+     py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("seed"), py::arg("q"), py::arg("id_base"), py::arg("side"),
+     py::arg("first"), py::arg("last"), py::arg("targeted"), py::arg("M"), py::arg("stream"),
+     "one Square Attack query per image: accept the candidate when its margin is strictly lower, freeze a broken "
+     "image, write the next candidate (a square of +-eps at a Philox-drawn place); state [M] records of 16 bytes = "
+     "margin_best, queries_used, done, spare");
 
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")

@@ -435,6 +435,45 @@ struct ApgdStepArgs {
 // M in [1, INPUT_GRAD_MAX_B], eps >= 0, sign +-1, window >= 0, not first and last at once; l2: the L2 form
 void launch_apgd_step(const ApgdStepArgs& a, int M, bool l2, hipStream_t s);
 
+// ---------------- Square Attack (square.hip; Andriushchenko, Croce, Flammarion, Hein 2020), L-inf ----------------
+// A score-based black-box attack: one query is one eval forward of the candidate x_cand, then square_step reads the
+// candidate's margin from head_eval's logp row (untargeted lp[y] - max_{j != y} lp[j]; targeted the negative; < 0:
+// broken), accepts it as the best point when it is strictly lower, freezes an image that is broken, and writes the
+// next candidate: the best point with a square of side s set to clamp(x0 + eps) or clamp(x0 - eps), its place and
+// sign drawn from Philox-4x32-10 words keyed by seed with counter (q, SQUARE_PHILOX_DOMAIN, id_base + i, k): a
+// domain no dropout stream, adv_init or smooth_noise uses.  square_init writes the candidate of query 0, vertical
+// stripes of +-eps.  The exact form and the NaN rules are in square.hip.
+// PER-IMAGE RECORD, 16 bytes (the array 16-byte aligned): {margin_best fp32, queries_used int32, done int32, spare}.
+// first: reads no record and no x_best, writes both.  A record with done != 0 on entry: nothing of the image is
+// stored.  last: x_cand is not written.  Rows and records past M are untouched.
+constexpr uint32_t SQUARE_PHILOX_DOMAIN = 0x53515231u;   // Philox counter word 1 of square_init / square_step ("SQR1")
+static_assert(SQUARE_PHILOX_DOMAIN != 0u && SQUARE_PHILOX_DOMAIN != ADV_PHILOX_DOMAIN &&
+                  SQUARE_PHILOX_DOMAIN != SMOOTH_PHILOX_DOMAIN, "a counter domain of its own");
+struct SquareInitArgs {
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* x_cand;              // fp32 [M][784] the candidate of query 0
+  float eps, lo, hi;          // radius, valid range: normalised units
+  uint64_t seed;              // Philox key
+  uint32_t id_base;           // image i draws under the id id_base + i
+};
+void launch_square_init(const SquareInitArgs& a, int M, hipStream_t s);   // M in [1, INPUT_GRAD_MAX_B], eps >= 0
+struct SquareStepArgs {
+  const float* logp;          // fp32 [M][10] log-probabilities of x_cand (head_eval)
+  const int32_t* y;           // [M] the label (targeted: the class to reach)
+  const float* x0;            // fp32 [M][784] the clean normalised image
+  float* x_best;              // fp32 [M][784] the point of the lowest margin so far
+  float* x_cand;              // fp32 [M][784] the candidate (the xin of the next eval forward)
+  void* state;                // [M] 16-byte records
+  float eps, lo, hi;
+  uint64_t seed;
+  uint32_t q;                 // the query index of the proposal this launch writes (round j: j + 1)
+  uint32_t id_base;
+  int side;                   // of that proposal's square, in [1, 27]
+  int first, last, targeted;  // flags
+};
+// M in [1, INPUT_GRAD_MAX_B], eps >= 0, side in [1, 27], id_base + M <= 2^32
+void launch_square_step(const SquareStepArgs& a, int M, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -510,6 +549,7 @@ void preload_smooth();
 void preload_attr();
 void preload_deepfool();
 void preload_apgd();
+void preload_square();
 void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

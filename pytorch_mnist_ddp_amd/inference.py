@@ -32,6 +32,9 @@ in eval mode (where noise is drawn: the same distribution, not the same bits):
   log-probabilities are the predictor's own forward (above) of the adversarial images;
 * ``auto_pgd`` / ``robust_evaluate_apgd`` (Auto-PGD, Croce & Hein 2020: PGD without a step size to tune; the same
   norms, units and targeted form): ``ops.apgd.fused_auto_pgd`` / ``reference_auto_pgd``;
+* ``square_attack`` / ``robust_evaluate_square`` (the L-inf Square Attack, Andriushchenko et al. 2020: score-based and
+  black-box, it reads log-probabilities only; the same units; here both paths draw the same Philox bits):
+  ``ops.square.fused_square_attack`` / ``reference_square_attack``;
 * ``smoothed_counts`` / ``certify`` (randomized smoothing: the class counts of Gaussian-noised copies of an image and
   the certified L2 radius they give; ``sigma`` in pixel units): ``ops.smooth.fused_smooth_counts`` / ``torch.randn``
   over the reference forward; the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path;
@@ -54,9 +57,10 @@ import torch.nn.functional as F
 from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist  # noqa: F401
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
-from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, PGD_L2_TINY, apgd_checkpoints, apgd_step_reference,
-                             attr_path_reference, attr_reduce_reference, deepfool_step_reference,
-                             pgd_l2_step_reference)
+from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES, apgd_checkpoints,
+                             apgd_step_reference, attr_path_reference, attr_reduce_reference, deepfool_step_reference,
+                             pgd_l2_step_reference, square_init_reference, square_sides, square_state_margin,
+                             square_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -135,8 +139,44 @@ def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: fl
     return state[2], (-loss_best if targeted else loss_best.clone())
 
 
+def reference_square_attack(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, queries: int, lo: float,
+                            hi: float, p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False,
+                            check_every: int = 64):
+    """``ops.square.fused_square_attack`` in torch float32 on any device: the same ``queries`` rounds - the
+    log-probabilities of the candidates from ``Net.forward_reference`` in eval mode under ``no_grad`` (the net's mode
+    is restored afterwards), then ``square_step_reference`` with the same ``first`` / ``last`` flags, query indices
+    and ``square_sides`` - with the same Philox draws (``ops.philox``).  Same arguments (float32 [B, 784] normalised
+    images, normalised units), same return: ``(x_best [B, 784], margin_best [B], queries_used int32 [B])``.
+    ``check_every`` = k > 0 stops once every image is broken, looked at every k queries; the result does not depend
+    on it.  The CPU / fp32 path of ``Predictor.square_attack`` and the reference of its GPU tests."""
+    queries, check_every = int(queries), int(check_every)
+    if queries < 1 or queries >= 1 << 32:
+        raise ValueError("reference_square_attack: queries must be in [1, 2**32)")
+    if check_every < 0:
+        raise ValueError(f"reference_square_attack: check_every must be >= 0, got {check_every}")
+    sides = square_sides(p_init, queries)
+    B = x0.shape[0]
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).to(x0.device, torch.int32)
+    ids = list(range(B)) if ids is None else [int(v) for v in ids]
+    if len(ids) != B:
+        raise ValueError(f"reference_square_attack: {len(ids)} ids for {B} images")
+    x_cand = square_init_reference(x0, eps, lo, hi, seed, ids)
+    x_best = state = None
+    with _eval_mode(net), torch.no_grad():
+        for j in range(queries):
+            last = j == queries - 1
+            lp = net.forward_reference(x_cand.view(B, 1, 28, 28))
+            x_best, x_cand, state = square_step_reference(lp, y, x0, x_best, x_cand, state, eps, lo, hi, seed, j + 1,
+                                                          1 if last else sides[j], ids, first=j == 0, last=last,
+                                                          targeted=targeted)
+            if check_every and (j + 1) % check_every == 0 and bool((state[:, SQUARE_DONE] != 0).all()):
+                break
+    return x_best, square_state_margin(state), state[:, SQUARE_QUERIES].clone()
+
+
 ATTRIBUTION_METHODS = ("integrated_gradients", "smoothgrad")
-_REF_ROWS = 1000                    # rows per forward / backward (and per generator draw) of the torch paths
+_REF_ROWS = 1000                   # rows per forward / backward (and per generator draw) of the torch paths
 
 
 def reference_minimum_norm(net: Net, x0: torch.Tensor, labels: torch.Tensor, steps: int, overshoot: float,
@@ -505,6 +545,86 @@ class Predictor:
             hits += (lp.argmax(dim=1) == y).sum()
         return float(loss.item()), int(hits.item()), n
 
+    def square_attack(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.3, queries: int = 1000,
+                      p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64):
+        """(x_adv, log_probs, margin, queries_used): the L-inf Square Attack (Andriushchenko, Croce, Flammarion, Hein
+        2020, the score-based black-box attack of AutoAttack) on ``x`` - a random search that reads only the
+        log-probabilities of its candidates, never a gradient: the cross-check of ``adversarial`` / ``auto_pgd`` on
+        a net whose gradients may be masked.  ``x_adv``: float32 [B,1,28,28] in NORMALISED units, the queried point
+        of the lowest margin, every pixel of it clamp(x + eps) or clamp(x - eps) into the valid range [0, 1];
+        ``log_probs``: the predictor's own float32 [B,10] forward of ``x_adv``; ``margin``: float32 [B], the margin at
+        ``x_adv`` as the attack's own forward gave it (log p_y - max_{j != y} log p_j; ``targeted``: the negative;
+        < 0: broken); ``queries_used``: int32 [B], the forwards spent on the image until it broke (``queries`` when
+        it did not).
+
+        ``eps``: pixel units on the [0, 1] scale; ``labels``: [B] integers, or the class predicted on the clean
+        input when None; ``targeted``: ``labels`` (required) are the classes to reach.  At most ``queries`` queries per
+        image: query 0 is a start of vertical stripes of +-eps, every later one moves one square of the image to
+        +eps or -eps and is kept when the margin drops; the square's side follows ``functional.square_sides`` from
+        the share ``p_init`` of the image.  Image j draws under the id ``ids[j]`` (default j) from the Philox stream
+        keyed by ``seed``: its squares depend on (seed, id, query index) alone, on the GPU and on the CPU alike.
+        ``check_every``: look every that many queries whether every image is broken (0: never; the result does not
+        depend on it).  The margin loss serves the targeted form too (the paper uses cross-entropy there), and the
+        paper's resampling of a square that changes nothing is not made.  Inference semantics: no dropout; the
+        net's mode, parameters and gradients are untouched.  GPU with ``dtype="bf16"``: the native loop
+        ``ops.square.fused_square_attack``; CPU, or ``dtype="fp32"``: ``reference_square_attack``.  ``x``: uint8
+        [B,28,28] / [B,784] images or float [B,1,28,28] already-normalised input."""
+        B = self._check_input(x)
+        if targeted and labels is None:
+            raise ValueError("square_attack: a targeted attack needs labels (the target classes)")
+        if not eps >= 0:
+            raise ValueError(f"square_attack: eps must be >= 0, got {eps}")
+        if isinstance(queries, bool) or queries != int(queries) or queries < 1:
+            raise ValueError(f"square_attack: queries must be a positive integer, got {queries}")
+        if not 0.0 < p_init <= 1.0:
+            raise ValueError(f"square_attack: p_init must be in (0, 1], got {p_init}")
+        if isinstance(check_every, bool) or check_every != int(check_every) or check_every < 0:
+            raise ValueError(f"square_attack: check_every must be a non-negative integer, got {check_every}")
+        ids = _ids("square_attack", ids, B)
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels("square_attack", labels, B, check_range=True)
+        eps_n, _, lo, hi = adversarial_units(eps, 1, None)
+        if self.native:
+            from .ops.square import fused_square_attack as attack
+        else:
+            attack = reference_square_attack
+        x_adv, margin, used = attack(self.net, x0, labels, eps_n, int(queries), lo, hi, float(p_init), int(seed), ids,
+                                     targeted, int(check_every))
+        x_adv = x_adv.view(B, 1, 28, 28)
+        return x_adv, self._forward(x_adv)[0], margin, used
+
+    def robust_evaluate_square(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, queries: int = 1000,
+                               batch_size: int = 1000, p_init: float = 0.8, seed: int = 0):
+        """(loss_sum, correct, n, median_queries): the first three as ``robust_evaluate``, with the untargeted
+        ``square_attack`` against the true labels as the attack, ``batch_size`` images at a time; an image's id is its
+        row index, so its squares do not depend on ``batch_size``.  ``median_queries``: the median of
+        ``queries_used`` over the images that are correct on the clean input and broken after the attack (None when
+        there is none; the median of an even count is the mean of the middle two)."""
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("robust_evaluate_square: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("robust_evaluate_square: batch_size must be positive")
+        lab = labels.long().to(self.device)
+        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        hits = torch.zeros((), dtype=torch.int64, device=self.device)
+        spent = []
+        for i in range(0, n, batch_size):
+            y = lab[i:i + batch_size]
+            clean = self._forward(images_u8[i:i + batch_size])[1] == y
+            _, lp, _, used = self.square_attack(images_u8[i:i + batch_size], y, eps, queries, p_init, seed,
+                                                ids=range(i, i + y.shape[0]))
+            right = lp.argmax(dim=1) == y
+            loss += F.nll_loss(lp, y, reduction='none').double().sum()
+            hits += right.sum()
+            spent.append(used[clean & ~right].double().cpu())
+        spent = torch.cat(spent)
+        median = float(spent.quantile(0.5)) if spent.numel() else None
+        return float(loss.item()), int(hits.item()), n, median
+
     def minimum_norm(self, x: torch.Tensor, labels: torch.Tensor | None = None, steps: int = 50,
                      overshoot: float = 0.02, check_every: int = 8):
         """(x_adv, radii, log_probs, found): minimum-norm adversarial examples of ``x`` by L2 DeepFool
@@ -765,6 +885,14 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='Auto-PGD runs per image; more than one: each from a random start (default: 1, from the '
                          'clean image)')
     ap.add_argument('--apgd-seed', type=int, default=0, help='seed of the random starts (default: 0)')
+    ap.add_argument('--square-eps', type=float, default=None, metavar='E',
+                    help='also report loss and accuracy under the L-inf Square Attack (score-based, black-box: no '
+                         'gradient is read) of radius E, in pixel units on the [0, 1] scale (default: off)')
+    ap.add_argument('--square-queries', type=int, default=1000, metavar='N',
+                    help='most queries (forwards) per image of the Square Attack (default: 1000)')
+    ap.add_argument('--square-p-init', type=float, default=0.8, metavar='P',
+                    help='share of the image the first squares cover (default: 0.8)')
+    ap.add_argument('--square-seed', type=int, default=0, help='seed of the squares (default: 0)')
     ap.add_argument('--certify-sigma', type=float, default=None, metavar='S',
                     help='also report certified accuracy under randomized smoothing with Gaussian noise of standard '
                          'deviation S, in pixel units on the [0, 1] scale (default: off)')
@@ -817,6 +945,14 @@ def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: i
     """The ``Auto-PGD set`` line of ``mnist_predict.py --apgd-eps``, in the number formats of ``adversarial_line``."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
     return f"Auto-PGD set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}, restarts={restarts}): {figures}"
+
+
+def square_line(eps: float, queries: int, p_init: float, loss: float, correct: int, n: int, median) -> str:
+    """The ``Square set`` line of ``mnist_predict.py --square-eps``, in the number formats of ``adversarial_line``;
+    ``median``: the median queries of the broken images, None when none broke."""
+    figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
+    return (f"Square set (Linf eps={eps:g}, queries={queries}, p_init={p_init:g}): {figures}, "
+            f"median queries: {'n/a' if median is None else format(median, 'g')}")
 
 
 def minimum_norm_stats(radii: torch.Tensor, found: torch.Tensor, clean: torch.Tensor, at=()):
@@ -940,6 +1076,15 @@ def predict_main(argv=None) -> int:
                             args.apgd_norm))
         record.update(apgd_eps=args.apgd_eps, apgd_steps=args.apgd_steps, apgd_norm=args.apgd_norm,
                       apgd_restarts=args.apgd_restarts, apgd_loss=ap_loss / n, apgd_correct=ap_correct)
+    if args.square_eps is not None:
+        sq_loss, sq_correct, _, sq_median = predictor.robust_evaluate_square(
+            images, data.targets, args.square_eps, args.square_queries, args.batch_size, args.square_p_init,
+            args.square_seed)
+        print(square_line(args.square_eps, args.square_queries, args.square_p_init, sq_loss / n, sq_correct, n,
+                          sq_median))
+        record.update(square_eps=args.square_eps, square_queries=args.square_queries,
+                      square_p_init=args.square_p_init, square_seed=args.square_seed, square_loss=sq_loss / n,
+                      square_correct=sq_correct, square_median_queries=sq_median)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

@@ -876,6 +876,221 @@ def apgd_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: to
                    M, _s())
 
 
+SQUARE_PHILOX_DOMAIN = 0x53515231   # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
+SQUARE_MAX_M = 1 << 20              # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
+SQUARE_MAX_SIDE = 27
+# columns of the per-image record, int32 [M, 4] (kernels.h SquareStepArgs); column 0 holds the bits of a float32
+SQUARE_MARGIN, SQUARE_QUERIES, SQUARE_DONE = 0, 1, 2
+_SQUARE_SCHEDULE = ((10, 1), (50, 2), (200, 4), (500, 8), (1000, 16), (2000, 32), (4000, 64), (6000, 128), (8000, 256))
+
+
+def square_sides(p_init: float, queries: int) -> tuple:
+    """The side of the square of each proposal of a Square Attack (Andriushchenko et al. 2020) of ``queries``
+    queries: entry ``q - 1`` belongs to query index q = 1 .. queries - 1 (query 0 is the stripe start).  The share
+    of the image a square covers is ``p_init`` halved on the authors' piecewise-constant schedule, rescaled from
+    their 10000 queries: it = int(q / queries * 10000); p = p_init / 1, 2, 4, ... 512 as ``it`` passes 10, 50, 200,
+    500, 1000, 2000, 4000, 6000, 8000; side = min(max(floor(sqrt(p * 784) + 0.5), 1), 27) in float64."""
+    import math
+    queries = int(queries)
+    if queries < 1:
+        raise ValueError("square_sides: queries must be at least 1")
+    if not 0.0 < p_init <= 1.0:
+        raise ValueError(f"square_sides: p_init must be in (0, 1], got {p_init}")
+    out = []
+    for q in range(1, queries):
+        it = int(q / queries * 10000)
+        div = next((d for top, d in _SQUARE_SCHEDULE if it <= top), 512)
+        side = int(math.floor(math.sqrt(float(p_init) / div * 784.0) + 0.5))
+        out.append(min(max(side, 1), SQUARE_MAX_SIDE))
+    return tuple(out)
+
+
+def square_state_margin(state: torch.Tensor) -> torch.Tensor:
+    """float32 [M]: ``margin_best`` of the int32 [M, 4] records of ``square_step`` (column 0 read as float32)."""
+    return state[:, SQUARE_MARGIN].contiguous().view(torch.float32)
+
+
+def _square_ids(name: str, ids, id_base: int, M: int):
+    import numpy as np
+    ids = np.arange(M, dtype=np.int64) + int(id_base) if ids is None else np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.shape[0] != M:
+        raise ValueError(f"{name}: {ids.shape[0]} ids for {M} images")
+    if M and (ids.min() < 0 or ids.max() >= 1 << 32):
+        raise ValueError(f"{name}: every image id must fit 32 bits")
+    return ids
+
+
+def _square_vertex(x0: torch.Tensor, plus: torch.Tensor, eps: float, lo: float, hi: float) -> torch.Tensor:
+    """clamp(x0 + eps) where ``plus`` else clamp(x0 - eps): float32, each operation rounded on its own."""
+    import numpy as np
+    e = torch.tensor(float(np.float32(eps)), dtype=torch.float32, device=x0.device)
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    return torch.where(plus, x0 + e, x0 - e).clamp(lo, hi)
+
+
+def square_init_reference(x0: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, ids=None,
+                          id_base: int = 0) -> torch.Tensor:
+    """``square_init`` in torch float32 on any device: the candidate of query 0, vertical stripes - column c of every
+    row of image i is clamp(x0 + eps) when bit 0 of word ``c & 3`` of ``philox4x32(counter = (0,
+    SQUARE_PHILOX_DOMAIN, id_i, c >> 2), key = seed)`` is set, else clamp(x0 - eps).  ``ids``: the images' ids
+    (default ``id_base`` + i).  The same bits as the kernel (``ops.philox`` draws them)."""
+    import numpy as np
+    from .philox import philox4x32
+    M = x0.shape[0]
+    x0 = x0.detach().reshape(M, 784).to(torch.float32)
+    ids = _square_ids("square_init_reference", ids, id_base, M)
+    w = philox4x32(0, SQUARE_PHILOX_DOMAIN, ids[:, None], np.arange(7)[None, :], seed)        # [M, 7, 4]
+    plus = torch.from_numpy((w.reshape(M, 28) & 1).astype(np.bool_)).to(x0.device)
+    return _square_vertex(x0.view(M, 28, 28), plus[:, None, :], eps, lo, hi).reshape(M, 784)
+
+
+def square_margin_reference(logp: torch.Tensor, y: torch.Tensor, targeted: bool = False) -> torch.Tensor:
+    """float32 [M]: the margin ``square_step`` reads off a row of ten log-probabilities - untargeted lp[y] -
+    max_{j != y} lp[j], targeted the negative; < 0: broken.  A NaN anywhere in the row (the maximum lets it through)
+    and a y outside [0, 10) give a NaN."""
+    M = logp.shape[0]
+    lp = logp.detach().reshape(M, NCLS).to(torch.float32)
+    y = y.reshape(M).long().to(lp.device)
+    valid = (y >= 0) & (y < NCLS)
+    yc = y.clamp(0, NCLS - 1)
+    own = torch.zeros(M, NCLS, dtype=torch.bool, device=lp.device).scatter_(1, yc[:, None], valid[:, None])
+    ly = torch.where(valid, lp.gather(1, yc[:, None])[:, 0], torch.full_like(lp[:, 0], float("nan")))
+    mo = lp.masked_fill(own, float("-inf")).max(dim=1).values
+    return (mo - ly) if targeted else (ly - mo)
+
+
+def square_step_reference(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: torch.Tensor | None,
+                          x_cand: torch.Tensor, state: torch.Tensor | None, eps: float, lo: float, hi: float,
+                          seed: int = 0, q: int = 1, side: int = 1, ids=None, id_base: int = 0, first: bool = False,
+                          last: bool = False, targeted: bool = False):
+    """``square_step`` in torch float32 on any device (the CPU / fp32 path of ``Predictor.square_attack``): none of
+    the operands - ``logp`` [M, 10], ``y`` [M], ``x0`` / ``x_best`` / ``x_cand`` [M, 784], ``state`` int32 [M, 4]
+    (margin_best as float32 bits, queries_used, done, spare) - is modified; returns the new ``(x_best, x_cand,
+    state)``.  With ``first`` neither ``x_best`` nor ``state`` is read (None will do).  Per image, with L the margin
+    (``square_margin_reference``) of ``logp``:
+
+        first:          margin_best = L; x_best = x_cand; queries_used = 1
+        done on entry:  nothing changes (frozen)
+        else:           queries_used += 1;  L < margin_best (strict): margin_best = L, x_best = x_cand
+        done = margin_best < 0
+        last:           x_cand stays
+        else, done:     x_cand = x_best
+        else:           x_cand = x_best with the square of side ``side`` at (row0, col0) set to clamp(x0 + eps) (w2 & 1)
+                        or clamp(x0 - eps): w = philox4x32(counter = (q, SQUARE_PHILOX_DOMAIN, id_i, 0), key = seed),
+                        row0 = (w0 * (29 - side)) >> 32, col0 = (w1 * (29 - side)) >> 32
+
+    ``q``: the query index of that proposal (round j: j + 1)."""
+    import numpy as np
+    from .philox import philox4x32
+    side, q = int(side), int(q)
+    if not 1 <= side <= SQUARE_MAX_SIDE:
+        raise ValueError(f"square_step_reference: side must be in [1, {SQUARE_MAX_SIDE}], got {side}")
+    if not 0 <= q < 1 << 32:
+        raise ValueError("square_step_reference: q must fit 32 bits")
+    M = x_cand.shape[0]
+    dev = x_cand.device
+    x0 = x0.detach().reshape(M, 784).to(torch.float32)
+    x_cand = x_cand.detach().reshape(M, 784).to(torch.float32)
+    ids = _square_ids("square_step_reference", ids, id_base, M)
+    L = square_margin_reference(logp, y, targeted).to(dev)
+    if first:
+        active = accept = torch.ones(M, dtype=torch.bool, device=dev)
+        margin = L
+        used = torch.ones(M, dtype=torch.int32, device=dev)
+        done_was = spare = torch.zeros(M, dtype=torch.int32, device=dev)
+        xb = x_cand
+    else:
+        state = state.reshape(M, 4).to(torch.int32)
+        was = square_state_margin(state)
+        done_was, spare = state[:, SQUARE_DONE], state[:, 3]
+        active = done_was == 0
+        accept = active & (L < was)
+        margin = torch.where(accept, L, was)
+        used = state[:, SQUARE_QUERIES] + active.to(torch.int32)
+        xb = torch.where(accept[:, None], x_cand, x_best.detach().reshape(M, 784).to(torch.float32))
+    broken = margin < 0
+    done = torch.where(active, broken.to(torch.int32), done_was)
+    xc = x_cand
+    if not last:
+        w = philox4x32(q, SQUARE_PHILOX_DOMAIN, ids, 0, seed).astype(np.uint64)                 # [M, 4]
+        span = np.uint64(29 - side)
+        row0 = torch.from_numpy(((w[:, 0] * span) >> np.uint64(32)).astype(np.int64)).to(dev)
+        col0 = torch.from_numpy(((w[:, 1] * span) >> np.uint64(32)).astype(np.int64)).to(dev)
+        plus = torch.from_numpy((w[:, 2] & np.uint64(1)).astype(np.bool_)).to(dev)
+        at = torch.arange(28, device=dev)
+        rows = (at[None, :] >= row0[:, None]) & (at[None, :] < row0[:, None] + side)
+        cols = (at[None, :] >= col0[:, None]) & (at[None, :] < col0[:, None] + side)
+        window = (rows[:, :, None] & cols[:, None, :]).reshape(M, 784)
+        prop = torch.where(window, _square_vertex(x0, plus[:, None], eps, lo, hi), xb)
+        xc = torch.where((active & ~broken)[:, None], prop, torch.where(active[:, None], xb, x_cand))
+    margin_bits = torch.where(active, margin, square_state_margin(state) if not first else margin)
+    new = torch.stack((margin_bits.contiguous().view(torch.int32), used, done, spare), dim=1)
+    return xb, xc, new
+
+
+def _square_common(name: str, eps: float, lo: float, hi: float, id_base: int, M: int) -> None:
+    if M < 1 or M > SQUARE_MAX_M:
+        raise ValueError(f"{name}: M = {M} images must be in [1, SQUARE_MAX_M = {SQUARE_MAX_M}] a launch")
+    if not (eps >= 0 and lo <= hi):
+        raise ValueError(f"{name}: need eps >= 0 and lo <= hi")
+    if id_base < 0 or id_base + M > 1 << 32:
+        raise ValueError(f"{name}: id_base + M must not exceed 2**32")
+
+
+def square_init(x0: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, id_base: int = 0,
+                out: torch.Tensor | None = None, M: int | None = None) -> torch.Tensor:
+    """The start of a Square Attack (``csrc/kernels/square.hip``), one launch: ``out[i]`` = the stripe point of
+    ``square_init_reference`` for the M images ``x0`` (float32 [>= M, 784] normalised rows on the GPU), image i under
+    the id ``id_base + i``.  ``out``: float32 with at least M rows of 784, allocated when None; nothing past M is
+    written.  Bit for bit the reference."""
+    if x0.dim() != 2 or x0.device.type != "cuda":
+        raise ValueError("square_init: x0 must be a float32 [M, 784] tensor on the GPU")
+    M = int(x0.shape[0] if M is None else M)
+    _square_common("square_init", eps, lo, hi, int(id_base), M)
+    _f32_rows("square_init", "x0", x0, M, x0.device, at_least="M")
+    out = _out_rows("square_init", "out", out, M, x0.device, at_least="M")
+    if out.data_ptr() == x0.data_ptr():
+        raise ValueError("square_init: x0 and out must be two buffers")
+    _C().square_init(native.ptr(x0), native.ptr(out), float(eps), float(lo), float(hi), int(seed) & (2 ** 64 - 1),
+                     int(id_base), M, _s())
+    return out
+
+
+def square_step(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: torch.Tensor, x_cand: torch.Tensor,
+                state: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, q: int = 1, side: int = 1,
+                id_base: int = 0, first: bool = False, last: bool = False, targeted: bool = False,
+                M: int | None = None) -> None:
+    """One Square Attack query per image (``csrc/kernels/square.hip``), one launch, in place: from the
+    log-probabilities ``logp`` (float32 [>= M, 10], what ``head_eval`` wrote for the candidates ``x_cand``), the
+    labels ``y`` (int32 [>= M]; ``targeted``: the classes to reach) and the clean images ``x0``, the update of
+    ``square_step_reference`` on ``x_best``, ``x_cand`` (float32 [>= M, 784]) and ``state`` (int32 [>= M, 4]),
+    image i under the id ``id_base + i``.  ``first``: no record and no ``x_best`` is read, both are written;
+    ``last``: ``x_cand`` is not written; an image whose record says done is frozen: nothing of it is stored.  ``q``,
+    ``side``: the query index and the square's side of the proposal written to ``x_cand``.  ``M``: the images of the
+    launch (default ``x_cand.shape[0]``); nothing past M is touched.  Bit for bit the reference."""
+    if x_cand.dim() != 2 or x_cand.device.type != "cuda":
+        raise ValueError("square_step: x_cand must be a float32 [M, 784] tensor on the GPU")
+    dev = x_cand.device
+    M = int(x_cand.shape[0] if M is None else M)
+    _square_common("square_step", eps, lo, hi, int(id_base), M)
+    rows = (("x0", x0), ("x_best", x_best), ("x_cand", x_cand))
+    for what, t in rows:
+        _f32_rows("square_step", what, t, M, dev, at_least="M")
+    _df_vec("square_step", "logp", logp, torch.float32, NCLS * M, dev, "10 M")
+    _df_vec("square_step", "y", y, torch.int32, M, dev, "M")
+    _df_vec("square_step", "state", state, torch.int32, 4 * M, dev, "4 M")
+    if len({t.data_ptr() for _, t in rows}) != len(rows):
+        raise ValueError("square_step: x0, x_best and x_cand must be three buffers")
+    if not 1 <= int(side) <= SQUARE_MAX_SIDE:
+        raise ValueError(f"square_step: side must be in [1, {SQUARE_MAX_SIDE}], got {side}")
+    if not 0 <= int(q) < 1 << 32:
+        raise ValueError("square_step: q must fit 32 bits")
+    p = native.ptr
+    _C().square_step(p(logp), p(y), p(x0), p(x_best), p(x_cand), p(state), float(eps), float(lo), float(hi),
+                     int(seed) & (2 ** 64 - 1), int(q), int(id_base), int(side), bool(first), bool(last),
+                     bool(targeted), M, _s())
+
+
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:
     """``grid`` > 0 (``ADA_FC`` only): that many workgroups; below ``ADA_FC_TILES`` they walk the fc tiles
     grid-stride.  ``wt``: write-through 16-byte stores (the engine's choice at B <= WT_MAX_B)."""
