@@ -252,6 +252,22 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("z1part"), py::arg("b_fc1"), py::arg("w_fc2"), py::arg("b_fc2"), py::arg("labels"), py::arg("idx"),
      py::arg("idx_stride"), py::arg("state"), py::arg("inv_batch"), py::arg("loss_rows"), py::arg("dz1"),
      py::arg("h_bf"), py::arg("dl_bf"), py::arg("B"), py::arg("Bp"), py::arg("stream"), py::arg("dlogp") = 0);
+  m.attr("MARGIN_CW") = (int)MARGIN_CW;
+  m.attr("MARGIN_DLR") = (int)MARGIN_DLR;
+  m.attr("MARGIN_DLR_T") = (int)MARGIN_DLR_T;
+  m.def("head_margin", [](uintptr_t z1part, uintptr_t b_fc1, uintptr_t w_fc2, uintptr_t b_fc2, uintptr_t labels,
+                          uintptr_t targets, int kind, float scale, uintptr_t loss_rows, uintptr_t dz1,
+                          uintptr_t h_bf, uintptr_t dl_bf, int B, int Bp, uintptr_t stream) {
+    HeadMarginArgs a{};
+    a.z1part = P<const float>(z1part); a.b_fc1 = P<const float>(b_fc1); a.w_fc2 = P<const float>(w_fc2);
+    a.b_fc2 = P<const float>(b_fc2); a.labels = P<const int32_t>(labels); a.targets = P<const int32_t>(targets);
+    a.scale = scale; a.loss_rows = P<float>(loss_rows); a.dz1 = P<uint16_t>(dz1); a.h_bf = P<uint16_t>(h_bf);
+    a.dl_bf = P<uint16_t>(dl_bf);
+    launch_head_margin(a, B, Bp, kind, S(stream));
+    check_launch();
+  }, py::arg("z1part"), py::arg("b_fc1"), py::arg("w_fc2"), py::arg("b_fc2"), py::arg("labels"), py::arg("targets"),
+     py::arg("kind"), py::arg("scale"), py::arg("loss_rows"), py::arg("dz1"), py::arg("h_bf"), py::arg("dl_bf"),
+     py::arg("B"), py::arg("Bp"), py::arg("stream"));
   m.def("head_fwd", [](uintptr_t z1part, uintptr_t b_fc1, uintptr_t w_fc2, uintptr_t b_fc2, uintptr_t state,
                        uintptr_t logp, int B, bool train, uintptr_t stream) {
     HeadArgs a{};

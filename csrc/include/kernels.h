@@ -66,6 +66,39 @@ void launch_head_eval(const HeadArgs& a, int B, hipStream_t s);
 // module API forward: log-probs with (train) or without (eval) dropout-2
 void launch_head_fwd(const HeadArgs& a, int B, bool train, hipStream_t s);
 
+// Margin head (fc_head.hip): head_train's forward in inference semantics (no StepState, no dropout; z1, h and the
+// logits z carry head_train's bits with dropout off) with a margin loss L on the logits in place of the NLL, and
+// head_train's outputs under head_train's padding contract, so any fc_bwd role may follow.  Per row, with y =
+// labels[b], s = scale, and the selections made with explicit > in ascending class order (the first of equals
+// wins): pi1 the first maximum of z, pi2 / pi3 / pi4 the first maximum over the classes not yet taken, o the first
+// maximum over j != y.  Every operation below is rounded on its own; dl starts at 0 and the terms are added in the
+// order written:
+//   MARGIN_CW:     L = z[o] - z[y];                              dl[o] += s; dl[y] -= s
+//   MARGIN_DLR:    d = (z[pi1] - z[pi3]) + 1e-12f;  L = (z[o] - z[y]) / d;  dl[o] += s/d; dl[y] -= s/d;
+//                  q = (s L) / d;  dl[pi1] -= q; dl[pi3] += q
+//   MARGIN_DLR_T:  t = targets[b] (t != y is the caller's promise);  d = (z[pi1] - 0.5f (z[pi3] + z[pi4])) + 1e-12f;
+//                  L = (z[y] - z[t]) / d;  dl[y] += s/d; dl[t] -= s/d;
+//                  q = (s L) / d;  dl[pi1] -= q; dl[pi3] += 0.5f q; dl[pi4] += 0.5f q
+// CW and DLR are ascended to leave y (with y a target class, descended to reach it); DLR_T is descended: it is the
+// negative of the APGD-T objective of Croce & Hein (2020).
+enum MarginKind : int { MARGIN_CW = 0, MARGIN_DLR = 1, MARGIN_DLR_T = 2 };
+struct HeadMarginArgs {
+  const float* z1part;        // [fc1_ksplit(B)][B][128]
+  const float* b_fc1;         // [128]
+  const float* w_fc2;         // [10][128] fp32
+  const float* b_fc2;         // [10]
+  const int32_t* labels;      // [B] one label per batch row
+  const int32_t* targets;     // [B] MARGIN_DLR_T only (else unread, may be null)
+  float scale;                // s: dl = s dL/dz
+  float* loss_rows;           // [B] per-row L
+  uint16_t* dz1;              // bf16 [Bp][128] (z1 > 0) ? sum_c dl[c] w2[c] : 0 (rows [B, Bp) zeroed)
+  uint16_t* h_bf;             // bf16 [Bp][128] relu(z1) (rows [B, Bp) zeroed)
+  uint16_t* dl_bf;            // bf16 [Bp][16]  (cols >= 10, rows [B, Bp) zeroed)
+};
+// Refuses, without launching: an unknown kind, a null pointer (targets: with MARGIN_DLR_T), B <= 0, a Bp that is
+// not a multiple of 32 or is below B.  Grid: Bp one-wave workgroups, one row each.
+void launch_head_margin(const HeadMarginArgs& a, int B, int Bp, int kind, hipStream_t s);
+
 // ---------------- inference (infer_fwd.hip) ----------------
 // One launch: B images -> log-probs, argmax (+ per-row NLL / hit with labels).  Grid = (INFER_BANDS,
 // groups): workgroup (band, g) runs the conv trunk for pooled row `band` of the images

@@ -6,6 +6,7 @@
 #include "../include/device_utils.h"
 #include "../include/kernels.h"
 #include "../include/timeline.h"
+#include "../runtime/host_logic.h"
 
 #include <stdexcept>
 #include <stdlib.h>
@@ -432,6 +433,193 @@ void launch_head_train(const HeadArgs& a, int B, int Bp, hipStream_t s) {
 }
 void launch_head_eval(const HeadArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL(head_eval_kernel, dim3((B + 3) / 4), dim3(256), 0, s, a, B);
+}
+
+// ============================================================================================
+// Margin head: head_train's forward in inference semantics (no StepState, no dropout, labels given per
+// row) with a margin loss on the logits in place of log_softmax + NLL: the CW margin, the DLR loss of
+// Croce & Hein (2020) and its targeted form (kernels.h HeadMarginArgs has the formulas).  The losses are
+// shift-invariant, so no log-softmax is taken.  Same structure as head_train_row: one wave = one batch
+// row, every load of the row issued up front and none under a branch (KS and the loss kind are template
+// parameters); z1, h and the logits in head_train's expression forms and chunk order, so they carry the
+// bits head_train gives with dropout off.  The loss part is rounded operation by operation (contraction
+// off).  The ten-element selections are selects over unrolled loops - no dynamically indexed array, so
+// the logits and dl stay in registers.
+//
+// RESOURCES (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage), KS = 32 / KS = 4:
+//   head_margin_kernel<KS, CW>:    VGPRs 75 / 44, SGPRs 46 / 46, LDS 0 B, scratch 0, occupancy 6 / 8 waves / SIMD
+//   head_margin_kernel<KS, DLR>:   VGPRs 76 / 46, SGPRs 54 / 54, LDS 0 B, scratch 0, occupancy 6 / 8 waves / SIMD
+//   head_margin_kernel<KS, DLR_T>: VGPRs 76 / 48, SGPRs 72 / 72, LDS 0 B, scratch 0, occupancy 6 / 8 waves / SIMD
+// (head_train_kernel<32, false>: VGPRs 114, occupancy 4.)  mg_at starts its select chain at 0 and class 0, the form
+// of the dl_bf column pick: started at z[0] and class 1 the compiler turned the chain into an indexed read of a
+// ten-float array that it placed in LDS (2560 B a workgroup).
+// ============================================================================================
+namespace {
+// class i as a bit of mg_first_max's `taken` (i outside [0, 10): no bit)
+__device__ __forceinline__ unsigned mg_bit(int i) { return (unsigned)i < (unsigned)NCLS ? 1u << i : 0u; }
+// z[i] by selects (i outside [0, 10): 0)
+__device__ __forceinline__ float mg_at(const float (&z)[NCLS], int i) {
+  float v = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) v = (i == c) ? z[c] : v;
+  return v;
+}
+// The first maximum of z over the classes whose bit in `taken` is clear: explicit > in ascending class
+// order, the first of equals wins (a NaN never wins over an earlier class).  Returns the class, its
+// logit in `best`.
+__device__ __forceinline__ int mg_first_max(const float (&z)[NCLS], unsigned taken, float& best) {
+  int idx = -1;
+  best = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) {
+    const bool take = !((taken >> c) & 1u) && (idx < 0 || z[c] > best);
+    best = take ? z[c] : best;
+    idx = take ? c : idx;
+  }
+  return idx;
+}
+// dl[i] += v
+__device__ __forceinline__ void mg_add(float (&dl)[NCLS], int i, float v) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) dl[c] = (i == c) ? dl[c] + v : dl[c];
+}
+
+// loss L and d L * s / d z of one row from its logits (kernels.h HeadMarginArgs)
+template <int KIND>
+__device__ __forceinline__ float margin_loss(const float (&z)[NCLS], int y, int t, float s, float (&dl)[NCLS]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) dl[c] = 0.0f;
+  const float zy = mg_at(z, y);
+  if constexpr (KIND == MARGIN_CW) {
+    float zo;
+    const int o = mg_first_max(z, mg_bit(y), zo);
+    mg_add(dl, o, s);
+    mg_add(dl, y, -s);
+    return zo - zy;
+  } else {
+    float z1, z2, z3, z4;
+    const int p1 = mg_first_max(z, 0u, z1);
+    const int p2 = mg_first_max(z, mg_bit(p1), z2);
+    const int p3 = mg_first_max(z, mg_bit(p1) | mg_bit(p2), z3);
+    if constexpr (KIND == MARGIN_DLR) {
+      float zo;
+      const int o = mg_first_max(z, mg_bit(y), zo);
+      const float d = (z1 - z3) + 1e-12f;
+      const float L = (zo - zy) / d;
+      const float g = s / d;
+      mg_add(dl, o, g);
+      mg_add(dl, y, -g);
+      const float q = (s * L) / d;
+      mg_add(dl, p1, -q);
+      mg_add(dl, p3, q);
+      return L;
+    } else {
+      const int p4 = mg_first_max(z, mg_bit(p1) | mg_bit(p2) | mg_bit(p3), z4);
+      const float zt = mg_at(z, t);
+      const float d = (z1 - 0.5f * (z3 + z4)) + 1e-12f;
+      const float L = (zy - zt) / d;
+      const float g = s / d;
+      mg_add(dl, y, g);
+      mg_add(dl, t, -g);
+      const float q = (s * L) / d;
+      const float hq = 0.5f * q;
+      mg_add(dl, p1, -q);
+      mg_add(dl, p3, hq);
+      mg_add(dl, p4, hq);
+      return L;
+    }
+  }
+}
+}  // namespace
+
+template <int KS, int KIND>
+__global__ __launch_bounds__(64) void head_margin_kernel(HeadMarginArgs a, int B) {
+  RW_ENTRY();
+  const int b = blockIdx.x, lane = threadIdx.x & 63;
+  if (b >= B) {  // padding rows of the bf16 operands consumed by the backward GEMMs
+    a.dz1[(int64_t)b * NH + lane] = 0;
+    a.dz1[(int64_t)b * NH + lane + 64] = 0;
+    a.h_bf[(int64_t)b * NH + lane] = 0;
+    a.h_bf[(int64_t)b * NH + lane + 64] = 0;
+    if (lane < 16) a.dl_bf[(int64_t)b * 16 + lane] = 0;
+    return;
+  }
+  const int y = a.labels[b];
+  int t = 0;
+  if constexpr (KIND == MARGIN_DLR_T) t = a.targets[b];
+  float part[KS][2], bf1[2], w2v[NCLS][2], bf2[NCLS];
+#pragma unroll
+  for (int c = 0; c < KS; ++c)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) part[c][j] = a.z1part[((int64_t)c * B + b) * NH + lane + 64 * j];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) bf1[j] = a.b_fc1[lane + 64 * j];
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) w2v[c][j] = a.w_fc2[c * NH + lane + 64 * j];
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) bf2[c] = a.b_fc2[c];
+  float z1[2], h[2], logit[NCLS];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float z = bf1[j];
+    float s = 0.f;                                   // partial sums in fixed chunk order
+#pragma unroll
+    for (int c = 0; c < KS; ++c) s += part[c][j];
+    z += s;
+    z1[j] = z;
+    h[j] = fmaxf(z, 0.0f);
+  }
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) {
+    const float v = h[0] * w2v[c][0] + h[1] * w2v[c][1];
+    logit[c] = wave_sum(v) + bf2[c];
+  }
+  float dl[NCLS];
+  const float L = margin_loss<KIND>(logit, y, t, a.scale, dl);
+  if (lane == 0) a.loss_rows[b] = L;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int o = lane + 64 * j;
+    float dh = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) dh = __builtin_fmaf(dl[c], w2v[c][j], dh);
+    const float dz = (z1[j] > 0.0f) ? dh : 0.0f;
+    a.dz1[(int64_t)b * NH + o] = f2bf(dz);
+    a.h_bf[(int64_t)b * NH + o] = f2bf(h[j]);
+  }
+  if (lane < 16) {
+    float v = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) v = (lane == c) ? dl[c] : v;
+    a.dl_bf[(int64_t)b * 16 + lane] = f2bf(v);
+  }
+}
+
+void launch_head_margin(const HeadMarginArgs& a, int B, int Bp, int kind, hipStream_t s) {
+  if (kind != MARGIN_CW && kind != MARGIN_DLR && kind != MARGIN_DLR_T)
+    throw std::runtime_error("head_margin: unknown loss code");
+  if (!a.z1part || !a.b_fc1 || !a.w_fc2 || !a.b_fc2 || !a.labels || !a.loss_rows || !a.dz1 || !a.h_bf || !a.dl_bf)
+    throw std::runtime_error("head_margin: null argument");
+  if (kind == MARGIN_DLR_T && !a.targets)
+    throw std::runtime_error("head_margin: null argument (the targeted DLR loss needs the targets)");
+  if (B <= 0) throw std::runtime_error("head_margin: row count out of range");
+  if (Bp % 32 != 0 || Bp < B) throw std::runtime_error("head_margin: Bp must be a multiple of 32 that is >= B");
+  if (misaligned(3, a.z1part, a.b_fc1, a.w_fc2, a.b_fc2, a.loss_rows) || misaligned(3, a.labels, a.targets))
+    throw std::runtime_error("head_margin: the fp32 and int32 arrays must be 4-byte aligned");
+  if (misaligned(1, a.dz1, a.h_bf, a.dl_bf)) throw std::runtime_error("head_margin: the bf16 rows must be 2-byte aligned");
+  const dim3 g(Bp), t(64);   // one row (wave) per workgroup, as head_train
+#define HM_LAUNCH(KS)                                                                                       \
+  switch (kind) {                                                                                           \
+    case MARGIN_CW: hipLaunchKernelGGL((head_margin_kernel<KS, MARGIN_CW>), g, t, 0, s, a, B); break;       \
+    case MARGIN_DLR: hipLaunchKernelGGL((head_margin_kernel<KS, MARGIN_DLR>), g, t, 0, s, a, B); break;     \
+    default: hipLaunchKernelGGL((head_margin_kernel<KS, MARGIN_DLR_T>), g, t, 0, s, a, B); break;           \
+  }
+  if (fc1_ksplit(B) == FC1_KSPLIT) HM_LAUNCH(FC1_KSPLIT) else HM_LAUNCH(FC1_KSPLIT_BIG)
+#undef HM_LAUNCH
 }
 
 // ============================================================================================

@@ -31,7 +31,9 @@ in eval mode (where noise is drawn: the same distribution, not the same bits):
   pixel units on the [0, 1] scale): ``ops.attack.fused_adversarial`` / ``reference_adversarial``; the returned
   log-probabilities are the predictor's own forward (above) of the adversarial images;
 * ``auto_pgd`` / ``robust_evaluate_apgd`` (Auto-PGD, Croce & Hein 2020: PGD without a step size to tune; the same
-  norms, units and targeted form): ``ops.apgd.fused_auto_pgd`` / ``reference_auto_pgd``;
+  norms, units and targeted form): ``ops.apgd.fused_auto_pgd`` / ``reference_auto_pgd``; it takes
+  ``loss="cw"`` / ``"dlr"`` (the CW margin, the DLR loss and its targeted form) in the NLL's place, and
+  ``robust_evaluate_ensemble`` counts the images that survive APGD-CE, targeted APGD-DLR and the Square Attack;
 * ``square_attack`` / ``robust_evaluate_square`` (the L-inf Square Attack, Andriushchenko et al. 2020: score-based and
   black-box, it reads log-probabilities only; the same units; here both paths draw the same Philox bits):
   ``ops.square.fused_square_attack`` / ``reference_square_attack``;
@@ -57,10 +59,11 @@ import torch.nn.functional as F
 from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist  # noqa: F401
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
+from .ops.chain import chain_loss
 from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES, apgd_checkpoints,
                              apgd_step_reference, attr_path_reference, attr_reduce_reference, deepfool_step_reference,
-                             pgd_l2_step_reference, square_init_reference, square_sides, square_state_margin,
-                             square_step_reference)
+                             margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_sides,
+                             square_state_margin, square_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -80,6 +83,19 @@ def _eval_mode(net: Net):
         yield
     finally:
         net.train(was_training)
+
+
+def _loss_rows_fn(name: str, loss: str, targeted: bool, labels: torch.Tensor, true_labels):
+    """log-probs [B, 10] -> the per-row loss [B] ``reference_auto_pgd`` ascends (``targeted``: descend): the NLL of
+    ``labels``, or the margin loss ``chain_loss`` names - targeted "dlr": of ``true_labels`` towards ``labels``."""
+    kind = chain_loss(name, loss, targeted)
+    if kind == "ce":
+        return lambda lp: F.nll_loss(lp, labels.long(), reduction='none')
+    if kind == "dlr_t":
+        if true_labels is None:
+            raise ValueError(f"{name}: the targeted DLR loss needs true_labels")
+        return lambda lp: margin_loss_reference(lp, true_labels.to(lp.device), "dlr_t", labels)
+    return lambda lp: margin_loss_reference(lp, labels, kind)
 
 
 def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int,
@@ -110,12 +126,14 @@ def reference_adversarial(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps:
 
 
 def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int, lo: float,
-                       hi: float, x_init: torch.Tensor | None = None, norm: str = "linf", targeted: bool = False):
+                       hi: float, x_init: torch.Tensor | None = None, norm: str = "linf", targeted: bool = False,
+                       loss: str = "ce", true_labels: torch.Tensor | None = None):
     """``ops.apgd.fused_auto_pgd`` in torch float32 on any device: the same ``steps + 1`` rounds - the per-row NLL of
     ``labels`` and its gradient by autograd over ``Net.forward_reference`` in eval mode (no dropout; the net's mode
     is restored afterwards), then ``apgd_step_reference`` with the same ``first`` / ``last`` flags and the windows
     of ``apgd_checkpoints``.  Same arguments (float32 [B, 784] normalised images, normalised units), same return:
-    ``(x_best [B, 784], loss_best [B])``, the loss as the NLL of ``labels``.  The CPU / fp32 path of
+    ``(x_best [B, 784], loss_best [B])``, the loss as the NLL of ``labels`` - with ``loss`` "cw" / "dlr" the margin
+    loss of ``margin_loss_reference`` on the log-probs instead, throughout.  The CPU / fp32 path of
     ``Predictor.auto_pgd`` and the reference of its GPU tests."""
     if steps < 1:
         raise ValueError("reference_auto_pgd: steps must be at least 1")
@@ -124,6 +142,7 @@ def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: fl
     y = labels.reshape(B).long().to(x0.device)
     window = dict(apgd_checkpoints(steps))
     sign = -1 if targeted else 1
+    loss_of = _loss_rows_fn("reference_auto_pgd", loss, targeted, y, true_labels)
     state = ((x0 if x_init is None else x_init.detach().reshape(B, 784).to(torch.float32)).clone(),
              None, None, None, None, None)
     with _eval_mode(net):
@@ -131,8 +150,8 @@ def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: fl
             xg = state[0].clone().requires_grad_()
             with torch.enable_grad():
                 lp = net.forward_reference(xg.view(B, 1, 28, 28))
-                g, = torch.autograd.grad(F.nll_loss(lp, y, reduction='sum'), xg)
-            loss_rows = F.nll_loss(lp.detach(), y, reduction='none')
+                g, = torch.autograd.grad(loss_of(lp).sum(), xg)
+            loss_rows = loss_of(lp.detach())
             state = apgd_step_reference(g, loss_rows, x0, *state, sign, eps, lo, hi, norm=norm, first=j == 0,
                                         last=j == steps, window=window.get(j, 0))
     loss_best = state[4][:, APGD_LOSS_BEST]
@@ -465,18 +484,25 @@ class Predictor:
 
     def auto_pgd(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1, steps: int = 100,
                  norm: str = "linf", targeted: bool = False, random_start: bool = False, restarts: int = 1,
-                 generator=None):
+                 generator=None, loss: str = "ce", true_labels: torch.Tensor | None = None):
         """(x_adv, log_probs, loss_best): Auto-PGD (Croce & Hein 2020, the gradient attack of AutoAttack) adversarial
         examples of ``x`` - PGD with a momentum step, a per-image step size that starts at ``2 eps`` and is halved at
         scheduled checkpoints when the loss stops rising, and a restart from the best point found so far; there is
         no step size to choose.  ``x_adv``: float32 [B,1,28,28] in NORMALISED units, the point of the highest loss
         among the ``steps + 1`` iterates (``targeted``: the lowest), inside both the ``eps`` ball around ``x`` and
         the valid pixel range [0, 1]; ``log_probs``: the predictor's own float32 [B,10] forward of ``x_adv``;
-        ``loss_best``: float32 [B], the NLL of ``labels`` at ``x_adv`` as the attack's own forward computed it.
+        ``loss_best``: float32 [B], the chosen loss (``loss``: the NLL of ``labels`` by default) at ``x_adv`` as the
+        attack's own forward computed it.
 
         Whether an image was broken is read from ``log_probs`` (``log_probs.argmax(1) != labels``): the attack keeps
         the highest-loss point, it has no arg-max of the iterates and so does not keep "the first misclassified
-        point" apart as the authors' code does; the loss used is the NLL (cross-entropy), not the DLR loss.
+        point" apart as the authors' code does.  ``loss``: "ce" (the NLL, cross-entropy), "cw" (the CW margin
+        max_{j != y} z_j - z_y on the logits) or "dlr" (the DLR loss of Croce & Hein 2020: that margin over z_pi1 -
+        z_pi3, invariant to a rescaling of the logits), ascended against ``labels`` or, ``targeted``, descended towards
+        them; ``targeted`` with "dlr" is the authors' APGD-T: the targeted DLR loss (z_y - z_t) / (z_pi1 - (z_pi3 +
+        z_pi4) / 2), which reads ``true_labels`` ([B] integers; None: the class predicted on the clean input; no row's
+        target may equal its true label), is descended (it is the negative of their objective).
+        ``ops.functional.margin_loss_reference`` has the exact forms and the tie rules.
 
         ``norm``, ``eps`` (pixel units on the [0, 1] scale), ``labels`` (None: the class predicted on the clean
         input), ``targeted`` (``labels`` required: the classes to reach, their NLL is descended), ``random_start``
@@ -489,6 +515,8 @@ class Predictor:
         B = self._check_input(x)
         if norm not in ("linf", "l2"):
             raise ValueError(f"auto_pgd: norm must be 'linf' or 'l2', got {norm!r}")
+        if loss not in ("ce", "cw", "dlr"):
+            raise ValueError(f"auto_pgd: loss must be 'ce', 'cw' or 'dlr', got {loss!r}")
         if targeted and labels is None:
             raise ValueError("auto_pgd: a targeted attack needs labels (the target classes)")
         if not eps >= 0:
@@ -504,6 +532,7 @@ class Predictor:
             labels = self._forward(x0.view(B, 1, 28, 28))[1]
         else:
             labels = self._labels("auto_pgd", labels, B, check_range=True)
+        true_labels = self._true_labels("auto_pgd", loss, targeted, labels, true_labels, x0, B)
         eps_n, _, lo, hi = adversarial_units(eps, int(steps), None)
         if self.native:
             from .ops.apgd import fused_auto_pgd as attack
@@ -512,7 +541,8 @@ class Predictor:
         x_adv = loss_best = None
         for _ in range(int(restarts)):
             x_init = _random_start(x0, eps_n, lo, hi, norm, generator, self.device) if random_start else None
-            xr, lr = attack(self.net, x0, labels, eps_n, int(steps), lo, hi, x_init, norm=norm, targeted=targeted)
+            xr, lr = attack(self.net, x0, labels, eps_n, int(steps), lo, hi, x_init, norm=norm, targeted=targeted,
+                            loss=loss, true_labels=true_labels)
             if x_adv is None:
                 x_adv, loss_best = xr, lr
             else:
@@ -523,10 +553,12 @@ class Predictor:
         return x_adv, self._forward(x_adv)[0], loss_best
 
     def robust_evaluate_apgd(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
-                             batch_size: int = 1000, norm: str = "linf", restarts: int = 1, generator=None):
+                             batch_size: int = 1000, norm: str = "linf", restarts: int = 1, generator=None,
+                             loss: str = "ce"):
         """(loss_sum, correct, n) as ``robust_evaluate``, with Auto-PGD as the attack: the images after an untargeted
         ``auto_pgd`` against their true labels, ``batch_size`` images at a time; ``restarts`` > 1: that many runs
-        from random starts drawn from ``generator``, else one run from the clean image.  There is no step size."""
+        from random starts drawn from ``generator``, else one run from the clean image.  There is no step size.
+        ``loss``: the loss the attack ascends (``auto_pgd``); ``loss_sum`` is the NLL of the attacked images."""
         if norm not in ("linf", "l2"):
             raise ValueError(f"robust_evaluate_apgd: norm must be 'linf' or 'l2', got {norm!r}")
         n = int(labels.shape[0])
@@ -535,15 +567,15 @@ class Predictor:
         if batch_size < 1:
             raise ValueError("robust_evaluate_apgd: batch_size must be positive")
         lab = labels.long().to(self.device)
-        loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
         hits = torch.zeros((), dtype=torch.int64, device=self.device)
         for i in range(0, n, batch_size):
             y = lab[i:i + batch_size]
             _, lp, _ = self.auto_pgd(images_u8[i:i + batch_size], y, eps, steps, norm=norm,
-                                     random_start=restarts > 1, restarts=restarts, generator=generator)
-            loss += F.nll_loss(lp, y, reduction='none').double().sum()
+                                     random_start=restarts > 1, restarts=restarts, generator=generator, loss=loss)
+            total += F.nll_loss(lp, y, reduction='none').double().sum()
             hits += (lp.argmax(dim=1) == y).sum()
-        return float(loss.item()), int(hits.item()), n
+        return float(total.item()), int(hits.item()), n
 
     def square_attack(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.3, queries: int = 1000,
                       p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64):
@@ -624,6 +656,66 @@ class Predictor:
         spent = torch.cat(spent)
         median = float(spent.quantile(0.5)) if spent.numel() else None
         return float(loss.item()), int(hits.item()), n, median
+
+    def robust_evaluate_ensemble(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
+                                 n_targets: int = 9, queries: int = 5000, batch_size: int = 1000,
+                                 p_init: float = 0.8, seed: int = 0):
+        """(correct, n, after): the worst case over an ensemble of L-inf attacks of radius ``eps`` - how many of the
+        ``n`` images are still classified correctly after all of them.  Per batch of ``batch_size`` images, each
+        stage runs only on the images that are still correct (a batch with none left skips the stage):
+
+            clean    the predictor's forward of the clean images;
+            apgd_ce  ``auto_pgd`` with ``loss="ce"`` and ``steps`` updates, from the clean point;
+            apgd_t   for k = 1 .. ``n_targets``: ``auto_pgd(targeted=True, loss="dlr")`` towards the k-th most likely
+                     class other than the label at the clean point (ties: the lower class);
+            square   ``square_attack`` with up to ``queries`` queries, ``p_init`` and ``seed``, an image's id its row
+                     index in ``images_u8`` (its squares do not depend on the batch or on what broke before).
+
+        An image is broken when the predictor's own forward of the returned point misses the label.  ``after``: a
+        dict of the survivors after each stage, in the order above.  ``n_targets`` in 0..9 and ``queries`` >= 0; 0
+        skips the stage.  This is not AutoAttack's standard set: FAB-T is not built, and APGD starts from the clean
+        point, not from random starts."""
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("robust_evaluate_ensemble: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("robust_evaluate_ensemble: batch_size must be positive")
+        if isinstance(n_targets, bool) or n_targets != int(n_targets) or not 0 <= n_targets <= 9:
+            raise ValueError(f"robust_evaluate_ensemble: n_targets must be an integer in 0..9, got {n_targets}")
+        if isinstance(queries, bool) or queries != int(queries) or queries < 0:
+            raise ValueError(f"robust_evaluate_ensemble: queries must be a non-negative integer, got {queries}")
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"robust_evaluate_ensemble: steps must be a positive integer, got {steps}")
+        if not eps >= 0:
+            raise ValueError(f"robust_evaluate_ensemble: eps must be >= 0, got {eps}")
+        lab = labels.long().to(self.device)
+        after = {"clean": 0, "apgd_ce": 0, "apgd_t": 0, "square": 0}
+        for i in range(0, n, batch_size):
+            xb, y = images_u8[i:i + batch_size], lab[i:i + batch_size]
+            rows = torch.arange(i, i + y.shape[0], device=self.device)
+            lp0 = self._forward(xb)[0]
+            alive = lp0.argmax(dim=1) == y
+            after["clean"] += int(alive.sum())
+            # the k-th most likely class other than the label: a stable descending sort with the label pushed last
+            order = lp0.clone().scatter_(1, y[:, None], float("-inf")).sort(dim=1, descending=True, stable=True)[1]
+
+            def stage(attack):
+                at = alive.nonzero()[:, 0]
+                if at.numel():
+                    lp = attack(at)
+                    alive[at] = lp.argmax(dim=1) == y[at]
+
+            stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], y[at], eps, steps, loss="ce")[1])
+            after["apgd_ce"] += int(alive.sum())
+            for k in range(int(n_targets)):
+                stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], order[at, k], eps, steps, targeted=True, loss="dlr",
+                                               true_labels=y[at])[1])
+            after["apgd_t"] += int(alive.sum())
+            if queries > 0:
+                stage(lambda at: self.square_attack(xb[at.to(xb.device)], y[at], eps, queries, p_init, seed,
+                                                    ids=rows[at])[1])
+            after["square"] += int(alive.sum())
+        return after["square"], n, after
 
     def minimum_norm(self, x: torch.Tensor, labels: torch.Tensor | None = None, steps: int = 50,
                      overshoot: float = 0.02, check_every: int = 8):
@@ -793,6 +885,20 @@ class Predictor:
             raise ValueError(f"Predictor expects [B,28,28] / [B,784] / [B,1,28,28] input, got {tuple(x.shape)}")
         return B
 
+    def _true_labels(self, name: str, loss: str, targeted: bool, labels: torch.Tensor, true_labels, x0: torch.Tensor,
+                     B: int):
+        """The true classes the targeted DLR loss reads beside the targets ``labels`` (None for every other loss):
+        ``true_labels`` checked, or the class predicted on the clean rows ``x0``; no row's target may equal it."""
+        if not (targeted and loss == "dlr"):
+            return None
+        if true_labels is None:
+            true_labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            true_labels = self._labels(name, true_labels, B, check_range=True)
+        if bool((true_labels == labels).any()):
+            raise ValueError(f"{name}: the targeted DLR loss needs every target to differ from its row's true label")
+        return true_labels
+
     def _rows_native(self, x: torch.Tensor, B: int) -> torch.Tensor:
         """The rows the native loops take, contiguous [B, 784] on the predictor's device: uint8 images stay uint8
         (the kernels normalise them), float input becomes detached float32."""
@@ -885,6 +991,20 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='Auto-PGD runs per image; more than one: each from a random start (default: 1, from the '
                          'clean image)')
     ap.add_argument('--apgd-seed', type=int, default=0, help='seed of the random starts (default: 0)')
+    ap.add_argument('--apgd-loss', choices=('ce', 'cw', 'dlr'), default='ce',
+                    help='loss Auto-PGD ascends: cross-entropy, the CW margin or the DLR loss (default: ce)')
+    ap.add_argument('--ensemble-eps', type=float, default=None, metavar='E',
+                    help='also report the accuracy of the images that survive every attack of an L-inf ensemble of '
+                         'radius E, in pixel units on the [0, 1] scale: Auto-PGD on the cross-entropy, targeted '
+                         'Auto-PGD on the DLR loss towards the T most likely other classes, the Square Attack; not '
+                         "AutoAttack's standard set: no FAB-T, no random starts (default: off)")
+    ap.add_argument('--ensemble-steps', type=int, default=100, metavar='N',
+                    help='Auto-PGD iterations of the ensemble (default: 100)')
+    ap.add_argument('--ensemble-targets', type=int, default=9, metavar='T',
+                    help='target classes of the targeted stage, 0..9 (default: 9)')
+    ap.add_argument('--ensemble-queries', type=int, default=5000, metavar='Q',
+                    help='most queries per image of the Square Attack stage; 0: skip it (default: 5000)')
+    ap.add_argument('--ensemble-seed', type=int, default=0, help='seed of the squares (default: 0)')
     ap.add_argument('--square-eps', type=float, default=None, metavar='E',
                     help='also report loss and accuracy under the L-inf Square Attack (score-based, black-box: no '
                          'gradient is read) of radius E, in pixel units on the [0, 1] scale (default: off)')
@@ -935,16 +1055,29 @@ def certified_line(sigma: float, n: int, alpha: float, radius: float, correct: i
             f"Accuracy: {correct}/{m} ({100.0 * correct / m:.0f}%), abstained {abstained}")
 
 
+def _loss_tag(loss_name: str) -> str:
+    return "" if loss_name == "ce" else f", loss={loss_name}"
+
+
 def adversarial_line(eps: float, steps: int, loss: float, correct: int, n: int, norm: str = "linf") -> str:
     """The ``Test set:`` line's figures (``utils.logging.test_line``) for the attacked split."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
     return f"Adversarial set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}): {figures}"
 
 
-def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: int, n: int, norm: str = "linf") -> str:
-    """The ``Auto-PGD set`` line of ``mnist_predict.py --apgd-eps``, in the number formats of ``adversarial_line``."""
+def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: int, n: int, norm: str = "linf",
+                  loss_name: str = "ce") -> str:
+    """The ``Auto-PGD set`` line of ``mnist_predict.py --apgd-eps``, in the number formats of ``adversarial_line``;
+    ``loss_name``: the loss the attack ascended, named in the line when it is not the cross-entropy."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
-    return f"Auto-PGD set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}, restarts={restarts}): {figures}"
+    return (f"Auto-PGD set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}, restarts={restarts}"
+            f"{_loss_tag(loss_name)}): {figures}")
+
+
+def ensemble_line(eps: float, targets: int, correct: int, n: int) -> str:
+    """The ``Ensemble set`` line of ``mnist_predict.py --ensemble-eps``."""
+    return (f"Ensemble set (Linf eps={eps:g}: apgd-ce, apgd-t x {targets}, square): "
+            f"Accuracy: {correct}/{n} ({100.0 * correct / n:.0f}%)")
 
 
 def square_line(eps: float, queries: int, p_init: float, loss: float, correct: int, n: int, median) -> str:
@@ -1071,11 +1204,14 @@ def predict_main(argv=None) -> int:
         gen = torch.Generator().manual_seed(args.apgd_seed) if args.apgd_restarts > 1 else None
         ap_loss, ap_correct, _ = predictor.robust_evaluate_apgd(images, data.targets, args.apgd_eps, args.apgd_steps,
                                                                 args.batch_size, norm=args.apgd_norm,
-                                                                restarts=args.apgd_restarts, generator=gen)
+                                                                restarts=args.apgd_restarts, generator=gen,
+                                                                loss=args.apgd_loss)
         print(auto_pgd_line(args.apgd_eps, args.apgd_steps, args.apgd_restarts, ap_loss / n, ap_correct, n,
-                            args.apgd_norm))
+                            args.apgd_norm, args.apgd_loss))
         record.update(apgd_eps=args.apgd_eps, apgd_steps=args.apgd_steps, apgd_norm=args.apgd_norm,
                       apgd_restarts=args.apgd_restarts, apgd_loss=ap_loss / n, apgd_correct=ap_correct)
+        if args.apgd_loss != "ce":
+            record.update(apgd_loss_name=args.apgd_loss)
     if args.square_eps is not None:
         sq_loss, sq_correct, _, sq_median = predictor.robust_evaluate_square(
             images, data.targets, args.square_eps, args.square_queries, args.batch_size, args.square_p_init,
@@ -1085,6 +1221,14 @@ def predict_main(argv=None) -> int:
         record.update(square_eps=args.square_eps, square_queries=args.square_queries,
                       square_p_init=args.square_p_init, square_seed=args.square_seed, square_loss=sq_loss / n,
                       square_correct=sq_correct, square_median_queries=sq_median)
+    if args.ensemble_eps is not None:
+        en_correct, _, en_after = predictor.robust_evaluate_ensemble(
+            images, data.targets, args.ensemble_eps, args.ensemble_steps, args.ensemble_targets, args.ensemble_queries,
+            args.batch_size, seed=args.ensemble_seed)
+        print(ensemble_line(args.ensemble_eps, args.ensemble_targets, en_correct, n))
+        record.update(ensemble_eps=args.ensemble_eps, ensemble_steps=args.ensemble_steps,
+                      ensemble_targets=args.ensemble_targets, ensemble_queries=args.ensemble_queries,
+                      ensemble_seed=args.ensemble_seed, ensemble_correct=en_correct, ensemble_after=en_after)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

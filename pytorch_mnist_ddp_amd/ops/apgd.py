@@ -14,23 +14,30 @@ stream, with no autograd ``Function``, no allocation and no host sync:
 ``steps`` updates take ``steps + 1`` rounds: round 0 has ``first`` (it sets the state up and makes update 1), round
 ``steps`` has ``last`` (it only brings the best point up to date with the loss of the last iterate), and the rounds
 ``functional.apgd_checkpoints`` names close a window.
+
+``loss="cw"`` / ``"dlr"`` put ``head_margin`` in ``head_train``'s place (``GradChain(loss=...)``): ``apgd_step`` only
+sees a loss per row and dx, so the CW margin and the DLR loss (targeted: the APGD-T objective) take the same six
+launches.
 """
 from __future__ import annotations
 
 import torch
 
 from . import native
-from .chain import GradChain
+from .chain import GradChain, chain_loss, margin_operands
 from .functional import APGD_LOSS_BEST, apgd_checkpoints
 from .fused_net import fused_state
 
 
 def fused_auto_pgd(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int, lo: float, hi: float,
-                   x_init: torch.Tensor | None = None, norm: str = "linf", targeted: bool = False):
+                   x_init: torch.Tensor | None = None, norm: str = "linf", targeted: bool = False, loss: str = "ce",
+                   true_labels: torch.Tensor | None = None):
     """``(x_best, loss_best)``: Auto-PGD with ``steps`` updates on the NLL of ``labels``, in inference semantics (no
     dropout), starting from ``x_init`` (default ``x0``), inside the ``norm`` ball of radius ``eps`` around ``x0`` and
     the range [lo, hi] (``functional.apgd_step_reference`` has the exact form).  ``targeted``: ``labels`` are the
-    targets and their NLL is descended.
+    targets and their NLL is descended.  ``loss``: "ce", or "cw" / "dlr" (``functional.margin_loss_reference``) in the
+    NLL's place throughout, the returned loss included; targeted "dlr" is the "dlr_t" form (the negative of the APGD-T
+    objective, descended), which also reads ``true_labels`` ([B], required).
 
     ``x0`` / ``x_init``: float32 [B, 784] normalised images on the net's device; ``labels``: [B] integers in [0, 10)
     (not checked here: ``Predictor.auto_pgd`` does); ``eps``, ``lo``, ``hi`` in normalised units.  Returns the float32
@@ -42,6 +49,7 @@ def fused_auto_pgd(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, step
         raise ValueError("fused_auto_pgd: steps must be at least 1")
     if norm not in ("linf", "l2"):
         raise ValueError(f"fused_auto_pgd: norm must be 'linf' or 'l2', got {norm!r}")
+    kind = chain_loss("fused_auto_pgd", loss, targeted)
     st = fused_state(net)
     st.sync()                                   # once: the bf16 shadows follow the parameters
     dev = st.ms.device
@@ -62,13 +70,14 @@ def fused_auto_pgd(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, step
     window = dict(apgd_checkpoints(steps))
     sign = -1.0 if targeted else 1.0
     l2 = norm == "l2"
-    chain = GradChain(st, B)
+    lab, tgt = margin_operands("fused_auto_pgd", kind, lab, true_labels, B, dev)
+    chain = GradChain(st, B, kind)
     C, s, p = native.load(), native.stream_handle(), native.ptr
-    px, plab, pdx, ploss = p(x), p(lab), p(dx), chain.loss_rows
+    px, plab, ptgt, pdx, ploss = p(x), p(lab), p(tgt), p(dx), chain.loss_rows
     rest = (p(x0), px, p(x_old), p(x_best), p(g_best), p(fstate), p(istate), sign, eps, lo, hi, l2)
     run, grad, step = chain.run, chain.input_grad, C.apgd_step
     for j in range(steps + 1):
-        run(px, plab, B)
+        run(px, plab, B, ptgt)
         grad(pdx, B)
         step(pdx, ploss, *rest, j == 0, j == steps, window.get(j, 0), B, s)
     chain.release()                             # last use enqueued: the next taker is stream ordered after it

@@ -123,6 +123,129 @@ def head_train(ms, labels: torch.Tensor, idx: torch.Tensor | None, buf: StepBuff
                     p(buf.loss_rows), p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), B, round_up(B, 32), _s())
 
 
+MARGIN_KINDS = {"cw": 0, "dlr": 1, "dlr_t": 2}      # head_margin loss codes (csrc/include/kernels.h MarginKind)
+DLR_GUARD = 1e-12                                   # added to the DLR denominators (the authors' guard)
+
+
+def first_max_excluding(z: torch.Tensor, taken: torch.Tensor) -> torch.Tensor:
+    """int64 [R]: per row of ``z`` [R, C] the first maximum over the classes whose ``taken`` [R, C] flag is False,
+    by explicit > comparisons in ascending class order - the first of equals wins, a NaN never wins over an earlier
+    class.  The selection rule of ``head_margin`` (at least one class per row must be free)."""
+    R, C = z.shape
+    idx = torch.full((R,), -1, dtype=torch.long, device=z.device)
+    best = torch.zeros(R, dtype=z.dtype, device=z.device)
+    for c in range(C):
+        take = ~taken[:, c] & ((idx < 0) | (z[:, c] > best))
+        best = torch.where(take, z[:, c], best)
+        idx = torch.where(take, torch.full_like(idx, c), idx)
+    return idx
+
+
+def margin_selections(z: torch.Tensor, labels: torch.Tensor):
+    """``(o, pi1, pi2, pi3, pi4)``, int64 [R] each, of the logits (or log-probs) ``z`` [R, 10]: ``o`` the first
+    maximum over j != label, ``pi1`` the first maximum, ``pi2`` .. ``pi4`` the first maximum over the classes not yet
+    taken (``first_max_excluding``)."""
+    z = z.detach()
+    cls = torch.arange(z.shape[1], device=z.device)[None, :]
+    o = first_max_excluding(z, cls == labels.long().reshape(-1, 1))
+    taken = torch.zeros_like(z, dtype=torch.bool)
+    pis = []
+    for _ in range(4):
+        pis.append(first_max_excluding(z, taken))
+        taken = taken | (cls == pis[-1][:, None])
+    return (o, *pis)
+
+
+def margin_loss_reference(logits_or_logp: torch.Tensor, labels: torch.Tensor, kind: str,
+                          targets: torch.Tensor | None = None) -> torch.Tensor:
+    """The per-row margin loss [R] of ``head_margin`` in differentiable torch ops on any device, in the dtype of the
+    [R, 10] logits - or log-probs: the losses are shift-invariant.  ``kind``, with y = ``labels`` and the selections
+    of ``margin_selections`` (explicit, not ``torch.sort``, so ties are defined as in the kernel):
+
+        "cw":     z[o] - z[y]
+        "dlr":    (z[o] - z[y]) / ((z[pi1] - z[pi3]) + 1e-12)
+        "dlr_t":  (z[y] - z[t]) / ((z[pi1] - 0.5 (z[pi3] + z[pi4])) + 1e-12),  t = ``targets`` (t != y)
+
+    Autograd treats the selections as constants; the gradient it gives is the ``dl`` of the kernel at scale 1."""
+    if kind not in MARGIN_KINDS:
+        raise ValueError(f"margin_loss_reference: kind must be one of {sorted(MARGIN_KINDS)}, got {kind!r}")
+    if kind == "dlr_t" and targets is None:
+        raise ValueError("margin_loss_reference: the targeted DLR loss needs targets")
+    z = logits_or_logp
+    y = labels.long().reshape(-1).to(z.device)
+    o, p1, _, p3, p4 = margin_selections(z, y)
+    at = lambda i: z.gather(1, i[:, None]).squeeze(1)                                       # noqa: E731
+    if kind == "cw":
+        return at(o) - at(y)
+    if kind == "dlr":
+        return (at(o) - at(y)) / ((at(p1) - at(p3)) + DLR_GUARD)
+    t = targets.long().reshape(-1).to(z.device)
+    return (at(y) - at(t)) / ((at(p1) - 0.5 * (at(p3) + at(p4))) + DLR_GUARD)
+
+
+def head_margin_reference(z1part: torch.Tensor, b_fc1: torch.Tensor, w_fc2: torch.Tensor, b_fc2: torch.Tensor,
+                          labels: torch.Tensor, kind: str, targets: torch.Tensor | None = None, scale: float = 1.0,
+                          dtype=None) -> dict:
+    """``head_margin`` in torch ops on any device, in ``dtype`` (default: that of ``z1part`` [ksplit, R, 128]): z1 =
+    bias + the partials summed in chunk order, h = relu(z1), the logits, the loss rows, ``dl`` [R, 10] with the terms
+    added in the kernel's order, and dz1 = (z1 > 0) (dl . w_fc2), all before any rounding to bf16."""
+    if kind not in MARGIN_KINDS:
+        raise ValueError(f"head_margin_reference: kind must be one of {sorted(MARGIN_KINDS)}, got {kind!r}")
+    if kind == "dlr_t" and targets is None:
+        raise ValueError("head_margin_reference: the targeted DLR loss needs targets")
+    dt = z1part.dtype if dtype is None else dtype
+    s = torch.zeros_like(z1part[0], dtype=dt)
+    for c in range(z1part.shape[0]):
+        s = s + z1part[c].to(dt)
+    z1 = b_fc1.to(dt) + s
+    h = torch.relu(z1)
+    z = h @ w_fc2.to(dt).t() + b_fc2.to(dt)
+    y = labels.long().reshape(-1).to(z.device)
+    o, p1, _, p3, p4 = margin_selections(z, y)
+    at = lambda i: z.gather(1, i[:, None]).squeeze(1)                                       # noqa: E731
+    dl = torch.zeros_like(z)
+    add = lambda i, v: dl.scatter_add_(1, i[:, None], v[:, None])                           # noqa: E731
+    sc = torch.full_like(z[:, 0], float(scale))
+    if kind == "cw":
+        loss = at(o) - at(y)
+        add(o, sc)
+        add(y, -sc)
+    elif kind == "dlr":
+        d = (at(p1) - at(p3)) + DLR_GUARD
+        loss = (at(o) - at(y)) / d
+        add(o, sc / d)
+        add(y, -(sc / d))
+        q = (sc * loss) / d
+        add(p1, -q)
+        add(p3, q)
+    else:
+        t = targets.long().reshape(-1).to(z.device)
+        d = (at(p1) - 0.5 * (at(p3) + at(p4))) + DLR_GUARD
+        loss = (at(y) - at(t)) / d
+        add(y, sc / d)
+        add(t, -(sc / d))
+        q = (sc * loss) / d
+        add(p1, -q)
+        add(p3, 0.5 * q)
+        add(p4, 0.5 * q)
+    dz1 = (dl @ w_fc2.to(dt)) * (z1 > 0)
+    return dict(z1=z1, h=h, logits=z, loss=loss, dl=dl, dz1=dz1, d=None if kind == "cw" else d)
+
+
+def head_margin(ms, labels: torch.Tensor, buf: StepBuffers, kind: str, targets: torch.Tensor | None = None,
+                scale: float = 1.0) -> None:
+    """One launch of ``head_margin`` (csrc/kernels/fc_head.hip) on ``buf.z1part``: ``head_train``'s forward without
+    dropout and the ``kind`` margin loss (``margin_loss_reference``) of the int32 [B] ``labels`` (``"dlr_t"``: and
+    int32 [B] ``targets``) into ``buf.loss_rows``, ``scale`` times its gradient into ``buf.dl_bf`` / ``buf.dz1``,
+    relu(z1) into ``buf.h_bf``, under ``head_train``'s padding contract."""
+    if kind not in MARGIN_KINDS:
+        raise ValueError(f"head_margin: kind must be one of {sorted(MARGIN_KINDS)}, got {kind!r}")
+    p, w = native.ptr, param_ptrs(ms)
+    B = buf.B
+    _C().head_margin(p(buf.z1part), w.f1b, w.f2w, w.f2b, p(labels), p(targets), MARGIN_KINDS[kind], float(scale),
+                     p(buf.loss_rows), p(buf.dz1), p(buf.h_bf), p(buf.dl_bf), B, round_up(B, 32), _s())
+
+
 def head_eval(ms, labels: torch.Tensor | None, idx: torch.Tensor | None, buf: StepBuffers) -> None:
     p, w = native.ptr, param_ptrs(ms)
     _C().head_eval(p(buf.z1part), w.f1b, w.f2w, w.f2b, p(labels), p(idx), p(buf.loss_rows), p(buf.correct),

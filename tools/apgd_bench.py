@@ -12,6 +12,13 @@ and the min-max spread), in us per iteration:
   step alone  ``apgd_step`` (a middle launch that closes a window) back to back on fixed operands, us per launch
 
     python tools/apgd_bench.py [--out profiles/apgd/apgd_bench.txt]
+
+``--loss ce,cw,dlr`` prints another table instead: per batch the native L-inf loop under each of the named losses
+(``fused_auto_pgd(loss=...)``, alternated in the same process; the launch count is the same, ``head_margin`` stands in
+``head_train``'s place), and the head alone: ``head_train`` (no dropout, loss scale 1) against ``head_margin`` of each
+kind, back to back on the partials of one forward, us per launch.
+
+    python tools/apgd_bench.py --loss ce,cw,dlr [--out profiles/apgd/apgd_bench_loss.txt]
 """
 import argparse
 import os
@@ -58,11 +65,60 @@ def host_loop(pr, x0, y, eps, steps, norm):
     return state[2]
 
 
+def loss_table(a, net, dev, batches, images, targets):
+    """The ``--loss`` table (module docstring)."""
+    from pytorch_mnist_ddp_amd.ops.fused_net import _step_state, fused_state
+    losses = [v for v in a.loss.split(",") if v]
+    for v in losses:
+        if v not in ("ce", "cw", "dlr"):
+            raise SystemExit(f"apgd_bench: --loss takes ce, cw, dlr, got {v!r}")
+    kinds = [v for v in losses if v != "ce"] + (["dlr_t"] if "dlr" in losses else [])
+    rounds = a.iters + 1
+    eps = 0.1 / MNIST_STD
+    st = fused_state(net)
+    st.sync()
+    ms = st.ms
+    nodrop = _step_state(st, False, dev, 1)          # step 0, STEP_FLAG_NO_DROPOUT: the chains' own state
+    head = " ".join(f"{'apgd ' + v:>29}" for v in losses) + " " + " ".join(
+        f"{h:>29}" for h in ["head_train"] + ["head_margin " + k for k in kinds])
+    lines = [f"apgd_bench --loss: L-inf, {a.iters} updates ({rounds} rounds) a sample, {a.rounds} samples; us per "
+             f"iteration (apgd) and per launch (head alone), median [min-max]", f"{'B':>5} {head}"]
+    for B in batches:
+        y = targets[:B]
+        x0 = _PIXEL_LUT.to(dev)[images[:B].long()]
+        buf = Fk.StepBuffers.allocate(B, dev)
+        lab = y.to(torch.int32).contiguous()
+        tgt = ((lab + 1) % 10).contiguous()
+        Fk.trunk_fwd(ms, None, None, buf, True, state=nodrop, xin=x0)
+        Fk.fc1_fwd(ms, buf)
+        arms = {"apgd " + v: (lambda v=v: fused_auto_pgd(net, x0, y, eps, a.iters, PIXEL_LO, PIXEL_HI, loss=v))
+                for v in losses}
+        reps = {k: max(1, 64 // B) for k in arms}
+        per = {k: rounds for k in arms}
+        arms["head_train"] = lambda: Fk.head_train(ms, lab, None, buf, state=nodrop, inv_batch=1.0)
+        for k in kinds:
+            arms["head_margin " + k] = lambda k=k: Fk.head_margin(ms, lab, buf, k, tgt if k == "dlr_t" else None)
+        for k in arms:
+            reps.setdefault(k, 200)
+            per.setdefault(k, 1)
+        for f in arms.values():
+            timed(f, 1)
+        res = {k: [] for k in arms}
+        for _ in range(a.rounds):
+            for k, f in arms.items():
+                res[k].append(timed(f, reps[k]) / per[k])
+        lines.append(f"{B:>5} " + " ".join(f"{fmt(res[k]):>29}" for k in arms))
+    return lines
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batches", type=str, default="1,64,200,1000")
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--loss", default=None, metavar="L1,L2,...",
+                    help="the loss table instead: the native L-inf loop under each of these losses (ce, cw, dlr) and "
+                         "head_margin alone against head_train")
     ap.add_argument("--out", default=None, help="also write the table to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -77,6 +133,14 @@ def main() -> int:
     images = test.device_images(dev).reshape(-1, 784).contiguous()
     targets = test.targets.long().to(dev)
     rounds = a.iters + 1
+    if a.loss:
+        text = "\n".join(loss_table(a, net, dev, batches, images, targets))
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return 0
     lines = [f"apgd_bench: {a.iters} updates ({rounds} rounds) a sample, {a.rounds} samples; us per iteration, median "
              f"[min-max]",
              f"{'B':>5} {'norm':>5} {'native':>29} {'l2 pgd':>29} {'host loop':>29} {'ratio':>6} {'apgd_step alone':>29}"]
