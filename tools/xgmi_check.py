@@ -49,9 +49,18 @@ def _expect(torch, world: int, n: int, it: int, dev):
 
 def init_rank(rank: int, world: int, port: int, same_device: bool):
     """A spawned rank's set-up: its GPU (``same_device``: all ranks on GPU 0) and the gloo process group on
-    127.0.0.1 that carries the handle exchange and the verdicts.  Returns the torch device."""
+    127.0.0.1 that carries the handle exchange and the verdicts.  Returns the torch device.
+
+    The ranks share this host's CPUs: torch's intra-op pool gets an equal share of the affinity mask (never more
+    than it had).  ``world`` pools of one thread per CPU each oversubscribe a host with no more CPUs than one pool,
+    and the CPU work between the launches (inputs, oracles, checks) then runs many times slower."""
     import torch
     import torch.distributed as dist
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        cpus = os.cpu_count() or 1
+    torch.set_num_threads(max(1, min(torch.get_num_threads(), cpus // world)))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     d = 0 if same_device else rank % torch.cuda.device_count()
     torch.cuda.set_device(d)
