@@ -45,6 +45,7 @@ void mnist::preload_all_kernels() {
   preload_deepfool();
   preload_apgd();
   preload_square();
+  preload_fab();
 }
 
 namespace {
@@ -553,6 +554,29 @@ PYBIND11_MODULE(_C, m) {
      py::arg("M"), py::arg("stream"),
      "one L2 DeepFool step per image from its ten gradient rows and losses: r_tot += the step to the nearest "
      "linearised boundary, x = rows = clamp(x0 + (1 + overshoot) r_tot, lo, hi); crossed / stuck images freeze");
+
+  // ---------------- Fast Adaptive Boundary attack ----------------
+  m.attr("FAB_LINF") = (int)FAB_LINF;
+  m.attr("FAB_L2") = (int)FAB_L2;
+  m.attr("FAB_RUNNING") = (int)FAB_RUNNING;
+  m.attr("FAB_DONE") = (int)FAB_DONE;
+  m.attr("FAB_STUCK") = (int)FAB_STUCK;
+  m.def("fab_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t y, uintptr_t x0, uintptr_t x, uintptr_t x_best,
+                       uintptr_t norm_best, uintptr_t rows, uintptr_t status, uintptr_t iters, uintptr_t proj,
+                       float alpha_max, float eta, float beta, float lo, float hi, int norm, bool last, int M,
+                       uintptr_t stream) {
+    FabStepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const int32_t>(y), P<const float>(x0), P<float>(x),
+                  P<float>(x_best), P<float>(norm_best), P<float>(rows), P<int32_t>(status), P<int32_t>(iters),
+                  P<float>(proj), alpha_max, eta, beta, lo, hi, last ? 1 : 0};
+    launch_fab_step(a, M, norm, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("y"), py::arg("x0"), py::arg("x"), py::arg("x_best"),
+     py::arg("norm_best"), py::arg("rows"), py::arg("status"), py::arg("iters"), py::arg("proj"),
+     py::arg("alpha_max"), py::arg("eta"), py::arg("beta"), py::arg("lo"), py::arg("hi"), py::arg("norm"),
+     py::arg("last"), py::arg("M"), py::arg("stream"),
+     "one FAB iteration per image from its ten gradient rows and losses: a crossed iterate is recorded when nearer "
+     "and pulled back towards x0, any other steps along the two box-constrained projections onto the nearest "
+     "linearised boundary");
 
   // ---------------- Auto-PGD ----------------
   m.def("apgd_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t x0, uintptr_t x, uintptr_t x_old, uintptr_t x_best,

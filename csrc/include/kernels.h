@@ -434,6 +434,44 @@ struct DeepfoolStepArgs {
 };
 void launch_deepfool_step(const DeepfoolStepArgs& a, int M, hipStream_t s);   // M in [1, DF_MAX_M], overshoot >= 0
 
+// ---------------- Fast Adaptive Boundary attack (fab.hip; Croce & Hein 2020), untargeted, L-inf or L2 ----------------
+// The ten-rows-per-image layout of the DeepFool kernels (deepfool_init starts a run; its r_tot output serves as
+// x_best).  fab_step, per image with y = y[i], f_k = loss_y - loss_k, w_k = g_y - g_k, |.| the norm of the launch and q
+// its dual exponent (1 for L-inf, 2 for L2):
+//   status != FAB_RUNNING                        -> nothing is stored (frozen); y outside [0, 10): FAB_STUCK
+//   crossed (deepfool_step's rule)               -> u = |x - x0|; u < norm_best: x_best = x, norm_best = u;
+//                                                   u == 0: status = FAB_DONE; else, unless `last`:
+//                                                   x = clamp(x0 + beta (x - x0)) -> x[i] and the ten rows, iters += 1
+//   not crossed, `last`                          -> nothing is stored
+//   l = the first smallest (|f_k| + DF_SLACK) / |w_k|_q in ascending k (deepfool_step's skips); none left: a NaN ratio
+//       fills x[i], the rows and proj with NaN (iters += 1), else status = FAB_STUCK and nothing else is stored
+//   w = w_l, r1 = f_l, r2 = f_l + sum w (x0 - x); d1 = P(x, r1), d2 = P(x0, r2); alpha = min(|d1| / (|d1| + |d2|),
+//   alpha_max) (0 / 0 -> 0); x = clamp((1 - alpha) (x + eta d1) + alpha (x0 + eta d2), lo, hi) -> x[i] and the ten
+//   rows; iters += 1; proj[i] = {d1, d2} when given
+// P(v, r): the delta of smallest norm with r + w . delta = 0 and lo <= v + delta <= hi (fab.hip: a sort of the 784
+// breakpoints, a scan, the first segment that reaches |r|; the hyperplane missing the box sends every element to its
+// bound).  Rows and entries past M are not written.  The fp32 row arrays are 16-byte aligned.
+enum FabNorm { FAB_LINF = 0, FAB_L2 = 1 };
+enum FabStatus { FAB_RUNNING = 0, FAB_DONE = 1, FAB_STUCK = 2 };
+struct FabStepArgs {
+  const float* dx;            // fp32 [10 M][784] gradient rows
+  const float* loss_rows;     // [10 M] -log p_c of row 10 i + c
+  const int32_t* y;           // [M] the class being left
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* x;                   // fp32 [M][784] the iterate
+  float* x_best;              // fp32 [M][784] the nearest crossed point so far
+  float* norm_best;           // [M] its distance |x_best - x0|; +inf until a crossing is recorded
+  float* rows;                // fp32 [10 M][784]
+  int32_t* status;            // [M] FabStatus
+  int32_t* iters;             // [M] updates made
+  float* proj;                // fp32 [M][2][784] d1, d2 of a forward step, or null
+  float alpha_max, eta, beta; // alpha_max in [0, 1], eta >= 1, beta in (0, 1]
+  float lo, hi;               // valid range in normalised units
+  int last;                   // the round after the last update: only the best point is brought up to date
+};
+// M in [1, DF_MAX_M]; norm: FabNorm
+void launch_fab_step(const FabStepArgs& a, int M, int norm, hipStream_t s);
+
 // ---------------- Auto-PGD (apgd.hip; Croce & Hein 2020) ----------------
 // One iteration's per-image update in one launch, one workgroup per image, fp32, no atomics: dx / loss_rows are the
 // gradient chain's outputs at the iterate x (input_grad's plain form, head_train's -log p_label).  With L = sign *
@@ -583,6 +621,7 @@ void preload_attr();
 void preload_deepfool();
 void preload_apgd();
 void preload_square();
+void preload_fab();
 void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

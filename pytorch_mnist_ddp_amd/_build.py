@@ -30,6 +30,9 @@ OUTPUT = os.path.join(PKG_DIR, "_C" + EXT_SUFFIX)
 #   "rw": race-window widening, 0..RACE_WIDEN_US us random sleeps before every kernel's first global
 #         read and every stream hand-off signal (device_utils.h; MNIST_AMD_RACE_WIDEN=1 loads it)
 RACE_WIDEN_US = 20
+# per-file compiler flags.  fab.hip: no packed fp32 instructions - every operation of its fixed-order sums is a scalar
+# one, rounded on its own, whatever the vectorizer would pair up
+FILE_FLAGS = {"fab.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 VARIANTS = {
     "": (os.path.join(ROOT, "build", "obj"), OUTPUT, []),
     "tl": (os.path.join(ROOT, "build", "obj_tl"), os.path.join(PKG_DIR, "_C_tl" + EXT_SUFFIX), ["-DMNIST_TIMELINE"]),
@@ -95,7 +98,8 @@ def _compile(src: str, kernel: bool, verbose: bool, variant: str = "") -> str:
     cmd = [_hipcc(), "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", *_includes(),
            *VARIANTS[variant][2]]
     if kernel:
-        cmd += ["-x", "hip", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
+        cmd += ["-x", "hip", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-slp-vectorize",
+                *FILE_FLAGS.get(os.path.basename(src), [])]
     else:
         rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
         cmd += ["-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include")]

@@ -42,6 +42,8 @@ in eval mode (where noise is drawn: the same distribution, not the same bits):
   over the reference forward; the certificate itself (``ops.smooth.certify_from_counts``) is host code on either path;
 * ``minimum_norm`` (L2 DeepFool: the smallest perturbation that leaves the class, per image; radii in pixel units):
   ``ops.deepfool.fused_minimum_norm`` / ``reference_minimum_norm``;
+* ``fab`` (the Fast Adaptive Boundary attack, Croce & Hein 2020, untargeted: the minimum-norm example in the L-inf or the
+  L2 norm, projected inside the pixel box): ``ops.fab.fused_fab`` / ``reference_fab``;
 * ``attribute`` (integrated gradients and SmoothGrad of log p_y(x): n gradient rows per image, reduced; ``sigma`` and
   scalar baselines in pixel units): ``ops.attribute.fused_attribution`` / ``reference_attribution``.
 
@@ -60,9 +62,9 @@ from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
 from .ops.chain import chain_loss
-from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES, apgd_checkpoints,
-                             apgd_step_reference, attr_path_reference, attr_reduce_reference, deepfool_step_reference,
-                             margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_sides,
+from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES,
+                             apgd_checkpoints, apgd_step_reference, attr_path_reference, attr_reduce_reference,
+                             deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_sides,
                              square_state_margin, square_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
@@ -231,6 +233,44 @@ def reference_minimum_norm(net: Net, x0: torch.Tensor, labels: torch.Tensor, ste
                     break
             x_adv[i0:i0 + m], status[i0:i0 + m], iters[i0:i0 + m], norm[i0:i0 + m] = state[1:]
     return x_adv, norm, iters, status
+
+
+def reference_fab(net: Net, x0: torch.Tensor, labels: torch.Tensor, norm: str, steps: int, alpha_max: float, eta: float,
+                  beta: float, lo: float, hi: float, history: list | None = None):
+    """``ops.fab.fused_fab`` in torch float32 on any device: untargeted FAB with the kernel's formulas
+    (``fab_step_reference``), the ten class gradients and losses of an image from one autograd pass over
+    ``Net.forward_reference`` in eval mode on its ten rows, as ``reference_minimum_norm``.  ``x0``: float32 [B, 784]
+    normalised images; same return: ``(x_best [B, 784], norm_best [B], iters int32 [B], status int32 [B])``, the
+    clean image and +inf where no point outside the label was examined.  ``steps`` + 1 rounds, the last one with
+    ``last``.  ``history``: a list that receives ``norm_best`` [B] after every round (one chunk only).  The CPU / fp32
+    path of ``Predictor.fab`` and the reference of its GPU tests."""
+    B, dev = x0.shape[0], x0.device
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(dev)
+    x_best = x0.clone()
+    norm_best = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+    iters = torch.zeros(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    mc = _REF_ROWS // DF_CLASSES
+    with _eval_mode(net):
+        for i0 in range(0, B, mc):
+            c0, yc = x0[i0:i0 + mc], y[i0:i0 + mc]
+            m = c0.shape[0]
+            lab10 = torch.arange(DF_CLASSES, device=dev).repeat(m)
+            state = (c0.clone(), torch.zeros_like(c0), norm_best[i0:i0 + m], status[i0:i0 + m], iters[i0:i0 + m])
+            for it in range(int(steps) + 1):
+                rows = state[0].repeat_interleave(DF_CLASSES, dim=0).requires_grad_()
+                with torch.enable_grad():
+                    lp = net.forward_reference(rows.view(DF_CLASSES * m, 1, 28, 28))
+                    g, = torch.autograd.grad(F.nll_loss(lp, lab10, reduction='sum'), rows)
+                loss_rows = -lp.detach()[torch.arange(DF_CLASSES * m, device=dev), lab10]
+                state = fab_step_reference(g, loss_rows, yc, c0, *state, alpha_max, eta, beta, lo, hi, norm,
+                                           last=it == int(steps))[:5]
+                if history is not None:
+                    history.append(state[2].clone())
+            x_best[i0:i0 + m] = torch.where(torch.isinf(state[2])[:, None], c0, state[1])
+            norm_best[i0:i0 + m], status[i0:i0 + m], iters[i0:i0 + m] = state[2:]
+    return x_best, norm_best, iters, status
 
 
 def _smooth_generator_seed(seed: int, image_id: int) -> int:
@@ -659,7 +699,7 @@ class Predictor:
 
     def robust_evaluate_ensemble(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
                                  n_targets: int = 9, queries: int = 5000, batch_size: int = 1000,
-                                 p_init: float = 0.8, seed: int = 0):
+                                 p_init: float = 0.8, seed: int = 0, fab_steps: int = 0):
         """(correct, n, after): the worst case over an ensemble of L-inf attacks of radius ``eps`` - how many of the
         ``n`` images are still classified correctly after all of them.  Per batch of ``batch_size`` images, each
         stage runs only on the images that are still correct (a batch with none left skips the stage):
@@ -673,8 +713,10 @@ class Predictor:
 
         An image is broken when the predictor's own forward of the returned point misses the label.  ``after``: a
         dict of the survivors after each stage, in the order above.  ``n_targets`` in 0..9 and ``queries`` >= 0; 0
-        skips the stage.  This is not AutoAttack's standard set: FAB-T is not built, and APGD starts from the clean
-        point, not from random starts."""
+        skips the stage.  ``fab_steps`` > 0 adds a stage ``fab`` after ``apgd_t``: untargeted L-inf ``fab`` with that
+        many iterations; an image is broken there when a point outside its label was found at a radius <= ``eps``,
+        and ``after`` gains the key ``fab``.  This is not AutoAttack's standard set: FAB is untargeted here (with ten
+        classes every boundary is looked at anyway), and APGD starts from the clean point, not from random starts."""
         n = int(labels.shape[0])
         if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
             raise ValueError("robust_evaluate_ensemble: images_u8 must be uint8 with one row per label")
@@ -688,8 +730,12 @@ class Predictor:
             raise ValueError(f"robust_evaluate_ensemble: steps must be a positive integer, got {steps}")
         if not eps >= 0:
             raise ValueError(f"robust_evaluate_ensemble: eps must be >= 0, got {eps}")
+        if isinstance(fab_steps, bool) or fab_steps != int(fab_steps) or fab_steps < 0:
+            raise ValueError(f"robust_evaluate_ensemble: fab_steps must be a non-negative integer, got {fab_steps}")
         lab = labels.long().to(self.device)
         after = {"clean": 0, "apgd_ce": 0, "apgd_t": 0, "square": 0}
+        if fab_steps > 0:
+            after = {"clean": 0, "apgd_ce": 0, "apgd_t": 0, "fab": 0, "square": 0}
         for i in range(0, n, batch_size):
             xb, y = images_u8[i:i + batch_size], lab[i:i + batch_size]
             rows = torch.arange(i, i + y.shape[0], device=self.device)
@@ -711,6 +757,12 @@ class Predictor:
                 stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], order[at, k], eps, steps, targeted=True, loss="dlr",
                                                true_labels=y[at])[1])
             after["apgd_t"] += int(alive.sum())
+            if fab_steps > 0:
+                at = alive.nonzero()[:, 0]
+                if at.numel():
+                    _, radii, _, found = self.fab(xb[at.to(xb.device)], y[at], "linf", int(fab_steps))
+                    alive[at] = ~(found & (radii <= eps))
+                after["fab"] += int(alive.sum())
             if queries > 0:
                 stage(lambda at: self.square_attack(xb[at.to(xb.device)], y[at], eps, queries, p_init, seed,
                                                     ids=rows[at])[1])
@@ -755,6 +807,50 @@ class Predictor:
         x_adv = x_adv.view(B, 1, 28, 28)
         lp = self._forward(x_adv)[0]
         return x_adv, norm * MNIST_STD, lp, lp.argmax(dim=1) != labels
+
+    def fab(self, x: torch.Tensor, labels: torch.Tensor | None = None, norm: str = "linf", steps: int = 100,
+            alpha_max: float = 0.1, eta: float = 1.05, beta: float = 0.9):
+        """(x_adv, radii, log_probs, found): minimum-norm adversarial examples of ``x`` by the Fast Adaptive Boundary
+        attack (Croce & Hein 2020), untargeted, in the ``norm`` "linf" or "l2", in ``minimum_norm``'s conventions.
+        ``x_adv``: float32 [B,1,28,28] in NORMALISED units, inside the valid pixel range; ``radii``: float32 [B], the
+        norm of ``x_adv - x`` in pixel units on the [0, 1] scale, +inf where the run examined no point outside the
+        label (there ``x_adv`` is the clean image); ``log_probs``: the predictor's own float32 [B,10] forward of
+        ``x_adv``; ``found``: bool [B], whether that forward no longer gives ``labels``.  An image already
+        misclassified on entry keeps ``x_adv = x``, radius 0 and is found.
+
+        ``labels`` ([B] integers): the class each image is to leave, or the class predicted on the clean input when
+        None.  ``steps`` iterations per image.  An iterate inside its class steps to a convex combination (weight at
+        most ``alpha_max`` on the clean image's) of the projections of itself and of the clean image onto the nearest
+        boundary of the classifier linearised at the iterate, each projection the smallest one that stays inside the
+        pixel box, extrapolated by ``eta`` >= 1; an iterate outside its class is kept when it is the nearest so far
+        and pulled towards the clean image by ``beta`` in (0, 1].  Differences from the authors' code: a crossed
+        round is a backward step only, there is no final search, no random restart and no targeted form, and the
+        class is chosen with DeepFool's slack constant.  Inference semantics as ``input_gradient``.  GPU with
+        ``dtype="bf16"``: the native loop ``ops.fab.fused_fab``; CPU, or ``dtype="fp32"``: ``reference_fab``."""
+        B = self._check_input(x)
+        if norm not in FAB_NORMS:
+            raise ValueError(f"fab: norm must be 'linf' or 'l2', got {norm!r}")
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"fab: steps must be a positive integer, got {steps}")
+        if not 0 <= alpha_max <= 1:
+            raise ValueError(f"fab: alpha_max must be in [0, 1], got {alpha_max}")
+        if not eta >= 1:
+            raise ValueError(f"fab: eta must be >= 1, got {eta}")
+        if not 0 < beta <= 1:
+            raise ValueError(f"fab: beta must be in (0, 1], got {beta}")
+        if labels is None:
+            labels = self._forward(x)[1]
+        else:
+            labels = self._labels("fab", labels, B, check_range=True)
+        args = (norm, int(steps), float(alpha_max), float(eta), float(beta), PIXEL_LO, PIXEL_HI)
+        if self.native:
+            from .ops.fab import fused_fab
+            x_adv, dist, _, _ = fused_fab(self.net, self._rows_native(x, B), labels, *args)
+        else:
+            x_adv, dist, _, _ = reference_fab(self.net, _rows_f32(x, B, self.device), labels, *args)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        lp = self._forward(x_adv)[0]
+        return x_adv, dist * MNIST_STD, lp, lp.argmax(dim=1) != labels
 
     # ------------------------------------------------------------------ randomized smoothing
     def smoothed_counts(self, x: torch.Tensor, sigma: float, n: int, seed: int = 0, ids=None,
@@ -1005,6 +1101,9 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--ensemble-queries', type=int, default=5000, metavar='Q',
                     help='most queries per image of the Square Attack stage; 0: skip it (default: 5000)')
     ap.add_argument('--ensemble-seed', type=int, default=0, help='seed of the squares (default: 0)')
+    ap.add_argument('--ensemble-fab-steps', type=int, default=0, metavar='N',
+                    help='iterations of an untargeted L-inf FAB stage after the targeted one; 0: no such stage '
+                         '(default: 0)')
     ap.add_argument('--square-eps', type=float, default=None, metavar='E',
                     help='also report loss and accuracy under the L-inf Square Attack (score-based, black-box: no '
                          'gradient is read) of radius E, in pixel units on the [0, 1] scale (default: off)')
@@ -1038,6 +1137,16 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack the first M images of the split (default: all)')
     ap.add_argument('--min-norm-radii', type=_radii, default=(), metavar='R1,R2,...',
                     help='L2 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
+    ap.add_argument('--fab', action='store_true', default=False,
+                    help='also report the minimum-norm adversarial radius of the images against their true labels by '
+                         'the FAB attack (untargeted, inside the pixel box): how many are found, the median and mean '
+                         'radius in pixel units (default: off)')
+    ap.add_argument('--fab-norm', choices=('linf', 'l2'), default='linf', help='norm of the FAB radii (default: linf)')
+    ap.add_argument('--fab-steps', type=int, default=100, metavar='N', help='FAB iterations per image (default: 100)')
+    ap.add_argument('--fab-count', type=int, default=None, metavar='M',
+                    help='attack the first M images of the split (default: all)')
+    ap.add_argument('--fab-radii', type=_radii, default=(), metavar='R1,R2,...',
+                    help='radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
     return ap
 
 
@@ -1074,9 +1183,9 @@ def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: i
             f"{_loss_tag(loss_name)}): {figures}")
 
 
-def ensemble_line(eps: float, targets: int, correct: int, n: int) -> str:
-    """The ``Ensemble set`` line of ``mnist_predict.py --ensemble-eps``."""
-    return (f"Ensemble set (Linf eps={eps:g}: apgd-ce, apgd-t x {targets}, square): "
+def ensemble_line(eps: float, targets: int, correct: int, n: int, fab: bool = False) -> str:
+    """The ``Ensemble set`` line of ``mnist_predict.py --ensemble-eps``; ``fab``: the ensemble had a FAB stage."""
+    return (f"Ensemble set (Linf eps={eps:g}: apgd-ce, apgd-t x {targets}, {'fab, ' if fab else ''}square): "
             f"Accuracy: {correct}/{n} ({100.0 * correct / n:.0f}%)")
 
 
@@ -1103,6 +1212,13 @@ def minimum_norm_line(steps: int, overshoot: float, m: int, found: int, median, 
     """The ``Minimum-norm set`` line of ``mnist_predict.py --min-norm``."""
     fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
     return (f"Minimum-norm set (L2 DeepFool, steps={steps}, overshoot={overshoot:g}): "
+            f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
+
+
+def fab_line(norm: str, steps: int, m: int, found: int, median, mean) -> str:
+    """The ``FAB set`` line of ``mnist_predict.py --fab``, in the number formats of ``minimum_norm_line``."""
+    fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
+    return (f"FAB set ({'L2' if norm == 'l2' else 'Linf'}, steps={steps}): "
             f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
@@ -1200,6 +1316,24 @@ def predict_main(argv=None) -> int:
                       min_norm_count=m, min_norm_found=stats[0], min_norm_median_radius=stats[1],
                       min_norm_mean_radius=stats[2],
                       min_norm_accuracy_at={f"{r:g}": c for r, c in zip(args.min_norm_radii, stats[3])})
+    if args.fab:
+        m = n if args.fab_count is None else max(1, min(n, args.fab_count))
+        found = torch.empty(m, dtype=torch.bool)
+        clean = torch.empty(m, dtype=torch.bool)
+        radii = torch.empty(m, dtype=torch.float32)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            yb = data.targets[i:j]
+            clean[i:j] = (predictor.predict(images[i:j]).cpu() == yb.long().cpu())
+            _, r, _, fnd = predictor.fab(images[i:j], yb, args.fab_norm, args.fab_steps)
+            radii[i:j], found[i:j] = r.cpu(), fnd.cpu()
+        stats = minimum_norm_stats(radii, found, clean, args.fab_radii)
+        print(fab_line(args.fab_norm, args.fab_steps, m, *stats[:3]))
+        for r, c in zip(args.fab_radii, stats[3]):
+            print(f"Accuracy at radius {r:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
+        record.update(fab_norm=args.fab_norm, fab_steps=args.fab_steps, fab_count=m, fab_found=stats[0],
+                      fab_median_radius=stats[1], fab_mean_radius=stats[2],
+                      fab_accuracy_at={f"{r:g}": c for r, c in zip(args.fab_radii, stats[3])})
     if args.apgd_eps is not None:
         gen = torch.Generator().manual_seed(args.apgd_seed) if args.apgd_restarts > 1 else None
         ap_loss, ap_correct, _ = predictor.robust_evaluate_apgd(images, data.targets, args.apgd_eps, args.apgd_steps,
@@ -1224,11 +1358,13 @@ def predict_main(argv=None) -> int:
     if args.ensemble_eps is not None:
         en_correct, _, en_after = predictor.robust_evaluate_ensemble(
             images, data.targets, args.ensemble_eps, args.ensemble_steps, args.ensemble_targets, args.ensemble_queries,
-            args.batch_size, seed=args.ensemble_seed)
-        print(ensemble_line(args.ensemble_eps, args.ensemble_targets, en_correct, n))
+            args.batch_size, seed=args.ensemble_seed, fab_steps=args.ensemble_fab_steps)
+        print(ensemble_line(args.ensemble_eps, args.ensemble_targets, en_correct, n, args.ensemble_fab_steps > 0))
         record.update(ensemble_eps=args.ensemble_eps, ensemble_steps=args.ensemble_steps,
                       ensemble_targets=args.ensemble_targets, ensemble_queries=args.ensemble_queries,
                       ensemble_seed=args.ensemble_seed, ensemble_correct=en_correct, ensemble_after=en_after)
+        if args.ensemble_fab_steps > 0:
+            record.update(ensemble_fab_steps=args.ensemble_fab_steps)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

@@ -842,6 +842,183 @@ def deepfool_step(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0
                        float(overshoot), float(lo), float(hi), M, _s())
 
 
+FAB_LINF, FAB_L2 = 0, 1             # the norm of a fab_step launch (kernels.h FabNorm)
+FAB_NORMS = {"linf": FAB_LINF, "l2": FAB_L2}
+FAB_RUNNING, FAB_DONE, FAB_STUCK = 0, 1, 2   # the per-image status (kernels.h FabStatus)
+
+
+def _f32_scalar(v: float, dt, dev) -> torch.Tensor:
+    import numpy as np
+    return torch.tensor(float(np.float32(v)), dtype=dt, device=dev)
+
+
+def fab_projection_reference(w: torch.Tensor, v: torch.Tensor, r: torch.Tensor, lo: float, hi: float,
+                             norm: str) -> torch.Tensor:
+    """The box-constrained projection P(v, r) of ``fab_step`` in torch ops, in the dtype of ``w``: per row of ``w``
+    / ``v`` ([M, 784]) and entry of ``r`` ([M]) the delta of smallest ``norm`` ("linf" / "l2") with r + w . delta = 0
+    and lo <= v + delta <= hi.  Per element a = |w|, d = -sgn(r) sgn(w), room = (hi - v if d > 0 else v - lo) floored
+    at 0, c = 1 (linf) or a (l2); delta = d min(tau c, room), tau the smallest root of sum a min(tau c, room) = |r|:
+    on the stably sorted breakpoints room / c, the first position k with R_k + tau_k S_k >= |r| (R_k: the sum of
+    a room before k, S_k: the sum of a c from k on) gives tau = (|r| - R_k) / S_k; none (the hyperplane misses the
+    box): tau = inf.  Elements with a = 0 take no part.  ``lo`` and ``hi`` are rounded to float32 first."""
+    if norm not in FAB_NORMS:
+        raise ValueError(f"fab_projection_reference: norm must be 'linf' or 'l2', got {norm!r}")
+    dt, dev = w.dtype, w.device
+    w = w.reshape(-1, w.shape[-1])
+    v, r = v.reshape(w.shape).to(dt), r.reshape(-1).to(dt)
+    lo, hi = _f32_scalar(lo, dt, dev), _f32_scalar(hi, dt, dev)
+    a = w.abs()
+    d = -(torch.sign(r)[:, None] * torch.sign(w))
+    room = torch.where(d > 0, hi - v, v - lo).clamp_min(0)
+    act = a > 0
+    c = a if norm == "l2" else torch.ones_like(a)
+    zero, inf = torch.zeros((), dtype=dt, device=dev), torch.full((), float("inf"), dtype=dt, device=dev)
+    taus, order = torch.sort(torch.where(act, room / c, inf), dim=1, stable=True)
+    ars = torch.where(act, a * room, zero).gather(1, order)
+    acs = torch.where(act, a * c, zero).gather(1, order)
+    R = torch.cat([torch.zeros_like(ars[:, :1]), ars.cumsum(1)[:, :-1]], dim=1)
+    S = acs.flip(1).cumsum(1).flip(1)
+    ra = r.abs()
+    ok = (R + taus * S) >= ra[:, None]
+    first = ok.to(torch.int8).argmax(dim=1, keepdim=True)               # the first position that reaches |r|
+    tau = torch.where(ok.any(dim=1), (ra - R.gather(1, first)[:, 0]) / S.gather(1, first)[:, 0], inf)
+    return torch.where(act, d * torch.minimum(tau[:, None] * c, room), zero)
+
+
+def _fab_norm(t: torch.Tensor, norm: str) -> torch.Tensor:
+    return t.abs().amax(dim=-1) if norm == "linf" else t.square().sum(dim=-1).sqrt()
+
+
+def fab_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x: torch.Tensor,
+                       x_best: torch.Tensor, norm_best: torch.Tensor, status: torch.Tensor, iters: torch.Tensor,
+                       alpha_max: float, eta: float, beta: float, lo: float, hi: float, norm: str,
+                       last: bool = False):
+    """``fab_step`` in torch ops on any device, in the dtype of ``dx`` (float32: the CPU / fp32 path of
+    ``Predictor.fab``).  Same operands - ``dx`` [10 M, 784], ``loss_rows`` [10 M], ``y`` [M] integers, ``x0`` / ``x`` /
+    ``x_best`` [M, 784], ``norm_best`` [M], ``status`` / ``iters`` [M] integers - none of them modified; returns the
+    new ``(x, x_best, norm_best, status, iters, proj)``, ``proj`` [M, 2, 784] the two projections of the images that
+    made a forward step (zeros elsewhere).  Per image, with f_k = loss_y - loss_k, w_k = g_y - g_k, |.| the norm and q
+    its dual exponent:
+
+        frozen (status != 0): everything kept
+        crossed (some loss_k < loss_y, or == with k < y): u = |x - x0|; u < norm_best: x_best = x, norm_best = u;
+            u == 0: status = 1 (done); else, unless ``last``: x = clamp(x0 + beta (x - x0)), iters += 1
+        not crossed and ``last``: everything kept
+        l = the first smallest (|f_k| + DF_SLACK) / |w_k|_q in ascending k, skipping |w_k|_q < PGD_L2_TINY and NaN
+            ratios; none left: a NaN ratio fills x and proj with NaN (iters += 1), else status = 2 (stuck)
+        r1 = f_l, r2 = f_l + sum w_l (x0 - x); d1 = P(x, r1), d2 = P(x0, r2) (``fab_projection_reference``);
+        alpha = min(|d1| / (|d1| + |d2|), alpha_max), 0 / 0 = 0;
+        x = clamp((1 - alpha) (x + eta d1) + alpha (x0 + eta d2), lo, hi); iters += 1
+
+    The scalars are rounded to float32 first, as the kernel receives them."""
+    if norm not in FAB_NORMS:
+        raise ValueError(f"fab_step_reference: norm must be 'linf' or 'l2', got {norm!r}")
+    dt, dev = dx.dtype, dx.device
+    M = y.numel()
+    g = dx.reshape(M, DF_CLASSES, 784)
+    loss = loss_rows.reshape(M, DF_CLASSES).to(dt)
+    x0, x, x_best = x0.reshape(M, 784).to(dt), x.reshape(M, 784).to(dt), x_best.reshape(M, 784).to(dt)
+    norm_best = norm_best.reshape(M).to(dt)
+    ar = torch.arange(M, device=dev)
+    yl = y.reshape(M).long()
+    inside = (yl >= 0) & (yl < DF_CLASSES)
+    yc = yl.clamp(0, DF_CLASSES - 1)
+    k = torch.arange(DF_CLASSES, device=dev)[None, :]
+    other = k != yc[:, None]
+    ly = loss[ar, yc][:, None]
+    crossed = (other & ((loss < ly) | ((loss == ly) & (k < yc[:, None])))).any(dim=1)
+    f = ly - loss
+    w = g[ar, yc][:, None, :] - g                                        # [M, 10, 784]
+    n = w.abs().sum(dim=2) if norm == "linf" else w.square().sum(dim=2).sqrt()
+    ratio = (f.abs() + _f32_scalar(DF_SLACK, dt, dev)) / n
+    nan = ratio != ratio
+    ok = other & ~nan & ~(n < PGD_L2_TINY)
+    l = torch.full((M,), -1, dtype=torch.long, device=dev)
+    best = torch.zeros(M, dtype=dt, device=dev)
+    for c in range(DF_CLASSES):                                          # ascending k, strict <: the first minimum
+        take = ok[:, c] & ((l < 0) | (ratio[:, c] < best))
+        best = torch.where(take, ratio[:, c], best)
+        l = torch.where(take, torch.full_like(l, c), l)
+    active = status.reshape(M).long() == FAB_RUNNING
+    cross = active & inside & crossed
+    fwd = active & inside & ~crossed & (not last)
+    upd = fwd & (l >= 0)
+    fill = fwd & (l < 0) & (other & nan).any(dim=1)
+    stuck = (active & ~inside) | (fwd & ~upd & ~fill)
+    lo_t, hi_t = _f32_scalar(lo, dt, dev), _f32_scalar(hi, dt, dev)
+    # the backward step of a crossed iterate
+    u = _fab_norm(x - x0, norm)
+    better = cross & (u < norm_best)
+    done = cross & (u == 0)
+    back = cross & ~done & (not last)
+    x_back = torch.minimum(torch.maximum(x0 + _f32_scalar(beta, dt, dev) * (x - x0), lo_t), hi_t)
+    # the forward step along the two projections
+    lc = l.clamp_min(0)
+    wl, r1 = w[ar, lc], f[ar, lc]
+    r2 = r1 + (wl * (x0 - x)).sum(dim=1)
+    d1 = fab_projection_reference(wl, x, r1, lo, hi, norm)
+    d2 = fab_projection_reference(wl, x0, r2, lo, hi, norm)
+    n1, n2 = _fab_norm(d1, norm), _fab_norm(d2, norm)
+    al = torch.where(n1 + n2 > 0, n1 / (n1 + n2), torch.zeros_like(n1))
+    al = torch.minimum(al, _f32_scalar(alpha_max, dt, dev))[:, None]
+    e = _f32_scalar(eta, dt, dev)
+    x_fwd = ((1 - al) * (x + e * d1) + al * (x0 + e * d2)).clamp(float(lo_t), float(hi_t))
+    qn = torch.full((), float("nan"), dtype=dt, device=dev)
+    x_new = torch.where(back[:, None], x_back, torch.where(upd[:, None], x_fwd, torch.where(fill[:, None], qn, x)))
+    proj = torch.stack([d1, d2], dim=1)
+    proj = torch.where(upd[:, None, None], proj, torch.where(fill[:, None, None], qn, torch.zeros_like(proj)))
+    st = status.reshape(M).clone()
+    st[done] = FAB_DONE
+    st[stuck] = FAB_STUCK
+    return (x_new, torch.where(better[:, None], x, x_best), torch.where(better, u, norm_best), st,
+            iters.reshape(M) + (back | upd | fill).to(iters.dtype), proj)
+
+
+def fab_step(dx: torch.Tensor, loss_rows: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x: torch.Tensor,
+             x_best: torch.Tensor, norm_best: torch.Tensor, rows: torch.Tensor, status: torch.Tensor,
+             iters: torch.Tensor, alpha_max: float, eta: float, beta: float, lo: float, hi: float, norm: str,
+             last: bool = False, proj: torch.Tensor | None = None, M: int | None = None) -> None:
+    """One FAB iteration per image (``csrc/kernels/fab.hip``), one launch, in place: from the ten gradient rows
+    ``dx[10 i + c]`` (float32 [>= 10 M, 784], what ``input_grad`` wrote), the losses ``loss_rows[10 i + c]`` = -log p_c
+    (float32 [>= 10 M]), the class ``y[i]`` being left (int32 [>= M]) and the clean image ``x0[i]``, the update of
+    ``fab_step_reference`` on ``x``, ``x_best`` (float32 [>= M, 784]), ``norm_best`` (float32 [>= M], +inf at the
+    start), the image's ten ``rows`` (float32 [>= 10 M, 784]), ``status`` and ``iters`` (int32 [>= M]).  ``proj``
+    (float32 [>= M, 2, 784], optional) receives the two projections of every image that made a forward step.  ``norm``:
+    "linf" or "l2".  float32 throughout, every sum in a fixed order: the same operands give the same bits.  An image
+    with ``status`` != 0 is frozen: nothing of it is stored.  ``last``: the round after the last update - the best
+    point is brought up to date, no iterate moves.  ``M``: the images of the launch (default ``y.numel()``); nothing
+    past M is touched."""
+    if norm not in FAB_NORMS:
+        raise ValueError(f"fab_step: norm must be 'linf' or 'l2', got {norm!r}")
+    if dx.dim() != 2 or dx.device.type != "cuda":
+        raise ValueError("fab_step: dx must be a float32 [10 M, 784] tensor on the GPU")
+    dev = dx.device
+    M = int(y.numel() if M is None else M)
+    if M < 1 or M > DF_MAX_M:
+        raise ValueError(f"fab_step: M = {M} images must be in [1, DF_MAX_M = {DF_MAX_M}] a launch")
+    _f32_rows("fab_step", "dx", dx, DF_CLASSES * M, dev, at_least="10 M")
+    _f32_rows("fab_step", "rows", rows, DF_CLASSES * M, dev, at_least="10 M")
+    for what, t in (("x0", x0), ("x", x), ("x_best", x_best)):
+        _f32_rows("fab_step", what, t, M, dev, at_least="M")
+    _df_vec("fab_step", "loss_rows", loss_rows, torch.float32, DF_CLASSES * M, dev, "10 M")
+    _df_vec("fab_step", "y", y, torch.int32, M, dev, "M")
+    _df_vec("fab_step", "norm_best", norm_best, torch.float32, M, dev, "M")
+    _df_vec("fab_step", "status", status, torch.int32, M, dev, "M")
+    _df_vec("fab_step", "iters", iters, torch.int32, M, dev, "M")
+    bufs = [dx, x0, x, x_best, rows]
+    if proj is not None:
+        _df_vec("fab_step", "proj", proj, torch.float32, 2 * 784 * M, dev, "2 * 784 M")
+        bufs.append(proj)
+    if len({t.data_ptr() for t in bufs}) != len(bufs):
+        raise ValueError("fab_step: dx, x0, x, x_best, rows and proj must be buffers of their own")
+    if not (eta >= 1 and 0 < beta <= 1 and 0 <= alpha_max <= 1 and lo <= hi):
+        raise ValueError("fab_step: need eta >= 1, beta in (0, 1], alpha_max in [0, 1] and lo <= hi")
+    p = native.ptr
+    _C().fab_step(p(dx), p(loss_rows), p(y), p(x0), p(x), p(x_best), p(norm_best), p(rows), p(status), p(iters),
+                  p(proj), float(alpha_max), float(eta), float(beta), float(lo), float(hi), FAB_NORMS[norm],
+                  bool(last), M, _s())
+
+
 APGD_MOMENTUM = 0.75                # a of the momentum step after the first update (csrc/kernels/apgd.hip)
 APGD_RHO = (3, 4)                   # a window of k iterations oscillates when 4 n_up <= 3 k (rho = 0.75, in integers)
 APGD_MAX_M = 1 << 20                # most images one apgd_step launch takes (kernels.h INPUT_GRAD_MAX_B)
