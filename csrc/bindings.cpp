@@ -45,6 +45,7 @@ void mnist::preload_all_kernels() {
   preload_deepfool();
   preload_apgd();
   preload_square();
+  preload_square_l2();
   preload_fab();
 }
 
@@ -623,6 +624,38 @@ PYBIND11_MODULE(_C, m) {
      "one Square Attack query per image: accept the candidate when its margin is strictly lower, freeze a broken "
      "image, write the next candidate (a square of +-eps at a Philox-drawn place); state [M] records of 16 bytes = "
      "margin_best, queries_used, done, spare");
+
+  // ---------------- L2 Square Attack ----------------
+  m.attr("SQUARE_L2_PHILOX_DOMAIN") = SQUARE_L2_PHILOX_DOMAIN;
+  m.def("square_l2_init", [](uintptr_t x0, uintptr_t x_cand, uintptr_t table, float eps, float lo, float hi,
+                             uint64_t seed, int64_t id_base, int M, uintptr_t stream) {
+    if (id_base < 0 || id_base > 0xFFFFFFFFll) throw std::runtime_error("square_l2_init: id_base must fit 32 bits");
+    SquareL2InitArgs a{P<const float>(x0), P<float>(x_cand), P<const float>(table), eps, lo, hi, seed,
+                       (uint32_t)id_base};
+    launch_square_l2_init(a, M, S(stream));
+    check_launch();
+  }, py::arg("x0"), py::arg("x_cand"), py::arg("table"), py::arg("eps"), py::arg("lo"), py::arg("hi"),
+     py::arg("seed"), py::arg("id_base"), py::arg("M"), py::arg("stream"),
+     "x_cand = clamp(x0 + (eps / 5) * (+-E_5 on 25 tiles, 0 on the border), lo, hi), signs and transposes drawn from "
+     "Philox: the candidate of query 0 of an L2 Square Attack; table: fp32 [5][5]");
+  m.def("square_l2_step", [](uintptr_t logp, uintptr_t y, uintptr_t x0, uintptr_t x_best, uintptr_t x_cand,
+                             uintptr_t state, uintptr_t table, float eps, float lo, float hi, uint64_t seed, int64_t q,
+                             int64_t id_base, int side, bool first, bool last, bool targeted, int M,
+                             uintptr_t stream) {
+    if (q < 0 || q > 0xFFFFFFFFll || id_base < 0 || id_base > 0xFFFFFFFFll)
+      throw std::runtime_error("square_l2_step: q and id_base must fit 32 bits");
+    SquareL2StepArgs a{P<const float>(logp), P<const int32_t>(y), P<const float>(x0), P<float>(x_best),
+                       P<float>(x_cand), P<void>(state), P<const float>(table), eps, lo, hi, seed, (uint32_t)q,
+                       (uint32_t)id_base, side, first ? 1 : 0, last ? 1 : 0, targeted ? 1 : 0};
+    launch_square_l2_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("logp"), py::arg("y"), py::arg("x0"), py::arg("x_best"), py::arg("x_cand"), py::arg("state"),
+     py::arg("table"), py::arg("eps"), py::arg("lo"), py::arg("hi"), py::arg("seed"), py::arg("q"),
+     py::arg("id_base"), py::arg("side"), py::arg("first"), py::arg("last"), py::arg("targeted"), py::arg("M"),
+     py::arg("stream"),
+     "one L2 Square Attack query per image: accept the candidate when its margin is strictly lower, freeze a broken "
+     "image, write the next candidate (the mass of a window W2 moved into a window W1 under the pattern table, the "
+     "perturbation rescaled to radius eps); state as square_step; table: fp32 [side][side]");
 
   // ---------------- communicator ----------------
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")

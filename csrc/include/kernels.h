@@ -545,6 +545,46 @@ struct SquareStepArgs {
 // M in [1, INPUT_GRAD_MAX_B], eps >= 0, side in [1, 27], id_base + M <= 2^32
 void launch_square_step(const SquareStepArgs& a, int M, hipStream_t s);
 
+// ---------------- L2 Square Attack (square.hip; the L2 branch of the authors' code) ----------------
+// The same query loop and the same per-image record as the L-inf kernels above; the proposal moves perturbation mass
+// from a window W2 into a window W1 (both s x s, s odd), where the pattern +-E_s (or its transpose) is added, and
+// rescales the whole perturbation to the sphere of radius eps: three dependent reductions over the image.  E_s is the
+// authors' meta_pseudo_gaussian_pert(s), built on the host (ops.functional.square_l2_pattern): `table` is fp32
+// [side][side], row-major.  square_l2_init writes the candidate of query 0: 25 tiles of +-E_5 scaled by eps / 5.
+// Draws: Philox-4x32-10 keyed by seed with counter (q, SQUARE_L2_PHILOX_DOMAIN, id_base + i, k).  The exact
+// operation order and the NaN rules are in square.hip.
+constexpr uint32_t SQUARE_L2_PHILOX_DOMAIN = 0x53514C32u;   // Philox counter word 1 of square_l2_init / _step ("SQL2")
+static_assert(SQUARE_L2_PHILOX_DOMAIN != 0u && SQUARE_L2_PHILOX_DOMAIN != ADV_PHILOX_DOMAIN &&
+                  SQUARE_L2_PHILOX_DOMAIN != SMOOTH_PHILOX_DOMAIN && SQUARE_L2_PHILOX_DOMAIN != SQUARE_PHILOX_DOMAIN,
+              "a counter domain of its own");
+constexpr int SQUARE_L2_INIT_SIDE = 5, SQUARE_L2_MIN_SIDE = 3, SQUARE_L2_MAX_SIDE = 27;
+struct SquareL2InitArgs {
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* x_cand;              // fp32 [M][784] the candidate of query 0
+  const float* table;         // fp32 [5][5] the pattern E_5
+  float eps, lo, hi;          // L2 radius, valid range: normalised units
+  uint64_t seed;              // Philox key
+  uint32_t id_base;           // image i draws under the id id_base + i
+};
+void launch_square_l2_init(const SquareL2InitArgs& a, int M, hipStream_t s);   // M in [1, INPUT_GRAD_MAX_B], eps >= 0
+struct SquareL2StepArgs {
+  const float* logp;          // fp32 [M][10] log-probabilities of x_cand (head_eval)
+  const int32_t* y;           // [M] the label (targeted: the class to reach)
+  const float* x0;            // fp32 [M][784] the clean normalised image
+  float* x_best;              // fp32 [M][784] the point of the lowest margin so far
+  float* x_cand;              // fp32 [M][784] the candidate (the xin of the next eval forward)
+  void* state;                // [M] 16-byte records (SquareStepArgs' layout)
+  const float* table;         // fp32 [side][side] the pattern E_side
+  float eps, lo, hi;
+  uint64_t seed;
+  uint32_t q;                 // the query index of the proposal this launch writes (round j: j + 1)
+  uint32_t id_base;
+  int side;                   // of that proposal's windows: odd, in [3, 27]
+  int first, last, targeted;  // flags
+};
+// M in [1, INPUT_GRAD_MAX_B], eps >= 0, side odd in [3, 27], id_base + M <= 2^32
+void launch_square_l2_step(const SquareL2StepArgs& a, int M, hipStream_t s);
+
 // ---------------- optimizer ----------------
 struct AdadeltaArgs {
   float* param;               // flat fp32
@@ -621,6 +661,7 @@ void preload_attr();
 void preload_deepfool();
 void preload_apgd();
 void preload_square();
+void preload_square_l2();
 void preload_fab();
 void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 

@@ -64,8 +64,9 @@ from .models.net import Net
 from .ops.chain import chain_loss
 from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES,
                              apgd_checkpoints, apgd_step_reference, attr_path_reference, attr_reduce_reference,
-                             deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_sides,
-                             square_state_margin, square_step_reference)
+                             deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_l2_init_reference,
+                             square_l2_step_reference, square_norm, square_sides, square_sides_l2, square_state_margin,
+                             square_step_reference)
 from .utils.checkpoint import load_state_dict
 from .utils.logging import test_line
 
@@ -162,35 +163,39 @@ def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: fl
 
 def reference_square_attack(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, queries: int, lo: float,
                             hi: float, p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False,
-                            check_every: int = 64):
+                            check_every: int = 64, norm: str = "linf"):
     """``ops.square.fused_square_attack`` in torch float32 on any device: the same ``queries`` rounds - the
     log-probabilities of the candidates from ``Net.forward_reference`` in eval mode under ``no_grad`` (the net's mode
     is restored afterwards), then ``square_step_reference`` with the same ``first`` / ``last`` flags, query indices
     and ``square_sides`` - with the same Philox draws (``ops.philox``).  Same arguments (float32 [B, 784] normalised
     images, normalised units), same return: ``(x_best [B, 784], margin_best [B], queries_used int32 [B])``.
     ``check_every`` = k > 0 stops once every image is broken, looked at every k queries; the result does not depend
-    on it.  The CPU / fp32 path of ``Predictor.square_attack`` and the reference of its GPU tests."""
+    on it.  ``norm="l2"``: ``square_l2_init_reference`` / ``square_l2_step_reference`` with ``square_sides_l2``, ``eps``
+    the L2 radius.  The CPU / fp32 path of ``Predictor.square_attack`` and the reference of its GPU tests."""
+    l2 = square_norm("reference_square_attack", norm)
+    init, step = (square_l2_init_reference, square_l2_step_reference) if l2 else \
+        (square_init_reference, square_step_reference)
     queries, check_every = int(queries), int(check_every)
     if queries < 1 or queries >= 1 << 32:
         raise ValueError("reference_square_attack: queries must be in [1, 2**32)")
     if check_every < 0:
         raise ValueError(f"reference_square_attack: check_every must be >= 0, got {check_every}")
-    sides = square_sides(p_init, queries)
+    sides = square_sides_l2(p_init, queries) if l2 else square_sides(p_init, queries)
+    idle = 3 if l2 else 1                       # the side of the last round, which proposes nothing
     B = x0.shape[0]
     x0 = x0.detach().reshape(B, 784).to(torch.float32)
     y = labels.reshape(B).to(x0.device, torch.int32)
     ids = list(range(B)) if ids is None else [int(v) for v in ids]
     if len(ids) != B:
         raise ValueError(f"reference_square_attack: {len(ids)} ids for {B} images")
-    x_cand = square_init_reference(x0, eps, lo, hi, seed, ids)
+    x_cand = init(x0, eps, lo, hi, seed, ids)
     x_best = state = None
     with _eval_mode(net), torch.no_grad():
         for j in range(queries):
             last = j == queries - 1
             lp = net.forward_reference(x_cand.view(B, 1, 28, 28))
-            x_best, x_cand, state = square_step_reference(lp, y, x0, x_best, x_cand, state, eps, lo, hi, seed, j + 1,
-                                                          1 if last else sides[j], ids, first=j == 0, last=last,
-                                                          targeted=targeted)
+            x_best, x_cand, state = step(lp, y, x0, x_best, x_cand, state, eps, lo, hi, seed, j + 1,
+                                         idle if last else sides[j], ids, first=j == 0, last=last, targeted=targeted)
             if check_every and (j + 1) % check_every == 0 and bool((state[:, SQUARE_DONE] != 0).all()):
                 break
     return x_best, square_state_margin(state), state[:, SQUARE_QUERIES].clone()
@@ -618,7 +623,8 @@ class Predictor:
         return float(total.item()), int(hits.item()), n
 
     def square_attack(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.3, queries: int = 1000,
-                      p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64):
+                      p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64,
+                      norm: str = "linf"):
         """(x_adv, log_probs, margin, queries_used): the L-inf Square Attack (Andriushchenko, Croce, Flammarion, Hein
         2020, the score-based black-box attack of AutoAttack) on ``x`` - a random search that reads only the
         log-probabilities of its candidates, never a gradient: the cross-check of ``adversarial`` / ``auto_pgd`` on
@@ -640,7 +646,16 @@ class Predictor:
         paper's resampling of a square that changes nothing is not made.  Inference semantics: no dropout; the
         net's mode, parameters and gradients are untouched.  GPU with ``dtype="bf16"``: the native loop
         ``ops.square.fused_square_attack``; CPU, or ``dtype="fp32"``: ``reference_square_attack``.  ``x``: uint8
-        [B,28,28] / [B,784] images or float [B,1,28,28] already-normalised input."""
+        [B,28,28] / [B,784] images or float [B,1,28,28] already-normalised input.
+
+        ``norm="l2"``: the L2 Square Attack of the same paper - ``eps`` is the radius of the L2 ball in pixel units
+        (1.5 to 2.0 are usual for MNIST) and ``x_adv`` lies inside it and inside the pixel range.  Query 0 is a start
+        of 25 tiles of the pattern E_5, every later one moves the perturbation's mass from one window into another
+        under +-E_s and rescales the whole to the sphere; the (odd) window side follows
+        ``functional.square_sides_l2``.  Differences from the authors' code: window positions cover 0 .. 28 - s
+        inclusive, one sign and one transpose are drawn per image (not per batch), their unused second window norm
+        is not computed.  Any other ``norm`` is a ValueError."""
+        l2 = square_norm("square_attack", norm)
         B = self._check_input(x)
         if targeted and labels is None:
             raise ValueError("square_attack: a targeted attack needs labels (the target classes)")
@@ -663,18 +678,20 @@ class Predictor:
             from .ops.square import fused_square_attack as attack
         else:
             attack = reference_square_attack
+        more = ("l2",) if l2 else ()             # (the default issues exactly the call it always did)
         x_adv, margin, used = attack(self.net, x0, labels, eps_n, int(queries), lo, hi, float(p_init), int(seed), ids,
-                                     targeted, int(check_every))
+                                     targeted, int(check_every), *more)
         x_adv = x_adv.view(B, 1, 28, 28)
         return x_adv, self._forward(x_adv)[0], margin, used
 
     def robust_evaluate_square(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, queries: int = 1000,
-                               batch_size: int = 1000, p_init: float = 0.8, seed: int = 0):
+                               batch_size: int = 1000, p_init: float = 0.8, seed: int = 0, norm: str = "linf"):
         """(loss_sum, correct, n, median_queries): the first three as ``robust_evaluate``, with the untargeted
         ``square_attack`` against the true labels as the attack, ``batch_size`` images at a time; an image's id is its
         row index, so its squares do not depend on ``batch_size``.  ``median_queries``: the median of
         ``queries_used`` over the images that are correct on the clean input and broken after the attack (None when
-        there is none; the median of an even count is the mean of the middle two)."""
+        there is none; the median of an even count is the mean of the middle two).  ``norm``: ``square_attack``'s."""
+        square_norm("robust_evaluate_square", norm)
         n = int(labels.shape[0])
         if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
             raise ValueError("robust_evaluate_square: images_u8 must be uint8 with one row per label")
@@ -688,7 +705,7 @@ class Predictor:
             y = lab[i:i + batch_size]
             clean = self._forward(images_u8[i:i + batch_size])[1] == y
             _, lp, _, used = self.square_attack(images_u8[i:i + batch_size], y, eps, queries, p_init, seed,
-                                                ids=range(i, i + y.shape[0]))
+                                                ids=range(i, i + y.shape[0]), norm=norm)
             right = lp.argmax(dim=1) == y
             loss += F.nll_loss(lp, y, reduction='none').double().sum()
             hits += right.sum()
@@ -699,7 +716,7 @@ class Predictor:
 
     def robust_evaluate_ensemble(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
                                  n_targets: int = 9, queries: int = 5000, batch_size: int = 1000,
-                                 p_init: float = 0.8, seed: int = 0, fab_steps: int = 0):
+                                 p_init: float = 0.8, seed: int = 0, fab_steps: int = 0, norm: str = "linf"):
         """(correct, n, after): the worst case over an ensemble of L-inf attacks of radius ``eps`` - how many of the
         ``n`` images are still classified correctly after all of them.  Per batch of ``batch_size`` images, each
         stage runs only on the images that are still correct (a batch with none left skips the stage):
@@ -716,7 +733,10 @@ class Predictor:
         skips the stage.  ``fab_steps`` > 0 adds a stage ``fab`` after ``apgd_t``: untargeted L-inf ``fab`` with that
         many iterations; an image is broken there when a point outside its label was found at a radius <= ``eps``,
         and ``after`` gains the key ``fab``.  This is not AutoAttack's standard set: FAB is untargeted here (with ten
-        classes every boundary is looked at anyway), and APGD starts from the clean point, not from random starts."""
+        classes every boundary is looked at anyway), and APGD starts from the clean point, not from random starts.
+        ``norm="l2"``: every stage in its L2 form - ``auto_pgd(norm="l2")``, ``fab(norm="l2")``,
+        ``square_attack(norm="l2")`` - with ``eps`` the L2 radius; any other ``norm`` is a ValueError."""
+        square_norm("robust_evaluate_ensemble", norm)
         n = int(labels.shape[0])
         if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
             raise ValueError("robust_evaluate_ensemble: images_u8 must be uint8 with one row per label")
@@ -751,21 +771,21 @@ class Predictor:
                     lp = attack(at)
                     alive[at] = lp.argmax(dim=1) == y[at]
 
-            stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], y[at], eps, steps, loss="ce")[1])
+            stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], y[at], eps, steps, norm, loss="ce")[1])
             after["apgd_ce"] += int(alive.sum())
             for k in range(int(n_targets)):
-                stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], order[at, k], eps, steps, targeted=True, loss="dlr",
-                                               true_labels=y[at])[1])
+                stage(lambda at: self.auto_pgd(xb[at.to(xb.device)], order[at, k], eps, steps, norm, targeted=True,
+                                               loss="dlr", true_labels=y[at])[1])
             after["apgd_t"] += int(alive.sum())
             if fab_steps > 0:
                 at = alive.nonzero()[:, 0]
                 if at.numel():
-                    _, radii, _, found = self.fab(xb[at.to(xb.device)], y[at], "linf", int(fab_steps))
+                    _, radii, _, found = self.fab(xb[at.to(xb.device)], y[at], norm, int(fab_steps))
                     alive[at] = ~(found & (radii <= eps))
                 after["fab"] += int(alive.sum())
             if queries > 0:
                 stage(lambda at: self.square_attack(xb[at.to(xb.device)], y[at], eps, queries, p_init, seed,
-                                                    ids=rows[at])[1])
+                                                    ids=rows[at], norm=norm)[1])
             after["square"] += int(alive.sum())
         return after["square"], n, after
 
@@ -1101,12 +1121,17 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--ensemble-queries', type=int, default=5000, metavar='Q',
                     help='most queries per image of the Square Attack stage; 0: skip it (default: 5000)')
     ap.add_argument('--ensemble-seed', type=int, default=0, help='seed of the squares (default: 0)')
+    ap.add_argument('--ensemble-norm', choices=('linf', 'l2'), default='linf',
+                    help='norm of the ensemble: every stage runs in that form, E is its radius (default: linf)')
     ap.add_argument('--ensemble-fab-steps', type=int, default=0, metavar='N',
                     help='iterations of an untargeted L-inf FAB stage after the targeted one; 0: no such stage '
                          '(default: 0)')
     ap.add_argument('--square-eps', type=float, default=None, metavar='E',
                     help='also report loss and accuracy under the L-inf Square Attack (score-based, black-box: no '
                          'gradient is read) of radius E, in pixel units on the [0, 1] scale (default: off)')
+    ap.add_argument('--square-norm', choices=('linf', 'l2'), default='linf',
+                    help='norm of the Square Attack; l2: E is the radius of the L2 ball, 1.5 to 2.0 are usual (default: '
+                         'linf)')
     ap.add_argument('--square-queries', type=int, default=1000, metavar='N',
                     help='most queries (forwards) per image of the Square Attack (default: 1000)')
     ap.add_argument('--square-p-init', type=float, default=0.8, metavar='P',
@@ -1183,17 +1208,21 @@ def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: i
             f"{_loss_tag(loss_name)}): {figures}")
 
 
-def ensemble_line(eps: float, targets: int, correct: int, n: int, fab: bool = False) -> str:
+def ensemble_line(eps: float, targets: int, correct: int, n: int, fab: bool = False, norm: str = "linf") -> str:
     """The ``Ensemble set`` line of ``mnist_predict.py --ensemble-eps``; ``fab``: the ensemble had a FAB stage."""
-    return (f"Ensemble set (Linf eps={eps:g}: apgd-ce, apgd-t x {targets}, {'fab, ' if fab else ''}square): "
+    return (f"Ensemble set ({_NORM_TAG[norm]} eps={eps:g}: apgd-ce, apgd-t x {targets}, {'fab, ' if fab else ''}square): "
             f"Accuracy: {correct}/{n} ({100.0 * correct / n:.0f}%)")
 
 
-def square_line(eps: float, queries: int, p_init: float, loss: float, correct: int, n: int, median) -> str:
+_NORM_TAG = {"linf": "Linf", "l2": "L2"}
+
+
+def square_line(eps: float, queries: int, p_init: float, loss: float, correct: int, n: int, median,
+                norm: str = "linf") -> str:
     """The ``Square set`` line of ``mnist_predict.py --square-eps``, in the number formats of ``adversarial_line``;
     ``median``: the median queries of the broken images, None when none broke."""
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
-    return (f"Square set (Linf eps={eps:g}, queries={queries}, p_init={p_init:g}): {figures}, "
+    return (f"Square set ({_NORM_TAG[norm]} eps={eps:g}, queries={queries}, p_init={p_init:g}): {figures}, "
             f"median queries: {'n/a' if median is None else format(median, 'g')}")
 
 
@@ -1349,22 +1378,27 @@ def predict_main(argv=None) -> int:
     if args.square_eps is not None:
         sq_loss, sq_correct, _, sq_median = predictor.robust_evaluate_square(
             images, data.targets, args.square_eps, args.square_queries, args.batch_size, args.square_p_init,
-            args.square_seed)
+            args.square_seed, norm=args.square_norm)
         print(square_line(args.square_eps, args.square_queries, args.square_p_init, sq_loss / n, sq_correct, n,
-                          sq_median))
+                          sq_median, args.square_norm))
         record.update(square_eps=args.square_eps, square_queries=args.square_queries,
                       square_p_init=args.square_p_init, square_seed=args.square_seed, square_loss=sq_loss / n,
                       square_correct=sq_correct, square_median_queries=sq_median)
+        if args.square_norm != "linf":
+            record.update(square_norm=args.square_norm)
     if args.ensemble_eps is not None:
         en_correct, _, en_after = predictor.robust_evaluate_ensemble(
             images, data.targets, args.ensemble_eps, args.ensemble_steps, args.ensemble_targets, args.ensemble_queries,
-            args.batch_size, seed=args.ensemble_seed, fab_steps=args.ensemble_fab_steps)
-        print(ensemble_line(args.ensemble_eps, args.ensemble_targets, en_correct, n, args.ensemble_fab_steps > 0))
+            args.batch_size, seed=args.ensemble_seed, fab_steps=args.ensemble_fab_steps, norm=args.ensemble_norm)
+        print(ensemble_line(args.ensemble_eps, args.ensemble_targets, en_correct, n, args.ensemble_fab_steps > 0,
+                            args.ensemble_norm))
         record.update(ensemble_eps=args.ensemble_eps, ensemble_steps=args.ensemble_steps,
                       ensemble_targets=args.ensemble_targets, ensemble_queries=args.ensemble_queries,
                       ensemble_seed=args.ensemble_seed, ensemble_correct=en_correct, ensemble_after=en_after)
         if args.ensemble_fab_steps > 0:
             record.update(ensemble_fab_steps=args.ensemble_fab_steps)
+        if args.ensemble_norm != "linf":
+            record.update(ensemble_norm=args.ensemble_norm)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

@@ -1191,18 +1191,24 @@ def square_sides(p_init: float, queries: int) -> tuple:
     their 10000 queries: it = int(q / queries * 10000); p = p_init / 1, 2, 4, ... 512 as ``it`` passes 10, 50, 200,
     500, 1000, 2000, 4000, 6000, 8000; side = min(max(floor(sqrt(p * 784) + 0.5), 1), 27) in float64."""
     import math
+    return tuple(min(max(int(math.floor(math.sqrt(p * 784.0) + 0.5)), 1), SQUARE_MAX_SIDE)
+                 for p in _square_p_schedule("square_sides", p_init, queries))
+
+
+def _square_p_schedule(name: str, p_init: float, queries: int) -> list:
+    """The share p of the image the proposal of each query index q = 1 .. queries - 1 covers (float64): the schedule
+    ``square_sides`` describes, shared with ``square_sides_l2``."""
     queries = int(queries)
     if queries < 1:
-        raise ValueError("square_sides: queries must be at least 1")
+        raise ValueError(f"{name}: queries must be at least 1")
     if not 0.0 < p_init <= 1.0:
-        raise ValueError(f"square_sides: p_init must be in (0, 1], got {p_init}")
+        raise ValueError(f"{name}: p_init must be in (0, 1], got {p_init}")
     out = []
     for q in range(1, queries):
         it = int(q / queries * 10000)
         div = next((d for top, d in _SQUARE_SCHEDULE if it <= top), 512)
-        side = int(math.floor(math.sqrt(float(p_init) / div * 784.0) + 0.5))
-        out.append(min(max(side, 1), SQUARE_MAX_SIDE))
-    return tuple(out)
+        out.append(float(p_init) / div)
+    return out
 
 
 def square_state_margin(state: torch.Tensor) -> torch.Tensor:
@@ -1259,6 +1265,31 @@ def square_margin_reference(logp: torch.Tensor, y: torch.Tensor, targeted: bool 
     return (mo - ly) if targeted else (ly - mo)
 
 
+def _square_decide(logp, y, x_best, x_cand, state, first: bool, targeted: bool):
+    """The record half of ``square_step_reference`` (and of its L2 form), before the proposal: ``(active, broken, xb,
+    margin, used, done, spare)`` - the images that are not frozen, those whose best margin is now below zero, the new
+    ``x_best``, and the new record's columns (``margin`` to be kept only where ``active``)."""
+    M, dev = x_cand.shape[0], x_cand.device
+    L = square_margin_reference(logp, y, targeted).to(dev)
+    if first:
+        active = accept = torch.ones(M, dtype=torch.bool, device=dev)
+        margin = L
+        used = torch.ones(M, dtype=torch.int32, device=dev)
+        done_was = spare = torch.zeros(M, dtype=torch.int32, device=dev)
+        xb = x_cand
+    else:
+        was = square_state_margin(state)
+        done_was, spare = state[:, SQUARE_DONE], state[:, 3]
+        active = done_was == 0
+        accept = active & (L < was)
+        margin = torch.where(accept, L, was)
+        used = state[:, SQUARE_QUERIES] + active.to(torch.int32)
+        xb = torch.where(accept[:, None], x_cand, x_best.detach().reshape(M, 784).to(torch.float32))
+    broken = margin < 0
+    done = torch.where(active, broken.to(torch.int32), done_was)
+    return active, broken, xb, margin, used, done, spare
+
+
 def square_step_reference(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: torch.Tensor | None,
                           x_cand: torch.Tensor, state: torch.Tensor | None, eps: float, lo: float, hi: float,
                           seed: int = 0, q: int = 1, side: int = 1, ids=None, id_base: int = 0, first: bool = False,
@@ -1292,24 +1323,9 @@ def square_step_reference(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor,
     x0 = x0.detach().reshape(M, 784).to(torch.float32)
     x_cand = x_cand.detach().reshape(M, 784).to(torch.float32)
     ids = _square_ids("square_step_reference", ids, id_base, M)
-    L = square_margin_reference(logp, y, targeted).to(dev)
-    if first:
-        active = accept = torch.ones(M, dtype=torch.bool, device=dev)
-        margin = L
-        used = torch.ones(M, dtype=torch.int32, device=dev)
-        done_was = spare = torch.zeros(M, dtype=torch.int32, device=dev)
-        xb = x_cand
-    else:
+    if not first:
         state = state.reshape(M, 4).to(torch.int32)
-        was = square_state_margin(state)
-        done_was, spare = state[:, SQUARE_DONE], state[:, 3]
-        active = done_was == 0
-        accept = active & (L < was)
-        margin = torch.where(accept, L, was)
-        used = state[:, SQUARE_QUERIES] + active.to(torch.int32)
-        xb = torch.where(accept[:, None], x_cand, x_best.detach().reshape(M, 784).to(torch.float32))
-    broken = margin < 0
-    done = torch.where(active, broken.to(torch.int32), done_was)
+    active, broken, xb, margin, used, done, spare = _square_decide(logp, y, x_best, x_cand, state, first, targeted)
     xc = x_cand
     if not last:
         w = philox4x32(q, SQUARE_PHILOX_DOMAIN, ids, 0, seed).astype(np.uint64)                 # [M, 4]
@@ -1389,6 +1405,244 @@ def square_step(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: t
     _C().square_step(p(logp), p(y), p(x0), p(x_best), p(x_cand), p(state), float(eps), float(lo), float(hi),
                      int(seed) & (2 ** 64 - 1), int(q), int(id_base), int(side), bool(first), bool(last),
                      bool(targeted), M, _s())
+
+
+SQUARE_L2_PHILOX_DOMAIN = 0x53514C32   # Philox counter word 1 of square_l2_init / square_l2_step (kernels.h)
+SQUARE_L2_SIDES = tuple(range(3, SQUARE_MAX_SIDE + 1, 2))   # the odd window sides of the L2 attack
+SQUARE_L2_INIT_SIDE = 5                 # the tiles of the start: 5 x 5 of them on rows and columns 1 .. 25
+SQUARE_NORMS = ("linf", "l2")
+_SQUARE_L2_TABLES: dict = {}
+
+
+def square_norm(name: str, norm: str) -> bool:
+    """True for "l2", False for "linf"; any other ``norm`` is a ValueError under ``name``."""
+    if norm not in SQUARE_NORMS:
+        raise ValueError(f"{name}: norm must be one of {SQUARE_NORMS}, got {norm!r}")
+    return norm == "l2"
+
+
+def square_l2_pattern(s: int) -> torch.Tensor:
+    """float32 [s, s]: the pattern E_s an L2 Square Attack proposal adds to its window (the authors'
+    ``meta_pseudo_gaussian_pert(s)``), s odd >= 3, built in float64 and rounded once.  rect(h, w): zeros [h, w] with
+    1 / (k + 1)^2 added to the centred block of (2k + 1)^2 pixels clipped to the array, k = 0 .. max(h // 2, w // 2),
+    divided by its L2 norm; E_s[: s // 2] = rect(s // 2, s), E_s[s // 2 :] = -rect(s - s // 2, s), divided by its L2
+    norm: unit norm, the upper half positive, the lower half negative."""
+    import numpy as np
+    s = int(s)
+    if s < 3 or s % 2 == 0:
+        raise ValueError(f"square_l2_pattern: the side must be odd and at least 3, got {s}")
+
+    def rect(h, w):
+        out = np.zeros((h, w), dtype=np.float64)
+        r0, c0 = h // 2, w // 2
+        for k in range(max(h // 2, w // 2) + 1):
+            out[max(r0, 0):min(r0 + 2 * k + 1, h), max(c0, 0):min(c0 + 2 * k + 1, w)] += 1.0 / (k + 1) ** 2
+            r0, c0 = r0 - 1, c0 - 1
+        return out / np.sqrt((out ** 2).sum())
+    e = np.concatenate((rect(s // 2, s), -rect(s - s // 2, s)), axis=0)
+    return torch.from_numpy((e / np.sqrt((e ** 2).sum())).astype(np.float32))
+
+
+def square_sides_l2(p_init: float, queries: int) -> tuple:
+    """``square_sides`` for the L2 attack: the same schedule of the share p, then in float64 s = max(floor(sqrt(p *
+    784) + 0.5), 3), + 1 when even, min(s, 27): odd sides in [3, 27]."""
+    import math
+    out = []
+    for p in _square_p_schedule("square_sides_l2", p_init, queries):
+        s = max(int(math.floor(math.sqrt(p * 784.0) + 0.5)), 3)
+        out.append(min(s + 1 if s % 2 == 0 else s, SQUARE_MAX_SIDE))
+    return tuple(out)
+
+
+def square_l2_table_offset(s: int) -> int:
+    """The first element of E_s in ``square_l2_tables``: the tables of the odd sides 3 .. 27 lie one after another."""
+    s = int(s)
+    if s not in SQUARE_L2_SIDES:
+        raise ValueError(f"square_l2: side must be odd and in [3, {SQUARE_MAX_SIDE}], got {s}")
+    return sum(t * t for t in SQUARE_L2_SIDES if t < s)
+
+
+def square_l2_tables(device) -> torch.Tensor:
+    """float32 [3654]: ``square_l2_pattern(s)`` of every odd s = 3 .. 27, row-major, E_s at
+    ``square_l2_table_offset(s)``, on ``device``; built once per device and kept."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    tab = _SQUARE_L2_TABLES.get(device)
+    if tab is None:
+        tab = torch.cat([square_l2_pattern(s).reshape(-1) for s in SQUARE_L2_SIDES]).to(device)
+        _SQUARE_L2_TABLES[device] = tab
+    return tab
+
+
+def _square_l2_table_ptr(name: str, tables: torch.Tensor | None, s: int, device) -> int:
+    """The address of E_s inside ``tables`` (default ``square_l2_tables(device)``)."""
+    off = square_l2_table_offset(s)
+    if tables is None:
+        tables = square_l2_tables(device)
+    elif tables.dtype != torch.float32 or not tables.is_contiguous() or tables.device != device or \
+            tables.numel() < square_l2_table_offset(SQUARE_MAX_SIDE) + SQUARE_MAX_SIDE ** 2:
+        raise ValueError(f"{name}: tables must be square_l2_tables() of the images' device")
+    return native.ptr(tables) + 4 * off
+
+
+def _square_l2_pattern_rows(rows: torch.Tensor, cols: torch.Tensor, s: int, plus: torch.Tensor, swap: torch.Tensor,
+                            dev) -> torch.Tensor:
+    """float32 [..., 28, 28]: +-E_s (``plus``), transposed where ``swap``, laid with its corner at (rows, cols) - all
+    four of one leading shape; the values outside the window are those of the nearest window pixel (masked by the
+    caller)."""
+    E = square_l2_pattern(s).to(dev)
+    at = torch.arange(28, device=dev)
+    rr = (at - rows[..., None]).clamp(0, s - 1)[..., :, None]
+    cc = (at - cols[..., None]).clamp(0, s - 1)[..., None, :]
+    pat = torch.where(swap[..., None, None], E[cc, rr], E[rr, cc])
+    return torch.where(plus[..., None, None], pat, -pat)
+
+
+def _square_window(row0: torch.Tensor, col0: torch.Tensor, s: int, dev) -> torch.Tensor:
+    """bool [M, 784]: the s x s window with its corner at (row0, col0) of each image."""
+    at = torch.arange(28, device=dev)
+    rows = (at[None, :] >= row0[:, None]) & (at[None, :] < row0[:, None] + s)
+    cols = (at[None, :] >= col0[:, None]) & (at[None, :] < col0[:, None] + s)
+    return (rows[:, :, None] & cols[:, None, :]).reshape(-1, 784)
+
+
+def square_l2_init_reference(x0: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, ids=None,
+                             id_base: int = 0) -> torch.Tensor:
+    """``square_l2_init`` in torch float32 on any device: the candidate of query 0 of the L2 attack.  The 25 tiles of
+    side 5 at rows 1 + 5 tr and columns 1 + 5 tc hold +E_5 where bit t = 5 tr + tc of word 0 of ``philox4x32(counter
+    = (0, SQUARE_L2_PHILOX_DOMAIN, id_i, 0), key = seed)`` is set, else -E_5, transposed where bit t of word 1 is;
+    the border holds 0; x_cand = clamp(x0 + e * (eps / 5)).  Every tile has unit norm, so the perturbation has norm
+    eps before the clamp.  The same bits as the kernel: there is no sum."""
+    import numpy as np
+    from .philox import philox4x32
+    M, dev = x0.shape[0], x0.device
+    x0 = x0.detach().reshape(M, 784).to(torch.float32)
+    ids = _square_ids("square_l2_init_reference", ids, id_base, M)
+    w = philox4x32(0, SQUARE_L2_PHILOX_DOMAIN, ids, 0, seed)                                     # [M, 4]
+    t = np.arange(25, dtype=np.uint32)
+    plus = torch.from_numpy(((w[:, 0:1] >> t) & 1).astype(np.bool_)).to(dev).view(M, 5, 5)
+    swap = torch.from_numpy(((w[:, 1:2] >> t) & 1).astype(np.bool_)).to(dev).view(M, 5, 5)
+    E = square_l2_pattern(SQUARE_L2_INIT_SIDE).to(dev)
+    tiles = torch.where(swap[..., None, None], E.t(), E)                                        # [M, 5, 5, 5, 5]
+    tiles = torch.where(plus[..., None, None], tiles, -tiles)
+    e = torch.zeros(M, 28, 28, dtype=torch.float32, device=dev)
+    e[:, 1:26, 1:26] = tiles.permute(0, 1, 3, 2, 4).reshape(M, 25, 25)
+    g = torch.tensor(float(np.float32(eps)), dtype=torch.float32, device=dev) / 5.0
+    return (x0 + e.reshape(M, 784) * g).clamp(float(np.float32(lo)), float(np.float32(hi)))
+
+
+def square_l2_step_reference(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: torch.Tensor | None,
+                             x_cand: torch.Tensor, state: torch.Tensor | None, eps: float, lo: float, hi: float,
+                             seed: int = 0, q: int = 1, side: int = 3, ids=None, id_base: int = 0,
+                             first: bool = False, last: bool = False, targeted: bool = False):
+    """``square_l2_step`` in torch float32 on any device (the CPU / fp32 path of ``Predictor.square_attack(norm=
+    "l2")``): ``square_step_reference``'s operands, record rules and return, with the L2 proposal for a live image
+    that is not done on a round that is not the last.  With d = x_best - x0 (x_best the point just accepted or kept),
+    wa / wb = philox4x32(counter = (q, SQUARE_L2_PHILOX_DOMAIN, id_i, 0 / 1), key = seed), W1 the ``side`` x ``side``
+    window at ((wa0 * (29 - side)) >> 32, (wa1 * (29 - side)) >> 32), W2 the one wb gives the same way, +E_side when
+    wa2 & 1 else -E_side, transposed when wa2 & 2:
+
+        S1, SU, SI = sum of d^2 over W1, over W1 u W2, over the image
+        n  = +-E[.] + d / (1e-10 + sqrt(S1)) on W1;  SN = sum_W1 n^2
+        d' = n * (sqrt(max(eps^2 - SI, 0) + SU) / sqrt(SN)) on W1, 0 on W2 \\ W1, d elsewhere;  SD = sum d'^2
+        x_cand = clamp(x0 + d' / sqrt(SD) * eps);  SN == 0 or SD == 0: x_cand = x_best
+
+    The kernel's formulas operation by operation; the sums are torch's, in torch's order: the same decisions and
+    record, ``x_cand`` up to the rounding of five sums."""
+    import numpy as np
+    from .philox import philox4x32
+    side, q = int(side), int(q)
+    square_l2_table_offset(side)
+    if not 0 <= q < 1 << 32:
+        raise ValueError("square_l2_step_reference: q must fit 32 bits")
+    M = x_cand.shape[0]
+    dev = x_cand.device
+    x0 = x0.detach().reshape(M, 784).to(torch.float32)
+    x_cand = x_cand.detach().reshape(M, 784).to(torch.float32)
+    ids = _square_ids("square_l2_step_reference", ids, id_base, M)
+    if not first:
+        state = state.reshape(M, 4).to(torch.int32)
+    active, broken, xb, margin, used, done, spare = _square_decide(logp, y, x_best, x_cand, state, first, targeted)
+    xc = x_cand
+    if not last:
+        wa = philox4x32(q, SQUARE_L2_PHILOX_DOMAIN, ids, 0, seed).astype(np.uint64)              # [M, 4]
+        wb = philox4x32(q, SQUARE_L2_PHILOX_DOMAIN, ids, 1, seed).astype(np.uint64)
+        span = np.uint64(29 - side)
+        row1, col1, row2, col2 = (torch.from_numpy(((w * span) >> np.uint64(32)).astype(np.int64)).to(dev)
+                                  for w in (wa[:, 0], wa[:, 1], wb[:, 0], wb[:, 1]))
+        plus = torch.from_numpy((wa[:, 2] & np.uint64(1)).astype(np.bool_)).to(dev)
+        swap = torch.from_numpy((wa[:, 2] & np.uint64(2)).astype(np.bool_)).to(dev)
+        w1, w2 = _square_window(row1, col1, side, dev), _square_window(row2, col2, side, dev)
+        e = torch.tensor(float(np.float32(eps)), dtype=torch.float32, device=dev)
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        d = xb - x0
+        qd = d * d
+        S1, SU, SI = torch.where(w1, qd, zero).sum(1), torch.where(w1 | w2, qd, zero).sum(1), qd.sum(1)
+        b = 1e-10 + S1.sqrt()
+        n = _square_l2_pattern_rows(row1, col1, side, plus, swap, dev).reshape(M, 784) + d / b[:, None]
+        SN = torch.where(w1, n * n, zero).sum(1)
+        h = e * e - SI
+        h = torch.where(h < 0, zero, h)                                                          # (a NaN passes)
+        f = (h + SU).sqrt() / SN.sqrt()
+        dn = torch.where(w1, n * f[:, None], torch.where(w2, zero, d))
+        SD = (dn * dn).sum(1)
+        prop = (x0 + (dn / SD.sqrt()[:, None]) * e).clamp(float(np.float32(lo)), float(np.float32(hi)))
+        prop = torch.where(((SN == 0) | (SD == 0))[:, None], xb, prop)
+        xc = torch.where((active & ~broken)[:, None], prop, torch.where(active[:, None], xb, x_cand))
+    margin_bits = torch.where(active, margin, square_state_margin(state) if not first else margin)
+    new = torch.stack((margin_bits.contiguous().view(torch.int32), used, done, spare), dim=1)
+    return xb, xc, new
+
+
+def square_l2_init(x0: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, id_base: int = 0,
+                   out: torch.Tensor | None = None, M: int | None = None,
+                   tables: torch.Tensor | None = None) -> torch.Tensor:
+    """The start of an L2 Square Attack (``csrc/kernels/square.hip``), one launch: ``out[i]`` = the tiled point of
+    ``square_l2_init_reference`` for the M images ``x0``, in ``square_init``'s conventions.  ``tables``:
+    ``square_l2_tables`` of the device (looked up when None).  Bit for bit the reference."""
+    if x0.dim() != 2 or x0.device.type != "cuda":
+        raise ValueError("square_l2_init: x0 must be a float32 [M, 784] tensor on the GPU")
+    M = int(x0.shape[0] if M is None else M)
+    _square_common("square_l2_init", eps, lo, hi, int(id_base), M)
+    _f32_rows("square_l2_init", "x0", x0, M, x0.device, at_least="M")
+    out = _out_rows("square_l2_init", "out", out, M, x0.device, at_least="M")
+    if out.data_ptr() == x0.data_ptr():
+        raise ValueError("square_l2_init: x0 and out must be two buffers")
+    tab = _square_l2_table_ptr("square_l2_init", tables, SQUARE_L2_INIT_SIDE, x0.device)
+    _C().square_l2_init(native.ptr(x0), native.ptr(out), tab, float(eps), float(lo), float(hi),
+                        int(seed) & (2 ** 64 - 1), int(id_base), M, _s())
+    return out
+
+
+def square_l2_step(logp: torch.Tensor, y: torch.Tensor, x0: torch.Tensor, x_best: torch.Tensor, x_cand: torch.Tensor,
+                   state: torch.Tensor, eps: float, lo: float, hi: float, seed: int = 0, q: int = 1, side: int = 3,
+                   id_base: int = 0, first: bool = False, last: bool = False, targeted: bool = False,
+                   M: int | None = None, tables: torch.Tensor | None = None) -> None:
+    """One L2 Square Attack query per image (``csrc/kernels/square.hip``), one launch, in place: ``square_step``'s
+    operands and rules with the proposal of ``square_l2_step_reference``.  ``side``: odd, in [3, 27]; ``tables``:
+    ``square_l2_tables`` of the device (looked up when None).  The record, ``x_best`` and the decisions are bit for
+    bit the reference's; ``x_cand`` up to the order of its five sums."""
+    if x_cand.dim() != 2 or x_cand.device.type != "cuda":
+        raise ValueError("square_l2_step: x_cand must be a float32 [M, 784] tensor on the GPU")
+    dev = x_cand.device
+    M = int(x_cand.shape[0] if M is None else M)
+    _square_common("square_l2_step", eps, lo, hi, int(id_base), M)
+    rows = (("x0", x0), ("x_best", x_best), ("x_cand", x_cand))
+    for what, t in rows:
+        _f32_rows("square_l2_step", what, t, M, dev, at_least="M")
+    _df_vec("square_l2_step", "logp", logp, torch.float32, NCLS * M, dev, "10 M")
+    _df_vec("square_l2_step", "y", y, torch.int32, M, dev, "M")
+    _df_vec("square_l2_step", "state", state, torch.int32, 4 * M, dev, "4 M")
+    if len({t.data_ptr() for _, t in rows}) != len(rows):
+        raise ValueError("square_l2_step: x0, x_best and x_cand must be three buffers")
+    tab = _square_l2_table_ptr("square_l2_step", tables, side, dev)
+    if not 0 <= int(q) < 1 << 32:
+        raise ValueError("square_l2_step: q must fit 32 bits")
+    p = native.ptr
+    _C().square_l2_step(p(logp), p(y), p(x0), p(x_best), p(x_cand), p(state), tab, float(eps), float(lo), float(hi),
+                        int(seed) & (2 ** 64 - 1), int(q), int(id_base), int(side), bool(first), bool(last),
+                        bool(targeted), M, _s())
 
 
 def adadelta_step(ms, region: int = 0, advance_step: bool = False, grid: int = 0, wt: bool = False) -> None:

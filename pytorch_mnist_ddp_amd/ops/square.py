@@ -1,5 +1,5 @@
 """Square Attack (Andriushchenko, Croce, Flammarion, Hein, ECCV 2020: the score-based black-box attack of
-AutoAttack), L-inf, on the fused MI355X kernels: the native loop behind ``Predictor.square_attack``.
+AutoAttack), L-inf and L2, on the fused MI355X kernels: the native loop behind ``Predictor.square_attack``.
 
 The attack reads nothing but the log-probabilities of its candidates: no gradient, so a net whose gradients are
 masked gets no credit for it.  One query is four launches on the current stream, with no autograd, no allocation and
@@ -11,7 +11,9 @@ no host sync:
 
 preceded once by ``square_init`` (the stripe start, query 0).  ``queries`` queries are ``queries`` rounds: round 0 has
 ``first``, round ``queries - 1`` has ``last``; round j writes the proposal of query index j + 1 with the side
-``functional.square_sides`` gives it.
+``functional.square_sides`` gives it.  ``norm="l2"`` is the same loop on ``square_l2_init`` / ``square_l2_step`` with
+the odd sides of ``functional.square_sides_l2`` and the pattern tables of ``functional.square_l2_tables``: four
+launches a query as well.
 """
 from __future__ import annotations
 
@@ -19,7 +21,8 @@ import torch
 
 from . import native
 from .chain import EvalChain
-from .functional import SQUARE_DONE, SQUARE_QUERIES, EvalBuffers, square_sides, square_state_margin
+from .functional import (SQUARE_DONE, SQUARE_L2_INIT_SIDE, SQUARE_QUERIES, EvalBuffers, square_l2_table_offset,
+                         square_l2_tables, square_norm, square_sides, square_sides_l2, square_state_margin)
 from .fused_net import fused_state
 
 
@@ -47,7 +50,8 @@ def square_runs(ids) -> list:
 
 
 def fused_square_attack(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, queries: int, lo: float, hi: float,
-                        p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64):
+                        p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64,
+                        norm: str = "linf"):
     """``(x_best, margin_best, queries_used)``: the L-inf Square Attack with at most ``queries`` queries per image on
     the margin of ``labels`` (untargeted lp[y] - max_{j != y} lp[j]; ``targeted``: ``labels`` are the classes to reach
     and the negative is used; < 0: broken), in inference semantics (no dropout), inside the ``eps`` box around ``x0``
@@ -63,13 +67,19 @@ def fused_square_attack(net, x0: torch.Tensor, labels: torch.Tensor, eps: float,
     Images with consecutive ids run together (``square_runs``).  ``check_every`` = k > 0 reads a run's ``done`` flags
     on the host after every k queries and ends the run once every image is broken; 0 never syncs; the result does
     not depend on it by a bit.  The candidate rows and the activation set stay on the net's fused state, the call
-    allocates the results; the net's mode, parameters and ``.grad`` are untouched."""
+    allocates the results; the net's mode, parameters and ``.grad`` are untouched.
+
+    ``norm="l2"``: the L2 Square Attack - ``eps`` is the radius of the L2 ball, the start is 25 tiles of the pattern
+    E_5, a query moves the perturbation's mass between two windows and rescales it to the sphere
+    (``functional.square_l2_step_reference`` has the exact form).  The same loop, launch for launch; the pattern
+    tables stay on the net's fused state."""
+    l2 = square_norm("fused_square_attack", norm)
     queries, check_every = int(queries), int(check_every)
     if queries < 1 or queries >= 1 << 32:
         raise ValueError("fused_square_attack: queries must be in [1, 2**32)")
     if check_every < 0:
         raise ValueError(f"fused_square_attack: check_every must be >= 0, got {check_every}")
-    sides = square_sides(p_init, queries)
+    sides = square_sides_l2(p_init, queries) if l2 else square_sides(p_init, queries)
     st = fused_state(net)
     st.sync()                                   # once: the bf16 shadows follow the parameters
     dev = st.ms.device
@@ -96,15 +106,30 @@ def fused_square_attack(net, x0: torch.Tensor, labels: torch.Tensor, eps: float,
     C, s, p = native.load(), native.stream_handle(), native.ptr
     px0, pbest, pcand, plab, pstate, plogp = p(x0), p(x_best), p(buf.x), p(lab), p(state), p(buf.logp)
     seed = int(seed) & (2 ** 64 - 1)
-    run, step = chain.run, C.square_step
+    run, step = chain.run, C.square_l2_step if l2 else C.square_step
+    if l2:
+        tab = getattr(st, "square_l2_tab", None)
+        if tab is None or tab.device != dev:
+            tab = st.square_l2_tab = square_l2_tables(dev)
+        ptab = p(tab)
+        side_tab = [ptab + 4 * square_l2_table_offset(v) for v in sides] + [ptab]     # (the last round draws nothing)
+        sides = sides + (3,)
     for i0, m in runs:
         o784, o4, o16, idb = 3136 * i0, 4 * i0, 16 * i0, ids[i0]
-        C.square_init(px0 + o784, pcand, eps, lo, hi, seed, idb, m, s)
+        if l2:
+            C.square_l2_init(px0 + o784, pcand, ptab + 4 * square_l2_table_offset(SQUARE_L2_INIT_SIDE), eps, lo, hi,
+                             seed, idb, m, s)
+        else:
+            C.square_init(px0 + o784, pcand, eps, lo, hi, seed, idb, m, s)
         for j in range(queries):
             last = j == queries - 1
             run(m, xin=pcand)
-            step(plogp, plab + o4, px0 + o784, pbest + o784, pcand, pstate + o16, eps, lo, hi, seed, j + 1, idb,
-                 1 if last else sides[j], j == 0, last, targeted, m, s)
+            if l2:
+                step(plogp, plab + o4, px0 + o784, pbest + o784, pcand, pstate + o16, side_tab[j], eps, lo, hi, seed,
+                     j + 1, idb, sides[j], j == 0, last, targeted, m, s)
+            else:
+                step(plogp, plab + o4, px0 + o784, pbest + o784, pcand, pstate + o16, eps, lo, hi, seed, j + 1, idb,
+                     1 if last else sides[j], j == 0, last, targeted, m, s)
             if check_every and (j + 1) % check_every == 0 and not last:
                 seen[:m].copy_(state[i0:i0 + m, SQUARE_DONE])             # the one host sync: every image frozen?
                 if bool((seen[:m] != 0).all()):

@@ -13,6 +13,11 @@ alternated samples; the table gives the median and the min-max spread), in us pe
 Each batch size runs in a child process of its own under a time limit; after a child that fails no other is started.
 
     python tools/square_bench.py [--out profiles/square/square_bench.txt]
+
+``--norm l2``: the L2 attack (eps 2.0) - the native L2 loop beside the native L-inf loop in the same process (both four
+launches a query), and ``square_l2_step`` (side 9, every image live) back to back; no host loop, no ratio.
+
+    python tools/square_bench.py --norm l2 [--out profiles/square/square_bench_l2.txt]
 """
 import argparse
 import os
@@ -53,6 +58,47 @@ def host_loop(pr, x0, y, eps, queries, seed):
         x_best, x_cand, state = Fk.square_step_reference(lp, y, x0, x_best, x_cand, state, eps, PIXEL_LO, PIXEL_HI, seed,
                                                          j + 1, 1 if last else sides[j], first=j == 0, last=last)
     return x_best
+
+
+def one_l2(B: int, queries: int, rounds: int) -> str:
+    import torch
+
+    from pytorch_mnist_ddp_amd.data.datasets import MNIST_STD, load_mnist
+    from pytorch_mnist_ddp_amd.inference import _PIXEL_LUT, PIXEL_HI, PIXEL_LO
+    from pytorch_mnist_ddp_amd.models.net import Net
+    from pytorch_mnist_ddp_amd.ops import functional as Fk
+    from pytorch_mnist_ddp_amd.ops.square import fused_square_attack
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(1)
+    net = Net().to(dev)
+    test = load_mnist(synthetic_data=True, train=False, synthetic_size=B, verbose=False)
+    x0 = _PIXEL_LUT.to(dev)[test.device_images(dev).reshape(-1, 784)[:B].long()].contiguous()
+    y = test.targets.long().to(dev)[:B]
+    eps2, epsi = 2.0 / MNIST_STD, 0.3 / MNIST_STD
+    logits = torch.randn(B, 10, device=dev)
+    logits[torch.arange(B, device=dev), y] += 10.0          # (the label leads: a margin > 0, equal from launch to launch)
+    logp = torch.log_softmax(logits, dim=1)
+    y32 = y.to(torch.int32)
+    x_best = Fk.square_l2_init(x0, eps2, PIXEL_LO, PIXEL_HI, 1)
+    x_cand = Fk.square_l2_init(x0, eps2, PIXEL_LO, PIXEL_HI, 2)
+    fixed = torch.tensor([0x42C80000, 3, 0, 0], dtype=torch.int32, device=dev).repeat(B, 1).contiguous()   # 100.0f
+    tables = Fk.square_l2_tables(dev)
+
+    def step():
+        Fk.square_l2_step(logp, y32, x0, x_best, x_cand, fixed, eps2, PIXEL_LO, PIXEL_HI, 0, 7, 9, tables=tables)
+
+    arms = {"l2": lambda: fused_square_attack(net, x0, y, eps2, queries, PIXEL_LO, PIXEL_HI, check_every=0, norm="l2"),
+            "linf": lambda: fused_square_attack(net, x0, y, epsi, queries, PIXEL_LO, PIXEL_HI, check_every=0),
+            "step": step}
+    reps = {"l2": max(1, 64 // B), "linf": max(1, 64 // B), "step": 200}
+    per = {"l2": queries, "linf": queries, "step": 1}
+    for f in arms.values():
+        timed(f, 1)
+    res = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, f in arms.items():
+            res[k].append(timed(f, reps[k]) / per[k])
+    return f"{B:>5} {fmt(res['l2']):>29} {fmt(res['linf']):>29} {fmt(res['step']):>29}"
 
 
 def one(B: int, queries: int, rounds: int) -> str:
@@ -106,18 +152,22 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds a batch size may take")
     ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--norm", choices=("linf", "l2"), default="linf")
     ap.add_argument("--one", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one is not None:
-        print(one(a.one, a.queries, a.rounds))
+        print((one_l2 if a.norm == "l2" else one)(a.one, a.queries, a.rounds))
         return 0
     lines = [f"square_bench: {a.queries} queries a sample, {a.rounds} samples; us per query, median [min-max]",
              f"{'B':>5} {'native':>29} {'host loop':>29} {'ratio':>6} {'square_step alone':>29}"]
+    if a.norm == "l2":
+        lines = [f"square_bench --norm l2: {a.queries} queries a sample, {a.rounds} samples; us per query, median "
+                 f"[min-max]", f"{'B':>5} {'native L2':>29} {'native Linf':>29} {'square_l2_step alone':>29}"]
     status = 0
     for B in (int(v) for v in a.batches.split(",")):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(B), "--queries", str(a.queries),
-                                "--rounds", str(a.rounds)], capture_output=True, text=True, timeout=a.step_timeout)
+                                "--rounds", str(a.rounds), "--norm", a.norm], capture_output=True, text=True, timeout=a.step_timeout)
         except subprocess.TimeoutExpired:
             lines.append(f"{B:>5} timed out after {a.step_timeout:g} s; nothing more was started")
             status = 3
