@@ -47,6 +47,7 @@ void mnist::preload_all_kernels() {
   preload_square();
   preload_square_l2();
   preload_fab();
+  preload_apgd_l1();
 }
 
 namespace {
@@ -595,6 +596,22 @@ PYBIND11_MODULE(_C, m) {
      "one Auto-PGD iteration per image: counters and best point, checkpoint (halve eta, restart from the best), "
      "momentum step; fstate [M][4] = eta, loss_best, loss_prev, loss_check; istate [M][4] = n_up, reduced, iters, "
      "restarted");
+
+  // ---------------- L1 Auto-PGD ----------------
+  m.def("apgd_l1_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t x0, uintptr_t x, uintptr_t x_best,
+                           uintptr_t g_best, uintptr_t fstate, uintptr_t istate, float sign, float eps, float lo,
+                           float hi, bool first, bool last, int window, int M, uintptr_t stream) {
+    ApgdL1StepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const float>(x0), P<float>(x), P<float>(x_best),
+                     P<float>(g_best), P<float>(fstate), P<int32_t>(istate), sign, eps, lo, hi, first ? 1 : 0,
+                     last ? 1 : 0, window};
+    launch_apgd_l1_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("x0"), py::arg("x"), py::arg("x_best"), py::arg("g_best"),
+     py::arg("fstate"), py::arg("istate"), py::arg("sign"), py::arg("eps"), py::arg("lo"), py::arg("hi"),
+     py::arg("first"), py::arg("last"), py::arg("window"), py::arg("M"), py::arg("stream"),
+     "one L1 Auto-PGD iteration per image: best point, checkpoint (sparsity rule: restart or shrink eta), sparse "
+     "top-k step, exact projection onto the L1 ball and the box; fstate [M][4] = eta, loss_best, lam, thr; istate "
+     "[M][4] = k_sel, sp_old, iters, restarted");
 
   // ---------------- Square Attack ----------------
   m.attr("SQUARE_PHILOX_DOMAIN") = SQUARE_PHILOX_DOMAIN;

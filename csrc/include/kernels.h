@@ -506,6 +506,39 @@ struct ApgdStepArgs {
 // M in [1, INPUT_GRAD_MAX_B], eps >= 0, sign +-1, window >= 0, not first and last at once; l2: the L2 form
 void launch_apgd_step(const ApgdStepArgs& a, int M, bool l2, hipStream_t s);
 
+// ---------------- L1 Auto-PGD (apgd_l1.hip; Croce & Hein 2021, "Mind the box") ----------------
+// One iteration's per-image update in one launch, one workgroup per image, fp32, no atomics, on the same operands as
+// apgd_step.  With L = sign * loss_rows[i] and g = sign * dx[i]: the best point is brought up to date; a launch that
+// closes a checkpoint window counts the changed pixels sp of the best point, sets k_sel = ceil(2 sp / 3) and either
+// restarts from the best point with eta = eps (when 100 sp < 95 sp_old) or shrinks eta by 1.5 (not below eps / 10);
+// then the sparse step on the elements whose |g| reaches the k_sel-th largest, and the exact projection onto the
+// intersection of the L1 ball of radius eps around x0 and the box [lo, hi].  There is no momentum and no x_old.
+// The exact form, the sort network and the NaN rules are in apgd_l1.hip.
+// PER-IMAGE SCALARS, two 16-byte records an image (both arrays 16-byte aligned):
+//   fstate[i] = {eta, loss_best, lam, thr}            (fp32; loss_best carries `sign`; lam: the multiplier of the last
+//                                                      projection, 0 when the ball did not bind; thr: the k_sel-th
+//                                                      largest |g| of the last step)
+//   istate[i] = {k_sel, sp_old, iters, restarted}     (int32; restarted: 1 when the last update started from x_best)
+// first: reads no record and no x_best / g_best, writes all of them.  last: only the best point (loss_best, x_best,
+// g_best) is brought up to date; x and the rest keep their values; window is ignored.  Rows and records past M are
+// untouched.
+struct ApgdL1StepArgs {
+  const float* dx;            // fp32 [M][784] d loss / d x at the iterate
+  const float* loss_rows;     // [M] the loss at the iterate
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* x;                   // fp32 [M][784] the iterate (the xin of the next chain run)
+  float* x_best;              // fp32 [M][784] the point of the highest sign * loss so far
+  float* g_best;              // fp32 [M][784] its dx row, stored raw (without sign)
+  float* fstate;              // [M][4]
+  int32_t* istate;            // [M][4]
+  float sign;                 // +1 untargeted (ascent), -1 targeted (the labels' loss is descended)
+  float eps, lo, hi;          // L1 radius, valid range: normalised units
+  int first, last;            // flags: launch 0 / the launch after the last update
+  int window;                 // > 0: this launch is a checkpoint; else 0
+};
+// M in [1, INPUT_GRAD_MAX_B], eps >= 0, sign +-1, window >= 0, not first and last at once
+void launch_apgd_l1_step(const ApgdL1StepArgs& a, int M, hipStream_t s);
+
 // ---------------- Square Attack (square.hip; Andriushchenko, Croce, Flammarion, Hein 2020), L-inf ----------------
 // A score-based black-box attack: one query is one eval forward of the candidate x_cand, then square_step reads the
 // candidate's margin from head_eval's logp row (untargeted lp[y] - max_{j != y} lp[j]; targeted the negative; < 0:
@@ -663,6 +696,7 @@ void preload_apgd();
 void preload_square();
 void preload_square_l2();
 void preload_fab();
+void preload_apgd_l1();
 void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

@@ -62,8 +62,9 @@ from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
 from .ops.chain import chain_loss
-from .ops.functional import (APGD_LOSS_BEST, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE, SQUARE_QUERIES,
-                             apgd_checkpoints, apgd_step_reference, attr_path_reference, attr_reduce_reference,
+from .ops.functional import (APGD_L1_LOSS_BEST, APGD_LOSS_BEST, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE,
+                             SQUARE_QUERIES, apgd_checkpoints, apgd_l1_checkpoints, apgd_l1_step_reference,
+                             apgd_step_reference, attr_path_reference, attr_reduce_reference,
                              deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_l2_init_reference,
                              square_l2_step_reference, square_norm, square_sides, square_sides_l2, square_state_margin,
                              square_step_reference)
@@ -159,6 +160,37 @@ def reference_auto_pgd(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: fl
                                         last=j == steps, window=window.get(j, 0))
     loss_best = state[4][:, APGD_LOSS_BEST]
     return state[2], (-loss_best if targeted else loss_best.clone())
+
+
+def reference_auto_pgd_l1(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int, lo: float,
+                          hi: float, targeted: bool = False, loss: str = "ce",
+                          true_labels: torch.Tensor | None = None):
+    """``ops.apgd.fused_auto_pgd_l1`` in torch float32 on any device: the same ``steps + 1`` rounds - the per-row loss
+    and its gradient by autograd over ``Net.forward_reference`` in eval mode (the net's mode is restored afterwards),
+    then ``apgd_l1_step_reference`` with the same ``first`` / ``last`` flags and the checkpoints of
+    ``apgd_l1_checkpoints``.  Same arguments (float32 [B, 784] normalised images, normalised units), same return:
+    ``(x_best [B, 784], loss_best [B])``.  The CPU / fp32 path of ``Predictor.auto_pgd_l1`` and the reference of its
+    GPU tests."""
+    if steps < 1:
+        raise ValueError("reference_auto_pgd_l1: steps must be at least 1")
+    B, steps = x0.shape[0], int(steps)
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(x0.device)
+    window = dict(apgd_l1_checkpoints(steps))
+    sign = -1 if targeted else 1
+    loss_of = _loss_rows_fn("reference_auto_pgd_l1", loss, targeted, y, true_labels)
+    state = (x0.clone(), None, None, None, None)
+    with _eval_mode(net):
+        for j in range(steps + 1):
+            xg = state[0].clone().requires_grad_()
+            with torch.enable_grad():
+                lp = net.forward_reference(xg.view(B, 1, 28, 28))
+                g, = torch.autograd.grad(loss_of(lp).sum(), xg)
+            loss_rows = loss_of(lp.detach())
+            state = apgd_l1_step_reference(g, loss_rows, x0, *state, sign, eps, lo, hi, first=j == 0,
+                                           last=j == steps, window=window.get(j, 0))
+    loss_best = state[3][:, APGD_L1_LOSS_BEST]
+    return state[1], (-loss_best if targeted else loss_best.clone())
 
 
 def reference_square_attack(net: Net, x0: torch.Tensor, labels: torch.Tensor, eps: float, queries: int, lo: float,
@@ -621,6 +653,78 @@ class Predictor:
             total += F.nll_loss(lp, y, reduction='none').double().sum()
             hits += (lp.argmax(dim=1) == y).sum()
         return float(total.item()), int(hits.item()), n
+
+    def auto_pgd_l1(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 10.0, steps: int = 100,
+                    targeted: bool = False, loss: str = "ce", true_labels: torch.Tensor | None = None):
+        """(x_adv, log_probs, loss_best): L1 Auto-PGD (Croce & Hein 2021, "Mind the box") adversarial examples of
+        ``x`` - sparse perturbations that move a few pixels a long way.  Every step moves only the coordinates with
+        the largest gradients (their number follows the sparsity of the best point), is projected exactly onto the
+        intersection of the L1 ball and the pixel box, and the step size is reset or shrunk at checkpoints every 4 %
+        of ``steps``; there is no step size to choose and no momentum.  ``x_adv``: float32 [B,1,28,28] in NORMALISED
+        units, the point of the highest loss among the ``steps + 1`` iterates (``targeted``: the lowest), with at most
+        ``eps`` of L1 mass away from ``x`` and inside the valid pixel range [0, 1]; ``log_probs`` and ``loss_best``:
+        as ``auto_pgd``.
+
+        ``eps``: the L1 radius in pixel units on the [0, 1] scale (10 is usual for MNIST).  ``labels``, ``targeted``,
+        ``loss`` ("ce", "cw", "dlr") and ``true_labels``: as ``auto_pgd``.  The run starts from the clean image:
+        there is no random start and there are no restarts.  Inference semantics: no dropout; the net's mode,
+        parameters and gradients are untouched.  GPU with ``dtype="bf16"``: the native loop
+        ``ops.apgd.fused_auto_pgd_l1``; CPU, or ``dtype="fp32"``: ``reference_auto_pgd_l1``."""
+        B = self._check_input(x)
+        if loss not in ("ce", "cw", "dlr"):
+            raise ValueError(f"auto_pgd_l1: loss must be 'ce', 'cw' or 'dlr', got {loss!r}")
+        if targeted and labels is None:
+            raise ValueError("auto_pgd_l1: a targeted attack needs labels (the target classes)")
+        if not eps >= 0:
+            raise ValueError(f"auto_pgd_l1: eps must be >= 0, got {eps}")
+        if isinstance(steps, bool) or steps != int(steps) or steps < 1:
+            raise ValueError(f"auto_pgd_l1: steps must be a positive integer, got {steps}")
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels("auto_pgd_l1", labels, B, check_range=True)
+        true_labels = self._true_labels("auto_pgd_l1", loss, targeted, labels, true_labels, x0, B)
+        eps_n, _, lo, hi = adversarial_units(eps, int(steps), None)
+        if self.native:
+            from .ops.apgd import fused_auto_pgd_l1 as attack
+        else:
+            attack = reference_auto_pgd_l1
+        x_adv, loss_best = attack(self.net, x0, labels, eps_n, int(steps), lo, hi, targeted=targeted, loss=loss,
+                                  true_labels=true_labels)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        return x_adv, self._forward(x_adv)[0], loss_best
+
+    def robust_evaluate_apgd_l1(self, images_u8: torch.Tensor, labels: torch.Tensor, eps: float, steps: int = 100,
+                                batch_size: int = 1000, loss: str = "ce"):
+        """(loss_sum, correct, n, median_l0): the first three as ``robust_evaluate``, with the untargeted
+        ``auto_pgd_l1`` of L1 radius ``eps`` against the true labels as the attack, ``batch_size`` images at a time;
+        ``loss_sum`` is the NLL of the attacked images.  ``median_l0``: the median count of changed pixels over the
+        images that are correct on the clean input and broken after the attack (None when there is none; the median
+        of an even count is the mean of the middle two)."""
+        n = int(labels.shape[0])
+        if images_u8.dtype != torch.uint8 or images_u8.shape[0] != n:
+            raise ValueError("robust_evaluate_apgd_l1: images_u8 must be uint8 with one row per label")
+        if batch_size < 1:
+            raise ValueError("robust_evaluate_apgd_l1: batch_size must be positive")
+        lab = labels.long().to(self.device)
+        total = torch.zeros((), dtype=torch.float64, device=self.device)
+        hits = torch.zeros((), dtype=torch.int64, device=self.device)
+        changed = []
+        for i in range(0, n, batch_size):
+            y = lab[i:i + batch_size]
+            B = y.shape[0]
+            x0 = _rows_f32(images_u8[i:i + batch_size], B, self.device)
+            clean = self._forward(x0.view(B, 1, 28, 28))[1] == y
+            x_adv, lp, _ = self.auto_pgd_l1(x0.view(B, 1, 28, 28), y, eps, steps, loss=loss)
+            right = lp.argmax(dim=1) == y
+            total += F.nll_loss(lp, y, reduction='none').double().sum()
+            hits += right.sum()
+            l0 = (x_adv.reshape(B, 784) != x0).sum(dim=1)
+            changed.append(l0[clean & ~right].double().cpu())
+        changed = torch.cat(changed)
+        median = float(changed.quantile(0.5)) if changed.numel() else None
+        return float(total.item()), int(hits.item()), n, median
 
     def square_attack(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.3, queries: int = 1000,
                       p_init: float = 0.8, seed: int = 0, ids=None, targeted: bool = False, check_every: int = 64,
@@ -1109,6 +1213,13 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--apgd-seed', type=int, default=0, help='seed of the random starts (default: 0)')
     ap.add_argument('--apgd-loss', choices=('ce', 'cw', 'dlr'), default='ce',
                     help='loss Auto-PGD ascends: cross-entropy, the CW margin or the DLR loss (default: ce)')
+    ap.add_argument('--apgd-l1-eps', type=float, default=None, metavar='E',
+                    help='also report loss and accuracy under the L1 Auto-PGD attack (sparse perturbations) of L1 '
+                         'radius E, in pixel units on the [0, 1] scale; 10 is usual for MNIST (default: off)')
+    ap.add_argument('--apgd-l1-steps', type=int, default=100, metavar='N',
+                    help='L1 Auto-PGD iterations (default: 100)')
+    ap.add_argument('--apgd-l1-loss', choices=('ce', 'cw', 'dlr'), default='ce',
+                    help='loss L1 Auto-PGD ascends (default: ce)')
     ap.add_argument('--ensemble-eps', type=float, default=None, metavar='E',
                     help='also report the accuracy of the images that survive every attack of an L-inf ensemble of '
                          'radius E, in pixel units on the [0, 1] scale: Auto-PGD on the cross-entropy, targeted '
@@ -1206,6 +1317,14 @@ def auto_pgd_line(eps: float, steps: int, restarts: int, loss: float, correct: i
     figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
     return (f"Auto-PGD set ({'L2' if norm == 'l2' else 'Linf'} eps={eps:g}, steps={steps}, restarts={restarts}"
             f"{_loss_tag(loss_name)}): {figures}")
+
+
+def auto_pgd_l1_line(eps: float, steps: int, loss: float, correct: int, n: int, median, loss_name: str = "ce") -> str:
+    """The ``Auto-PGD set (L1 ...)`` line of ``mnist_predict.py --apgd-l1-eps``, in the number formats of
+    ``adversarial_line``; ``median``: the median changed pixels of the broken images, None when none broke."""
+    figures = test_line(loss, correct, n).split(": ", 1)[1].rstrip("\n")
+    return (f"Auto-PGD set (L1 eps={eps:g}, steps={steps}{_loss_tag(loss_name)}): {figures}, "
+            f"median pixels changed: {'n/a' if median is None else format(median, 'g')}")
 
 
 def ensemble_line(eps: float, targets: int, correct: int, n: int, fab: bool = False, norm: str = "linf") -> str:
@@ -1399,6 +1518,15 @@ def predict_main(argv=None) -> int:
             record.update(ensemble_fab_steps=args.ensemble_fab_steps)
         if args.ensemble_norm != "linf":
             record.update(ensemble_norm=args.ensemble_norm)
+    if args.apgd_l1_eps is not None:
+        l1_loss, l1_correct, _, l1_median = predictor.robust_evaluate_apgd_l1(
+            images, data.targets, args.apgd_l1_eps, args.apgd_l1_steps, args.batch_size, loss=args.apgd_l1_loss)
+        print(auto_pgd_l1_line(args.apgd_l1_eps, args.apgd_l1_steps, l1_loss / n, l1_correct, n, l1_median,
+                               args.apgd_l1_loss))
+        record.update(apgd_l1_eps=args.apgd_l1_eps, apgd_l1_steps=args.apgd_l1_steps, apgd_l1_loss=l1_loss / n,
+                      apgd_l1_correct=l1_correct, apgd_l1_median_l0=l1_median)
+        if args.apgd_l1_loss != "ce":
+            record.update(apgd_l1_loss_name=args.apgd_l1_loss)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

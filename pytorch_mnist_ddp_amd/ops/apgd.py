@@ -18,6 +18,10 @@ stream, with no autograd ``Function``, no allocation and no host sync:
 ``loss="cw"`` / ``"dlr"`` put ``head_margin`` in ``head_train``'s place (``GradChain(loss=...)``): ``apgd_step`` only
 sees a loss per row and dx, so the CW margin and the DLR loss (targeted: the APGD-T objective) take the same six
 launches.
+
+``fused_auto_pgd_l1`` is the L1 attack of Croce & Hein (ICML 2021) on the same chain: ``apgd_l1_step``
+(csrc/kernels/apgd_l1.hip) stands in ``apgd_step``'s place - six launches a round as well, with the schedule of
+``functional.apgd_l1_checkpoints`` - and ``fused_auto_pgd`` is untouched by it.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import torch
 
 from . import native
 from .chain import GradChain, chain_loss, margin_operands
-from .functional import APGD_LOSS_BEST, apgd_checkpoints
+from .functional import APGD_L1_LOSS_BEST, APGD_LOSS_BEST, apgd_checkpoints, apgd_l1_checkpoints
 from .fused_net import fused_state
 
 
@@ -82,4 +86,54 @@ def fused_auto_pgd(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, step
         step(pdx, ploss, *rest, j == 0, j == steps, window.get(j, 0), B, s)
     chain.release()                             # last use enqueued: the next taker is stream ordered after it
     loss_best = fstate[:, APGD_LOSS_BEST]
+    return x_best, (-loss_best if targeted else loss_best.clone())
+
+
+def fused_auto_pgd_l1(net, x0: torch.Tensor, labels: torch.Tensor, eps: float, steps: int, lo: float, hi: float,
+                      targeted: bool = False, loss: str = "ce", true_labels: torch.Tensor | None = None):
+    """``(x_best, loss_best)``: L1 Auto-PGD (Croce & Hein 2021) with ``steps`` updates from the clean point, in
+    inference semantics (no dropout), inside the L1 ball of radius ``eps`` around ``x0`` and the range [lo, hi]
+    (``functional.apgd_l1_step_reference`` has the exact form): a sparse step on the top-k coordinates of the gradient,
+    the exact projection onto the intersection of ball and box, a step size driven by the sparsity of the best point.
+    ``targeted``, ``loss``, ``true_labels``: as ``fused_auto_pgd`` - the kernel sees a loss per row and dx only.
+
+    ``x0``: float32 [B, 784] normalised images on the net's device; ``labels``: [B] integers in [0, 10) (not checked
+    here: ``Predictor.auto_pgd_l1`` does); ``eps``, ``lo``, ``hi`` in normalised units.  Returns the float32 [B, 784]
+    point of the highest loss (targeted: the lowest) among the ``steps + 1`` iterates and float32 [B] its loss as the
+    chain's head computed it.  ``steps + 1`` rounds of six launches, every buffer allocated before the loop, no host
+    sync; the net's mode, parameters and ``.grad`` are left as they were."""
+    if steps < 1:
+        raise ValueError("fused_auto_pgd_l1: steps must be at least 1")
+    if not eps >= 0:
+        raise ValueError("fused_auto_pgd_l1: eps must be >= 0")
+    kind = chain_loss("fused_auto_pgd_l1", loss, targeted)
+    st = fused_state(net)
+    st.sync()                                   # once: the bf16 shadows follow the parameters
+    dev = st.ms.device
+    if x0.dim() != 2 or x0.shape[1] != 784 or x0.dtype != torch.float32 or x0.device != dev:
+        raise ValueError("fused_auto_pgd_l1: x0 must be float32 [B, 784] on the net's device")
+    B = x0.shape[0]
+    if labels.numel() != B:
+        raise ValueError(f"fused_auto_pgd_l1: {labels.numel()} labels for {B} images")
+    x0 = x0.contiguous()
+    x = x0.clone(memory_format=torch.contiguous_format)                                    # the iterate
+    lab = labels.reshape(B).to(dev, torch.int32).contiguous()
+    # every element of these is written by launch 0 (dx: by every input_grad) before it is read
+    dx, x_best, g_best = (torch.empty(B, 784, dtype=torch.float32, device=dev) for _ in range(3))
+    fstate = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    istate = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    window = dict(apgd_l1_checkpoints(steps))
+    sign = -1.0 if targeted else 1.0
+    lab, tgt = margin_operands("fused_auto_pgd_l1", kind, lab, true_labels, B, dev)
+    chain = GradChain(st, B, kind)
+    C, s, p = native.load(), native.stream_handle(), native.ptr
+    px, plab, ptgt, pdx, ploss = p(x), p(lab), p(tgt), p(dx), chain.loss_rows
+    rest = (p(x0), px, p(x_best), p(g_best), p(fstate), p(istate), sign, eps, lo, hi)
+    run, grad, step = chain.run, chain.input_grad, C.apgd_l1_step
+    for j in range(steps + 1):
+        run(px, plab, B, ptgt)
+        grad(pdx, B)
+        step(pdx, ploss, *rest, j == 0, j == steps, window.get(j, 0), B, s)
+    chain.release()                             # last use enqueued: the next taker is stream ordered after it
+    loss_best = fstate[:, APGD_L1_LOSS_BEST]
     return x_best, (-loss_best if targeted else loss_best.clone())

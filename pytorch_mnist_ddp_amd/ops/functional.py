@@ -1176,6 +1176,190 @@ def apgd_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: to
                    M, _s())
 
 
+APGD_L1_N = 784
+APGD_L1_K_INIT = APGD_L1_N - (APGD_L1_N * 4) // 5          # 157: the first step moves the top 20 % of the coordinates
+# columns of the per-image records (kernels.h ApgdL1StepArgs)
+APGD_L1_ETA, APGD_L1_LOSS_BEST, APGD_L1_LAM, APGD_L1_THR = 0, 1, 2, 3          # fstate, float32 [M, 4]
+APGD_L1_K_SEL, APGD_L1_SP_OLD, APGD_L1_ITERS, APGD_L1_RESTARTED = 0, 1, 2, 3   # istate, int32 [M, 4]
+
+
+def apgd_l1_checkpoints(steps: int) -> tuple:
+    """The checkpoint schedule of L1 Auto-PGD (Croce & Hein 2021) for ``steps`` iterations: a tuple of
+    ``(iteration, k)`` - a checkpoint after every k = max(int(0.04 steps), 1) updates (1-based), the last one <=
+    ``steps``.  steps = 100: iterations 4, 8, ..., 100."""
+    n = int(steps)
+    if n < 1:
+        raise ValueError("apgd_l1_checkpoints: steps must be at least 1")
+    k = max(int(0.04 * n), 1)
+    return tuple((at, k) for at in range(k, n + 1, k))
+
+
+def apgd_l1_k_sel(sp):
+    """The coordinates the next L1 Auto-PGD steps move, from the count ``sp`` (an int or an integer tensor) of changed
+    pixels of the best point: ceil(2 sp / 3) in exact integers, at least 1 and at most 784.  (The authors' float form
+    floor((1 - sp / n / 1.5) n) counts the coordinates left out and differs by one at 34 values of sp.)"""
+    k = (2 * sp + 2) // 3
+    if isinstance(k, torch.Tensor):
+        return k.clamp(1, APGD_L1_N)
+    return min(max(int(k), 1), APGD_L1_N)
+
+
+def l1_box_projection_reference(z: torch.Tensor, x0: torch.Tensor, eps: float, lo: float, hi: float):
+    """``(delta, lam)``: per row the Euclidean projection of the perturbation ``z`` ([M, n], any float dtype and
+    device) onto the intersection of the L1 ball of radius ``eps`` and the box lo <= x0 + delta <= hi, in the sorted
+    form of ``csrc/kernels/apgd_l1.hip``.  s = sgn(z), a = |z|, cap = max(s > 0 ? hi - x0 : x0 - lo, 0), w = min(a, cap):
+
+        eps == 0:        delta = s 0, lam = 0
+        sum w <= eps:    delta = s w, lam = 0
+        otherwise:       delta = s min(max(a - lam, 0), cap),  lam the root of  sum min(max(a - lam, 0), cap) = eps
+
+    With b = max(a - cap, 0) the sum is sum_{a > lam} (a - lam) - sum_{b > lam} (b - lam); on the 2 n breakpoints
+    sorted ascending (a stable sort, the a before the b), S_k / N_k the sums over the positions >= k of +a, -b /
+    of +-1: k = the first position with N_k > 0 and S_k - tau_k N_k <= eps, lam = (S_k - eps) / N_k (a row with no
+    such position - a NaN in it - gets lam = NaN and a NaN delta)."""
+    M, n = z.shape
+    dt, dev = z.dtype, z.device
+    x0 = x0.reshape(M, n).to(dt)
+    s = torch.where(z != z, z, torch.sign(z))
+    if eps == 0:
+        return s * 0.0, torch.zeros(M, dtype=dt, device=dev)
+    a = z.abs()
+    cap = torch.where(s > 0, hi - x0, x0 - lo).clamp_min(0)
+    w = torch.where(cap < a, cap, a)
+    b = (a - cap).clamp_min(0)
+    tau, order = torch.sort(torch.cat((a, b), dim=1), dim=1, stable=True)
+    unit = torch.cat((torch.ones(M, n, dtype=dt, device=dev), -torch.ones(M, n, dtype=dt, device=dev)), dim=1)
+    unit = unit.gather(1, order)
+    S = (tau * unit).flip(1).cumsum(dim=1).flip(1)
+    N = unit.flip(1).cumsum(dim=1).flip(1)
+    ok = (N > 0) & (S - tau * N <= eps)
+    k = ok.to(torch.int8).argmax(dim=1, keepdim=True)
+    lam = ((S.gather(1, k) - eps) / N.gather(1, k))[:, 0]
+    lam = torch.where(ok.any(dim=1), lam, torch.full_like(lam, float("nan")))
+    t = a - lam[:, None]
+    t = torch.where(t < 0, torch.zeros_like(t), t)
+    t = torch.where(cap < t, cap, t)
+    inside = w.sum(dim=1) <= eps
+    return torch.where(inside[:, None], s * w, s * t), torch.where(inside, torch.zeros_like(lam), lam)
+
+
+def apgd_l1_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: torch.Tensor,
+                           x_best: torch.Tensor | None, g_best: torch.Tensor | None, fstate: torch.Tensor | None,
+                           istate: torch.Tensor | None, sign: float, eps: float, lo: float, hi: float,
+                           first: bool = False, last: bool = False, window: int = 0):
+    """``apgd_l1_step`` in torch ops on any device, in the dtype of ``dx`` (float32: the CPU / fp32 path of
+    ``Predictor.auto_pgd_l1``; float64: the oracle of the kernel's tests).  Same operands - ``dx``, ``x0``, ``x``,
+    ``x_best``, ``g_best`` [M, 784], ``loss_rows`` [M], ``fstate`` [M, 4] (eta, loss_best, lam, thr), ``istate``
+    integers [M, 4] (k_sel, sp_old, iters, restarted) - none of them modified; returns the new ``(x, x_best, g_best,
+    fstate, istate)``.  With ``first`` the last four inputs are not read (None will do).  Per image, with L = sign *
+    loss and g = sign * dx:
+
+        first:   eta = eps; loss_best = L; x_best = x; g_best = dx; k_sel = 157; sp_old = 784; iters = 0;
+                 restarted = 0; (src, gs) = (x, g)
+        else:    L > loss_best: loss_best = L, x_best = x, g_best = dx
+                 last: stop here
+                 (src, gs) = (x, g); restarted = 0
+                 window > 0: sp = #{x_best != x0}; red = 100 sp < 95 sp_old; k_sel = ``apgd_l1_k_sel(sp)``;
+                             red: eta = eps, (src, gs) = (x_best, sign g_best), restarted = 1;
+                             else eta = max(eta / 1.5, eps / 10);  sp_old = sp
+        step:    thr = the k_sel-th largest |gs|; sel = {|gs| >= thr and gs != 0} (and every NaN); m = |sel|
+                 t = src + (eta / max(m, 1)) sgn(gs) on sel, src elsewhere
+        project: delta, lam = ``l1_box_projection_reference(t - x0, x0, eps, lo, hi)``; x = clamp(x0 + delta, lo, hi);
+                 iters += 1
+
+    ``eps``, ``lo`` and ``hi`` are rounded to float32 first, as the kernel receives them."""
+    import numpy as np
+    if sign not in (1, -1) or (first and last) or window < 0:
+        raise ValueError("apgd_l1_step_reference: sign is +1 or -1, window >= 0, and a launch is not first and last")
+    if not eps >= 0:
+        raise ValueError("apgd_l1_step_reference: eps must be >= 0")
+    dt, dev = dx.dtype, dx.device
+    M = dx.shape[0]
+    eps, lo, hi = (float(np.float32(v)) for v in (eps, lo, hi))
+    sgn = float(sign)
+    x0, x = x0.reshape(M, 784).to(dt), x.reshape(M, 784).to(dt)
+    L = sgn * loss_rows.reshape(M).to(dt)
+    i32 = dict(dtype=torch.int32, device=dev)
+    eps_t = torch.full((M,), eps, dtype=dt, device=dev)
+    if first:
+        eta, loss_best = eps_t.clone(), L.clone()
+        lam, thr = torch.zeros(M, dtype=dt, device=dev), torch.zeros(M, dtype=dt, device=dev)
+        k_sel, sp_old = torch.full((M,), APGD_L1_K_INIT, **i32), torch.full((M,), APGD_L1_N, **i32)
+        iters, restarted = torch.zeros(M, **i32), torch.zeros(M, **i32)
+        xb, gb = x.clone(), dx.clone()
+    else:
+        eta, loss_best, lam, thr = fstate.reshape(M, 4).to(dt).unbind(dim=1)
+        k_sel, sp_old, iters, restarted = istate.reshape(M, 4).to(torch.int32).unbind(dim=1)
+        improved = L > loss_best
+        loss_best = torch.where(improved, L, loss_best)
+        xb = torch.where(improved[:, None], x, x_best.reshape(M, 784).to(dt))
+        gb = torch.where(improved[:, None], dx, g_best.reshape(M, 784).to(dt))
+    pack = lambda: (torch.stack((eta, loss_best, lam, thr), dim=1),                          # noqa: E731
+                    torch.stack((k_sel, sp_old, iters, restarted), dim=1))
+    if last:
+        return (x.clone(), xb, gb, *pack())
+    red = torch.zeros(M, dtype=torch.bool, device=dev)
+    if not first:
+        restarted = torch.zeros(M, **i32)
+        if window > 0:
+            sp = (xb != x0).sum(dim=1).to(torch.int32)
+            red = 100 * sp < 95 * sp_old
+            k_sel = apgd_l1_k_sel(sp)
+            # the step size is float32 state in every dtype, as the kernel keeps it (tensor divisors: a true division
+            # on every device, never a multiplication by a rounded reciprocal)
+            e32, eps32 = eta.to(torch.float32), eps_t.to(torch.float32)
+            shrunk = torch.maximum(e32 / torch.full_like(e32, 1.5), eps32 / torch.full_like(e32, 10.0))
+            eta = torch.where(red, eps_t, shrunk.to(dt))
+            restarted = red.to(torch.int32)
+            sp_old = sp
+    src = torch.where(red[:, None], xb, x)
+    gs = sgn * torch.where(red[:, None], gb, dx)
+    ag = gs.abs()
+    at = (k_sel.long().clamp(1, APGD_L1_N) - 1)[:, None]
+    thr = torch.sort(ag, dim=1, descending=True)[0].gather(1, at)[:, 0]
+    sel = ((ag >= thr[:, None]) | (gs != gs)) & (gs != 0)
+    m = sel.sum(dim=1).clamp_min(1).to(dt)
+    sg = torch.where(gs != gs, gs, torch.sign(gs))
+    t = torch.where(sel, src + (eta / m)[:, None] * sg, src)
+    delta, lam = l1_box_projection_reference(t - x0, x0, eps, lo, hi)
+    x_new = (x0 + delta).clamp(lo, hi)
+    iters = iters + 1
+    return (x_new, xb, gb, *pack())
+
+
+def apgd_l1_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x: torch.Tensor, x_best: torch.Tensor,
+                 g_best: torch.Tensor, fstate: torch.Tensor, istate: torch.Tensor, sign: float, eps: float, lo: float,
+                 hi: float, first: bool = False, last: bool = False, window: int = 0, M: int | None = None) -> None:
+    """One L1 Auto-PGD iteration per image (``csrc/kernels/apgd_l1.hip``), one launch, in place: from the gradient
+    rows ``dx`` (float32 [>= M, 784], what ``input_grad`` wrote) and losses ``loss_rows`` (float32 [>= M]) at the
+    iterate ``x``, and the clean images ``x0``, the update of ``apgd_l1_step_reference`` on ``x``, ``x_best``,
+    ``g_best`` (float32 [>= M, 784]), ``fstate`` (float32 [>= M, 4]) and ``istate`` (int32 [>= M, 4]).  float32
+    throughout, every sum in a fixed order, the counts in integers: the same operands give the same bits.  ``eps``:
+    the L1 radius in normalised units.  ``first``: no state is read, all of it is written; ``last``: only the best
+    point is brought up to date; ``window`` > 0: this launch is a checkpoint.  ``M``: the images of the launch
+    (default ``x.shape[0]``); nothing past M is touched."""
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("apgd_l1_step: x must be a float32 [M, 784] tensor on the GPU")
+    dev = x.device
+    M = int(x.shape[0] if M is None else M)
+    if M < 1 or M > APGD_MAX_M:
+        raise ValueError(f"apgd_l1_step: M = {M} images must be in [1, APGD_MAX_M = {APGD_MAX_M}] a launch")
+    rows = (("dx", dx), ("x0", x0), ("x", x), ("x_best", x_best), ("g_best", g_best))
+    for what, t in rows:
+        _f32_rows("apgd_l1_step", what, t, M, dev, at_least="M")
+    _df_vec("apgd_l1_step", "loss_rows", loss_rows, torch.float32, M, dev, "M")
+    _df_vec("apgd_l1_step", "fstate", fstate, torch.float32, 4 * M, dev, "4 M")
+    _df_vec("apgd_l1_step", "istate", istate, torch.int32, 4 * M, dev, "4 M")
+    ptrs = [t.data_ptr() for _, t in rows]
+    if len(set(ptrs)) != len(ptrs):
+        raise ValueError("apgd_l1_step: dx, x0, x, x_best and g_best must be five buffers")
+    if not (eps >= 0 and lo <= hi) or sign not in (1, -1) or int(window) < 0 or (first and last):
+        raise ValueError("apgd_l1_step: need eps >= 0, lo <= hi, sign +1 or -1, window >= 0, and not first and last")
+    p = native.ptr
+    _C().apgd_l1_step(p(dx), p(loss_rows), p(x0), p(x), p(x_best), p(g_best), p(fstate), p(istate), float(sign),
+                      float(eps), float(lo), float(hi), bool(first), bool(last), int(window), M, _s())
+
+
 SQUARE_PHILOX_DOMAIN = 0x53515231   # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
 SQUARE_MAX_M = 1 << 20              # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
 SQUARE_MAX_SIDE = 27

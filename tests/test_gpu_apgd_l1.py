@@ -1,0 +1,165 @@
+"""L1 Auto-PGD on the GPU (csrc/kernels/apgd_l1.hip).  x, lam and the L1 mass are held, per launch, to 4 x the float32
+error of ``apgd_l1_step_reference`` on that launch's operands, not below one ulp of max(|lo|, |hi|) (docs/COVERAGE.md)."""
+import copy
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import apgd_l1_ref as R
+from attr_ref import trained_net
+from pytorch_mnist_ddp_amd.data.datasets import MNIST_STD, normalize_u8
+from pytorch_mnist_ddp_amd.data.synthetic import generate
+from pytorch_mnist_ddp_amd.inference import Predictor, reference_auto_pgd_l1
+from pytorch_mnist_ddp_amd.ops import functional as Fk, native
+from pytorch_mnist_ddp_amd.ops.apgd import fused_auto_pgd_l1
+from pytorch_mnist_ddp_amd.ops.chain import GradChain
+from pytorch_mnist_ddp_amd.ops.fused_net import fused_state
+from pytorch_mnist_ddp_amd.utils.checkpoint import save_state_dict
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LO, HI, SENTINEL, EPS = R.LO, R.HI, -12345, 10.0 / MNIST_STD
+ULP = float(np.spacing(np.float32(max(abs(LO), abs(HI)))))
+STORES = 784 * 2.0 ** -24 * max(abs(LO), abs(HI))            # the rounding of a row's stores, in L1 mass
+RATIO_MARGIN, FOUND_MARGIN = max(2 * 0.0019, 0.05), max(2 * 2, 2)     # twice the first deviations, not below the floors
+NAMES = ("dx", "loss_rows", "x0", "x", "x_best", "g_best", "fstate", "istate")
+LAUNCHES = [dict(first=True), dict(), dict(window=2, restart=True), dict(window=2), dict(last=True, window=2),
+            dict(window=2, eps=0.0)]
+_bits = lambda t: t.contiguous().view(torch.int32)                                            # noqa: E731
+
+
+def _launch(case, dev, M, **kw):
+    """One ``apgd_l1_step`` on sentinel-filled buffers of M + 1 images: (outputs of the M images as numpy, intact)."""
+    t = {k: torch.full((M + 1,) + case[k].shape[1:], SENTINEL, dtype=case[k].dtype, device=dev) for k in NAMES}
+    for k in NAMES[:4] if kw.get("first") else NAMES:        # the first launch reads no state
+        t[k][:M] = case[k].to(dev)
+    before = [t[k].clone() for k in NAMES[:3]]
+    Fk.apgd_l1_step(*(t[k] for k in NAMES), case["sign"], case["eps"], LO, HI, M=M, **kw)
+    intact = all(bool((t[k][M] == SENTINEL).all()) for k in NAMES[3:]) and \
+        all(torch.equal(_bits(a), _bits(t[k])) for a, k in zip(before, NAMES))
+    return tuple(t[k][:M].cpu().numpy() for k in NAMES[3:]), intact
+
+
+@pytest.mark.parametrize("launch", LAUNCHES, ids=str)
+@pytest.mark.parametrize("sign", [1, -1])
+@pytest.mark.parametrize("M", [1, 3, 33])
+def test_apgd_l1_step_kernel_against_float64(cuda_device, M, sign, launch):
+    kw = dict(launch)
+    case = R.make_case(M, seed=100 * M + 10 * (sign > 0) + LAUNCHES.index(launch), sign=sign,
+                       restart=kw.pop("restart", False), eps=kw.pop("eps", EPS))
+    got, intact = _launch(case, cuda_device, M, **kw)
+    assert intact                                            # the guard image and the read-only operands
+    want = R.step_oracle(case, **kw)
+    ref = [o.numpy() for o in Fk.apgd_l1_step_reference(*(case[k] for k in NAMES), sign, case["eps"], LO, HI, **kw)]
+    assert all(np.array_equal(got[k].view(np.int32), want[k].view(np.int32)) for k in (1, 2, 4))   # x_best, g_best, istate
+    eta_best_thr = want[3][:, [0, 1, 3]].astype(np.float32)  # exact as well
+    assert np.array_equal(got[3][:, [0, 1, 3]].view(np.int32), eta_best_thr.view(np.int32))
+    x0 = case["x0"].numpy().astype(np.float64)
+    err = lambda o: (np.abs(o[0] - want[0]).max(), np.abs(o[3][:, 2] - want[3][:, 2]).max(),             # noqa: E731
+                     max((np.abs(o[0] - x0).sum(axis=1) - case["eps"]).max(), 0.0))
+    (gx, gl, gm), (rx, rl, rm) = err(got), err(ref)          # x, lam, L1 excess: the kernel's, the float32 reference's
+    assert gx <= max(4 * rx, ULP) and gl <= max(4 * rl, ULP) and gm <= STORES + 4 * rm, (gx, rx, gl, rl, gm, rm)
+    assert (got[0] >= LO).all() and (got[0] <= HI).all() and (case["eps"] > 0 or np.array_equal(got[0], x0))
+    again, _ = _launch(case, cuda_device, M, **kw)           # the same inputs, the same bits
+    assert all(np.array_equal(a.view(np.int32), b.view(np.int32)) for a, b in zip(got, again))
+
+
+def test_refusals_make_no_launch(cuda_device):
+    t = {k: R.make_case(4, seed=3)[k].to(cuda_device) for k in NAMES}
+    keep = {k: v.clone() for k, v in t.items()}
+    ok = dict({k: native.ptr(t[k]) for k in NAMES}, sign=1.0, eps=1.0, lo=LO, hi=HI, first=False, last=False,
+              window=0, M=4, stream=native.stream_handle())
+    for kw in (dict(M=0), dict(M=(1 << 20) + 1), dict(eps=-0.1), dict(eps=float("nan")), dict(sign=0.0),
+               dict(x=ok["x"] + 4), dict(fstate=ok["fstate"] + 4), dict(loss_rows=ok["loss_rows"] + 2), dict(x_best=0),
+               dict(window=-1), dict(first=True, last=True)):
+        with pytest.raises(RuntimeError):
+            native.load().apgd_l1_step(**dict(ok, **kw))
+    for bad in (dict(eps=-1.0), dict(sign=0), dict(first=True, last=True), dict(M=5), dict(window=-1),
+                dict(x_best=t["x"])):                        # the last: five buffers
+        with pytest.raises(ValueError):
+            Fk.apgd_l1_step(**dict(dict(t, sign=1, eps=1.0, lo=LO, hi=HI), **bad))
+    torch.cuda.synchronize()
+    assert all(torch.equal(_bits(t[k]), _bits(v)) for k, v in keep.items())     # nothing ran
+
+
+def _setup(dev, n=64):                                       # net, fused state, n normalised images, labels
+    net = copy.deepcopy(trained_net()).to(dev)
+    imgs, labels = generate(64, seed=5)
+    st = fused_state(net)
+    st.sync()
+    return net, st, normalize_u8(imgs).reshape(64, 784)[:n].to(dev).contiguous(), labels[:n].long().to(dev)
+
+
+@pytest.mark.parametrize("loss", ["ce", "cw"])
+def test_fused_loop_equals_its_launches_by_hand(cuda_device, loss):
+    (net, st, x0, y), steps = _setup(cuda_device, 8), 50     # 50 steps: windows of 2
+    params = [(q.detach().clone(), q.grad) for q in net.parameters()]
+    got = fused_auto_pgd_l1(net, x0, y, EPS, steps, LO, HI, loss=loss)
+    chain, lab, x = GradChain(st, 8, loss), y.to(torch.int32), x0.clone()
+    dx, x_best, g_best, fs = (torch.full((8, w), float(SENTINEL), device=cuda_device) for w in (784, 784, 784, 4))
+    ist = torch.full((8, 4), SENTINEL, dtype=torch.int32, device=cuda_device)
+    for j in range(steps + 1):
+        chain.run(native.ptr(x), native.ptr(lab), 8)
+        chain.input_grad(native.ptr(dx), 8)
+        Fk.apgd_l1_step(dx, chain._buf.loss_rows, x0, x, x_best, g_best, fs, ist, 1, EPS, LO, HI, first=j == 0,
+                        last=j == steps, window=dict(Fk.apgd_l1_checkpoints(steps)).get(j, 0), M=8)
+    chain.release()
+    assert torch.equal(_bits(got[0]), _bits(x_best)) and torch.equal(_bits(got[1]), _bits(fs[:, Fk.APGD_L1_LOSS_BEST]))
+    assert ist[:, Fk.APGD_L1_ITERS].tolist() == [steps] * 8
+    assert net.training is False                             # the mode, the parameters and their .grad are untouched
+    assert all(torch.equal(q, was) and q.grad is g for q, (was, g) in zip(net.parameters(), params))
+
+
+@pytest.mark.parametrize("cuts", [(16, 48), (1, 31, 32)])
+def test_fused_loop_under_chunkings(cuda_device, cuts):
+    net, _, x0, y = _setup(cuda_device)
+    whole = fused_auto_pgd_l1(net, x0, y, EPS, 8, LO, HI)
+    at = np.cumsum((0,) + cuts)
+    parts = [fused_auto_pgd_l1(net, x0[a:b], y[a:b], EPS, 8, LO, HI) for a, b in zip(at[:-1], at[1:])]
+    assert all(torch.equal(_bits(torch.cat([q[k] for q in parts])), _bits(whole[k])) for k in (0, 1))
+
+
+def test_predictor_auto_pgd_l1_against_the_cpu(cuda_device):
+    net, st, x0, y = _setup(cuda_device)
+    pr = Predictor(net)
+    assert pr.native
+    x_adv, lp, loss_best = pr.auto_pgd_l1(x0.view(64, 1, 28, 28), y, eps=10.0, steps=20)
+    xa = x_adv.reshape(64, 784).contiguous()
+    cpu_net, eps32 = trained_net(), float(np.float32(EPS))
+    x_ref, loss_ref = reference_auto_pgd_l1(cpu_net, x0.cpu(), y.cpu(), EPS, 20, LO, HI)
+    mass = lambda p, c: float((p.double() - c.double()).abs().sum(dim=1).max())               # noqa: E731
+    assert (xa >= LO).all() and (xa <= HI).all()             # the box, and the ball by the kernel test's bound
+    assert mass(xa, x0) <= eps32 + STORES + 4 * max(mass(x_ref, x0.cpu()) - eps32, 0.0)
+    chain, lab = GradChain(st, 64), y.to(torch.int32)        # the losses of the start and of the returned point
+    chain.run(native.ptr(x0), native.ptr(lab), 64)
+    start = chain._buf.loss_rows[:64].clone()
+    chain.run(native.ptr(xa), native.ptr(lab), 64)
+    again = chain._buf.loss_rows[:64].clone()
+    chain.release()
+    assert (loss_best >= start).all() and torch.equal(_bits(again), _bits(loss_best))
+    with torch.no_grad():                                    # against the CPU reference, never the kernel itself
+        found_ref = cpu_net.forward_reference(x_ref.view(64, 1, 28, 28)).argmax(1) != y.cpu()
+    ratio = float(loss_best.double().mean().cpu()) / float(loss_ref.double().mean())
+    flips = int(((lp.argmax(1) != y).cpu() != found_ref).sum())
+    assert abs(ratio - 1.0) <= RATIO_MARGIN and flips <= FOUND_MARGIN, (ratio, flips)
+
+
+def test_predict_cli_apgd_l1_on_gpu(cuda_device, tmp_path):
+    ckpt, log = str(tmp_path / "mnist_cnn.pt"), str(tmp_path / "log.jsonl")
+    save_state_dict(trained_net(), ckpt)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "mnist_predict.py"), "--synthetic", "--synthetic-test-size",
+                        "200", "--checkpoint", ckpt, "--json-log", log, "--apgd-l1-eps", "10", "--apgd-l1-steps", "10"],
+                       cwd=tmp_path, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    with open(log) as f:
+        rec = json.loads(f.read())
+    assert len(lines) == 2 and lines[1].startswith("Auto-PGD set (L1 eps=10, steps=10): Average loss: ")
+    assert f"Accuracy: {rec['apgd_l1_correct']}/200 " in lines[1] and "median pixels changed: " in lines[1]
+    assert rec["device"].startswith("cuda") and rec["apgd_l1_correct"] <= rec["correct"] and "apgd_eps" not in rec

@@ -19,6 +19,14 @@ and the min-max spread), in us per iteration:
 kind, back to back on the partials of one forward, us per launch.
 
     python tools/apgd_bench.py --loss ce,cw,dlr [--out profiles/apgd/apgd_bench_loss.txt]
+
+``--norm l1`` prints the L1 table instead: per batch the fused L1 loop (``fused_auto_pgd_l1``, L1 radius 10) beside an
+L2 Auto-PGD iteration in the same process, and ``apgd_l1_step`` alone back to back on a middle launch whose every image
+projects; the launch moves its iterate into the ball, so a device copy puts it back before each launch and is timed
+alone beside it.  Each batch size runs in a child process of its own under ``--step-timeout``; after a child that fails
+no other is started.
+
+    python tools/apgd_bench.py --norm l1 [--out profiles/apgd/apgd_bench_l1.txt]
 """
 import argparse
 import os
@@ -34,7 +42,7 @@ from pytorch_mnist_ddp_amd.data.datasets import MNIST_STD, load_mnist  # noqa: E
 from pytorch_mnist_ddp_amd.inference import _PIXEL_LUT, PIXEL_HI, PIXEL_LO, Predictor  # noqa: E402
 from pytorch_mnist_ddp_amd.models.net import Net  # noqa: E402
 from pytorch_mnist_ddp_amd.ops import functional as Fk  # noqa: E402
-from pytorch_mnist_ddp_amd.ops.apgd import fused_auto_pgd  # noqa: E402
+from pytorch_mnist_ddp_amd.ops.apgd import fused_auto_pgd, fused_auto_pgd_l1  # noqa: E402
 from pytorch_mnist_ddp_amd.ops.attack import fused_adversarial  # noqa: E402
 
 
@@ -111,11 +119,85 @@ def loss_table(a, net, dev, batches, images, targets):
     return lines
 
 
+def l1_row(a, B):
+    """One row of the ``--norm l1`` table: the fused L1 loop and an L2 Auto-PGD iteration in this process, and
+    ``apgd_l1_step`` alone back to back on a middle launch whose every image projects (dense random iterates of ten
+    times the radius's mass)."""
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(1)
+    net = Net().to(dev)
+    test = load_mnist(synthetic_data=True, train=False, synthetic_size=B, verbose=False)
+    x0 = _PIXEL_LUT.to(dev)[test.device_images(dev).reshape(-1, 784)[:B].long()].contiguous()
+    y = test.targets.long().to(dev)[:B]
+    rounds, eps = a.iters + 1, 10.0 / MNIST_STD
+    dx, g_best = torch.randn(B, 784, device=dev), torch.randn(B, 784, device=dev)
+    loss = torch.rand(B, device=dev) + 1.0
+    x_far = (x0 + torch.randn(B, 784, device=dev)).clamp(PIXEL_LO, PIXEL_HI)
+    x, x_best = x_far.clone(), x0.clone()
+    fs = torch.tensor([eps, 9.0, 0.0, 0.0], device=dev).repeat(B, 1).contiguous()
+    ist = torch.tensor([157, 784, 5, 0], dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+
+    def step():
+        x.copy_(x_far)                                       # (the launch moves x into the ball: put it back)
+        Fk.apgd_l1_step(dx, loss, x0, x, x_best, g_best, fs, ist, 1, eps, PIXEL_LO, PIXEL_HI)
+
+    arms = {"l1": lambda: fused_auto_pgd_l1(net, x0, y, eps, a.iters, PIXEL_LO, PIXEL_HI),
+            "l2": lambda: fused_auto_pgd(net, x0, y, 1.5 / MNIST_STD, a.iters, PIXEL_LO, PIXEL_HI, norm="l2"),
+            "copy": lambda: x.copy_(x_far), "step": step}
+    reps = {"l1": max(1, 64 // B), "l2": max(1, 64 // B), "copy": 200, "step": 200}
+    per = {"l1": rounds, "l2": rounds, "copy": 1, "step": 1}
+    for f in arms.values():
+        timed(f, 1)
+    res = {k: [] for k in arms}
+    for _ in range(a.rounds):
+        for k, f in arms.items():
+            res[k].append(timed(f, reps[k]) / per[k])
+    assert float(fs[:, Fk.APGD_L1_LAM].min()) > 0.0           # every image projected
+    return f"{B:>5} {fmt(res['l1']):>29} {fmt(res['l2']):>29} {fmt(res['step']):>29} {fmt(res['copy']):>29}"
+
+
+def l1_table(a):
+    """The ``--norm l1`` table: each batch size in a child process of its own under a time limit; after a child that
+    fails no other is started."""
+    import subprocess
+    lines = [f"apgd_bench --norm l1: {a.iters} updates ({a.iters + 1} rounds) a sample, {a.rounds} samples; us per "
+             f"iteration (loops) and per launch (step alone, with the copy that resets its iterate), median [min-max]",
+             f"{'B':>5} {'native L1':>29} {'native L2':>29} {'copy + apgd_l1_step':>29} {'copy alone':>29}"]
+    status = 0
+    for B in (int(v) for v in a.batches.split(",")):
+        cmd = [sys.executable, os.path.abspath(__file__), "--norm", "l1", "--one", str(B), "--iters", str(a.iters),
+               "--rounds", str(a.rounds)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
+        except subprocess.TimeoutExpired:
+            lines.append(f"{B:>5} timed out after {a.step_timeout:g} s; nothing more was started")
+            status = 3
+            break
+        if r.returncode != 0:
+            lines.append(f"{B:>5} failed with status {r.returncode}; nothing more was started")
+            sys.stderr.write(r.stderr[-2000:])
+            status = 3
+            break
+        lines.append(r.stdout.rstrip("\n").splitlines()[-1])
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    return status
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batches", type=str, default="1,64,200,1000")
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--norm", choices=("l1",), default=None,
+                    help="l1: the L1 table instead - the fused L1 loop beside an L2 Auto-PGD iteration and "
+                         "apgd_l1_step alone, each batch size in a child process under --step-timeout")
+    ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds a batch size of --norm l1 may take")
+    ap.add_argument("--one", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--loss", default=None, metavar="L1,L2,...",
                     help="the loss table instead: the native L-inf loop under each of these losses (ce, cw, dlr) and "
                          "head_margin alone against head_train")
@@ -124,6 +206,11 @@ def main() -> int:
     if not torch.cuda.is_available():
         print("apgd_bench: no GPU", file=sys.stderr)
         return 2
+    if a.norm == "l1":
+        if a.one is not None:
+            print(l1_row(a, a.one))
+            return 0
+        return l1_table(a)
     dev = torch.device("cuda", 0)
     torch.manual_seed(1)
     net = Net().to(dev)
