@@ -57,6 +57,10 @@
 //            +a / -b are read off the registers - nothing is gathered from LDS and no LDS index is ever derived
 //            from a key.  S is a backward scan in a fixed order: eight serial per thread, Hillis-Steele over
 //            shfl_down across the wave, the four wave totals through LDS added in wave order; N the same in integers.
+//            S, phi and the quotient are float64 (a few dozen operations a thread): S_k cancels +a against -b of the
+//            pixels far past the box and then eps against S_k, and a float32 S_k, a few ulps of 30 .. 100 off, left
+//            lam off by up to 1.2e-6 on the iterates of a real attack, 16 times what four times the float32
+//            reference's own error allows (its cumulative sum on the CPU is a float64 one).  lam is rounded once.
 //   pick     each thread's first slot that crosses as (position << 32 | bits of its lam): the minimum over the wave
 //            by cross-lane moves, over the four waves through LDS.  Positions are distinct: one lam wins.
 // sp, m and N are integer counts, exact in any order.  No atomics; every float operation is rounded on its own
@@ -67,13 +71,16 @@
 // stands between.  Row elements are read and written by their owner only and read before they are written.  The
 // grid is exactly M workgroups: nothing past M is touched.
 //
-// NaN: a NaN loss never becomes the best.  A NaN gradient element is selected (its key is above every number), makes
-// t, a, sum w and every S_k that covers it NaN, no position crosses, lam = NaN and the image's whole x is NaN -
-// that image's only.
+// NaN: a NaN loss never becomes the best (L > loss_best is false; the first launch stores the loss it is given).  A
+// NaN gradient element is selected (its key is above every number), makes t, a, sum w and every S_k that covers it
+// NaN, no position crosses, lam = NaN and the image's whole x is NaN - that image's only.  Under eps == 0 no sum is
+// taken: lam = 0, x = x0, and the NaN shows in the element it entered by (d = s * 0 with s = NaN) and in no other.
+// A record from elsewhere (k_sel outside [1, 784] on a launch that is no checkpoint) selects with the clamped slot and
+// is stored as it came; no memory index is derived from it.
 //
 // RESOURCES (the build's flags: hipcc -O3 --offload-arch=gfx950 -munsafe-fp-atomics -fno-slp-vectorize
 // -Xclang -target-feature -Xclang -packed-fp32-ops, with -Rpass-analysis=kernel-resource-usage):
-//   apgd_l1_step_kernel: VGPRs 71, SGPRs 106 (28 kept in VGPR lanes), LDS 32888 B, scratch 0, occupancy 4 waves /
+//   apgd_l1_step_kernel: VGPRs 79, SGPRs 106 (28 kept in VGPR lanes), LDS 32904 B, scratch 0, occupancy 4 waves /
 //   SIMD (LDS bound: four workgroups a CU).  The two 16 KB sort buffers are the whole of the LDS: the sorted terms
 //   come out of the keys, so there is no 8 KB value array to gather from.
 // x_best and g_best are re-read by address, every index into a register array is a counter of an unrolled loop.
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(ROW_THREADS) void apgd_l1_step_kernel(ApgdL1StepArg
   __shared__ uint64_t ex[2 * L1_PRJ_SLOTS];                // the sorts' LDS stages (the select uses a quarter)
   __shared__ int cnt[2][ROW_WAVES];                        // sp, m
   __shared__ float part[ROW_WAVES];                        // sum w
-  __shared__ float scan_s[ROW_WAVES];                      // wave totals of S
+  __shared__ double scan_s[ROW_WAVES];                     // wave totals of S
   __shared__ int scan_n[ROW_WAVES];                        // ... of N
   __shared__ uint64_t hit[ROW_WAVES];                      // the waves' first crossing slot
   __shared__ int thr_w;
@@ -296,10 +303,11 @@ __global__ __launch_bounds__(ROW_THREADS) void apgd_l1_step_kernel(ApgdL1StepArg
       q[L1_SEL_PER + s] = ((uint64_t)tb << 32) | (uint32_t)(L1_SEL_SLOTS + L1_SEL_PER * tid + s);
     }
     l1_sort<uint64_t, L1_PRJ_PER>(q, ex, tid);
-    float tau[L1_PRJ_PER], Sk[L1_PRJ_PER];
+    float tau[L1_PRJ_PER];
+    double Sk[L1_PRJ_PER];                                 // S in float64: a sum of floats, exact to its last bits
     int Nk[L1_PRJ_PER];
     bool real[L1_PRJ_PER];
-    float us = 0.0f;
+    double us = 0.0;
     int un = 0;
 #pragma unroll
     for (int s = L1_PRJ_PER - 1; s >= 0; --s) {            // the thread's own eight, backwards
@@ -307,7 +315,7 @@ __global__ __launch_bounds__(ROW_THREADS) void apgd_l1_step_kernel(ApgdL1StepArg
       const bool isb = (id & L1_SEL_SLOTS) != 0;
       real[s] = (id & (L1_SEL_SLOTS - 1)) < L1_N;
       tau[s] = __uint_as_float((uint32_t)(q[s] >> 32));
-      const float v = real[s] ? (isb ? -tau[s] : tau[s]) : 0.0f;
+      const double v = real[s] ? (double)(isb ? -tau[s] : tau[s]) : 0.0;
       const int n1 = real[s] ? (isb ? -1 : 1) : 0;
       us = s == L1_PRJ_PER - 1 ? v : us + v;
       un = un + n1;
@@ -316,33 +324,33 @@ __global__ __launch_bounds__(ROW_THREADS) void apgd_l1_step_kernel(ApgdL1StepArg
     }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {                     // the suffix over the wave
-      const float ts = __shfl_down(us, o, 64);
+      const double ts = __shfl_down(us, o, 64);
       const int tn = __shfl_down(un, o, 64);
       if (lane + o < 64) { us = us + ts; un = un + tn; }
     }
-    const float es = __shfl_down(us, 1, 64);
+    const double es = __shfl_down(us, 1, 64);
     const int en = __shfl_down(un, 1, 64);
-    const float sex = lane == 63 ? 0.0f : es;
+    const double sex = lane == 63 ? 0.0 : es;
     const int nex = lane == 63 ? 0 : en;
     if (lane == 0) { scan_s[wave] = us; scan_n[wave] = un; }
     lds_barrier();
-    const float s32 = scan_s[3] + scan_s[2];
+    const double s32 = scan_s[3] + scan_s[2];
     const int n32 = scan_n[3] + scan_n[2];
-    const float soff = wave == 3 ? 0.0f : wave == 2 ? scan_s[3] : wave == 1 ? s32 : s32 + scan_s[1];
+    const double soff = wave == 3 ? 0.0 : wave == 2 ? scan_s[3] : wave == 1 ? s32 : s32 + scan_s[1];
     const int noff = wave == 3 ? 0 : wave == 2 ? scan_n[3] : wave == 1 ? n32 : n32 + scan_n[1];
-    const float sb = soff + sex;
+    const double sb = soff + sex;
     const int nb = noff + nex;
     uint64_t cand = ((uint64_t)L1_PRJ_SLOTS << 32) | L1_NAN_BITS;    // no crossing (a NaN in the row): lam = NaN
 #pragma unroll
     for (int s = L1_PRJ_PER - 1; s >= 0; --s) {            // descending: the first slot wins
-      const float S = sb + Sk[s];
+      const double S = sb + Sk[s];
       const int N = nb + Nk[s];
-      const float nf = (float)N;
-      const float tn = tau[s] * nf;
-      const float phi = S - tn;
-      if (real[s] && N > 0 && phi <= a.eps) {
-        const float num = S - a.eps;
-        cand = ((uint64_t)(uint32_t)(L1_PRJ_PER * tid + s) << 32) | __float_as_uint(num / nf);
+      const double nf = (double)N;
+      const double tn = (double)tau[s] * nf;
+      const double phi = S - tn;
+      if (real[s] && N > 0 && phi <= (double)a.eps) {
+        const double num = S - (double)a.eps;              // lam is rounded to float32 once, here
+        cand = ((uint64_t)(uint32_t)(L1_PRJ_PER * tid + s) << 32) | __float_as_uint((float)(num / nf));
       }
     }
 #pragma unroll

@@ -1215,7 +1215,8 @@ def l1_box_projection_reference(z: torch.Tensor, x0: torch.Tensor, eps: float, l
 
     With b = max(a - cap, 0) the sum is sum_{a > lam} (a - lam) - sum_{b > lam} (b - lam); on the 2 n breakpoints
     sorted ascending (a stable sort, the a before the b), S_k / N_k the sums over the positions >= k of +a, -b /
-    of +-1: k = the first position with N_k > 0 and S_k - tau_k N_k <= eps, lam = (S_k - eps) / N_k (a row with no
+    of +-1 (S in float64): k = the first position with N_k > 0 and S_k - tau_k N_k <= eps, lam = (S_k - eps) / N_k
+    in float64, rounded to the dtype once (a row with no
     such position - a NaN in it - gets lam = NaN and a NaN delta)."""
     M, n = z.shape
     dt, dev = z.dtype, z.device
@@ -1230,11 +1231,14 @@ def l1_box_projection_reference(z: torch.Tensor, x0: torch.Tensor, eps: float, l
     tau, order = torch.sort(torch.cat((a, b), dim=1), dim=1, stable=True)
     unit = torch.cat((torch.ones(M, n, dtype=dt, device=dev), -torch.ones(M, n, dtype=dt, device=dev)), dim=1)
     unit = unit.gather(1, order)
-    S = (tau * unit).flip(1).cumsum(dim=1).flip(1)
-    N = unit.flip(1).cumsum(dim=1).flip(1)
-    ok = (N > 0) & (S - tau * N <= eps)
+    # S, phi and the quotient in float64 in every dtype and on every device, as the kernel has them (a float32 cumsum
+    # on the CPU accumulates in float64 anyway): S_k cancels +a against -b and then eps; lam is rounded once
+    tau64, unit64 = tau.double(), unit.double()
+    S = (tau64 * unit64).flip(1).cumsum(dim=1).flip(1)
+    N = unit64.flip(1).cumsum(dim=1).flip(1)
+    ok = (N > 0) & (S - tau64 * N <= eps)
     k = ok.to(torch.int8).argmax(dim=1, keepdim=True)
-    lam = ((S.gather(1, k) - eps) / N.gather(1, k))[:, 0]
+    lam = ((S.gather(1, k) - eps) / N.gather(1, k))[:, 0].to(dt)
     lam = torch.where(ok.any(dim=1), lam, torch.full_like(lam, float("nan")))
     t = a - lam[:, None]
     t = torch.where(t < 0, torch.zeros_like(t), t)
