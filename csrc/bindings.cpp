@@ -48,6 +48,7 @@ void mnist::preload_all_kernels() {
   preload_square_l2();
   preload_fab();
   preload_apgd_l1();
+  preload_cw();
 }
 
 namespace {
@@ -612,6 +613,30 @@ PYBIND11_MODULE(_C, m) {
      "one L1 Auto-PGD iteration per image: best point, checkpoint (sparsity rule: restart or shrink eta), sparse "
      "top-k step, exact projection onto the L1 ball and the box; fstate [M][4] = eta, loss_best, lam, thr; istate "
      "[M][4] = k_sel, sp_old, iters, restarted");
+
+  // ---------------- Carlini-Wagner L2 attack ----------------
+  m.attr("CW_SHRINK") = CW_SHRINK;
+  m.attr("CW_C_INF") = CW_C_INF;
+  m.attr("CW_C_BIG") = CW_C_BIG;
+  m.def("cw_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t x0, uintptr_t w, uintptr_t m1, uintptr_t v,
+                      uintptr_t x, uintptr_t x_best, uintptr_t fstate, uintptr_t istate, float sign, float kappa,
+                      float lr, float c_init, float beta1, float beta2, float adam_eps, float bc1, float bc2,
+                      float dist_scale, float lo, float hi, int search, bool first, bool search_end, bool last, int M,
+                      uintptr_t stream) {
+    CwStepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const float>(x0), P<float>(w), P<float>(m1),
+                 P<float>(v), P<float>(x), P<float>(x_best), P<float>(fstate), P<int32_t>(istate), sign, kappa, lr,
+                 c_init, beta1, beta2, adam_eps, bc1, bc2, dist_scale, lo, hi, search, first ? 1 : 0,
+                 search_end ? 1 : 0, last ? 1 : 0};
+    launch_cw_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("x0"), py::arg("w"), py::arg("m1"), py::arg("v"), py::arg("x"),
+     py::arg("x_best"), py::arg("fstate"), py::arg("istate"), py::arg("sign"), py::arg("kappa"), py::arg("lr"),
+     py::arg("c_init"), py::arg("beta1"), py::arg("beta2"), py::arg("adam_eps"), py::arg("bc1"), py::arg("bc2"),
+     py::arg("dist_scale"), py::arg("lo"), py::arg("hi"), py::arg("search"), py::arg("first"), py::arg("search_end"),
+     py::arg("last"), py::arg("M"), py::arg("stream"),
+     "one Carlini-Wagner L2 iteration per image: success test and nearest success, Adam step in tanh space (or, "
+     "search_end, the bisection of c and the restart from the clean image); fstate [M][4] = c, c_lo, c_hi, d_best; "
+     "istate [M][4] = succ, found_search, iters, spare");
 
   // ---------------- Square Attack ----------------
   m.attr("SQUARE_PHILOX_DOMAIN") = SQUARE_PHILOX_DOMAIN;

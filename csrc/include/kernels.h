@@ -539,6 +539,45 @@ struct ApgdL1StepArgs {
 // M in [1, INPUT_GRAD_MAX_B], eps >= 0, sign +-1, window >= 0, not first and last at once
 void launch_apgd_l1_step(const ApgdL1StepArgs& a, int M, hipStream_t s);
 
+// ---------------- Carlini-Wagner L2 attack (cw.hip; Carlini & Wagner 2017) ----------------
+// One iteration's per-image update in one launch, one workgroup per image, fp32, no atomics: dx / loss_rows are the
+// gradient chain's outputs with the CW margin (GradChain loss "cw": loss_rows = max_{j != y} z_j - z_y) at the
+// iterate rows x.  With L = sign * loss_rows[i] and D = sum (x - x0)^2: the iterate is a success when L > 0 and
+// L >= kappa, and the nearest success so far is kept (d_best, x_best, found_search = search + 1); then an Adam step
+// on the tanh-space variable w of |x - x0|^2 dist_scale + c * max(kappa - L, 0), x = lo + (hi - lo)(tanh(w) + 1) / 2;
+// a `search_end` launch instead bisects c on whether the search step had a success and puts w, m1, v, x back to the
+// clean image.  The exact form and the NaN rules are in cw.hip.
+// PER-IMAGE SCALARS, two 16-byte records an image (both arrays 16-byte aligned):
+//   fstate[i] = {c, c_lo, c_hi, d_best}                (fp32; d_best in normalised units squared, +inf: none yet)
+//   istate[i] = {succ, found_search, iters, spare}     (int32; succ: a success inside the current search step;
+//                                                       found_search: 1 + the search step of the best point, 0: none)
+// first: reads no record and no w / m1 / v / x_best, writes all of them; the caller has set x = x0.  last: only the
+// best point and the records are brought up to date.  Rows and records past M are untouched.
+constexpr float CW_SHRINK = 0.999999f;                   // pulls the clean image's tanh-space point inside (-1, 1)
+constexpr float CW_C_INF = 1e10f, CW_C_BIG = 1e9f;       // c_hi before any success; "c_hi is still unset" is c_hi >= BIG
+struct CwStepArgs {
+  const float* dx;            // fp32 [M][784] d margin / d x at the iterate
+  const float* loss_rows;     // [M] the CW margin at the iterate
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* w;                   // fp32 [M][784] the tanh-space variable
+  float* m1;                  // fp32 [M][784] Adam's first moment
+  float* v;                   // fp32 [M][784] Adam's second moment
+  float* x;                   // fp32 [M][784] the iterate (the xin of the next chain run)
+  float* x_best;              // fp32 [M][784] the nearest success so far (the clean image until there is one)
+  float* fstate;              // [M][4]
+  int32_t* istate;            // [M][4]
+  float sign;                 // +1 untargeted (leave labels), -1 targeted (reach labels)
+  float kappa, lr, c_init;    // confidence >= 0, Adam's step > 0, the first c > 0 (read by a first launch)
+  float beta1, beta2, adam_eps;
+  float bc1, bc2;             // 1 - beta1^t, 1 - beta2^t of this launch's Adam step index t
+  float dist_scale;           // the weight of |x - x0|^2 (MNIST_STD^2: pixel units)
+  float lo, hi;               // valid range, normalised units
+  int search;                 // the index of the current search step
+  int first, search_end, last;   // flags: launch 0 / the launch after a search step's last update / the very last
+};
+// M in [1, INPUT_GRAD_MAX_B], sign +-1, kappa >= 0, lr > 0, c_init > 0 when first, not first and last at once
+void launch_cw_step(const CwStepArgs& a, int M, hipStream_t s);
+
 // ---------------- Square Attack (square.hip; Andriushchenko, Croce, Flammarion, Hein 2020), L-inf ----------------
 // A score-based black-box attack: one query is one eval forward of the candidate x_cand, then square_step reads the
 // candidate's margin from head_eval's logp row (untargeted lp[y] - max_{j != y} lp[j]; targeted the negative; < 0:
@@ -697,7 +736,8 @@ void preload_square();
 void preload_square_l2();
 void preload_fab();
 void preload_apgd_l1();
-void preload_all_kernels();   // every one of the above, in this order (bindings.cpp: the one list)
+void preload_cw();
+void preload_all_kernels();  // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels
 struct F32Step {

@@ -62,9 +62,9 @@ from .data.datasets import MNIST_MEAN, MNIST_STD, PIXEL_HI, PIXEL_LO, load_mnist
 from .data.datasets import PIXEL_LUT as _PIXEL_LUT
 from .models.net import Net
 from .ops.chain import chain_loss
-from .ops.functional import (APGD_L1_LOSS_BEST, APGD_LOSS_BEST, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE,
+from .ops.functional import (APGD_L1_LOSS_BEST, APGD_LOSS_BEST, CW_C, CW_D_BEST, CW_FOUND_SEARCH, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE,
                              SQUARE_QUERIES, apgd_checkpoints, apgd_l1_checkpoints, apgd_l1_step_reference,
-                             apgd_step_reference, attr_path_reference, attr_reduce_reference,
+                             apgd_step_reference, attr_path_reference, attr_reduce_reference, cw_step_reference,
                              deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_l2_init_reference,
                              square_l2_step_reference, square_norm, square_sides, square_sides_l2, square_state_margin,
                              square_step_reference)
@@ -308,6 +308,43 @@ def reference_fab(net: Net, x0: torch.Tensor, labels: torch.Tensor, norm: str, s
             x_best[i0:i0 + m] = torch.where(torch.isinf(state[2])[:, None], c0, state[1])
             norm_best[i0:i0 + m], status[i0:i0 + m], iters[i0:i0 + m] = state[2:]
     return x_best, norm_best, iters, status
+
+
+def reference_carlini_wagner(net: Net, x0: torch.Tensor, labels: torch.Tensor, search_steps: int, steps: int, lr: float,
+                             c_init: float, kappa: float, sign: float, lo: float, hi: float):
+    """``ops.cw.fused_carlini_wagner`` in torch float32 on any device: the same ``search_steps * (steps + 1)`` rounds -
+    the CW margin of ``labels`` per row (``margin_loss_reference`` on the log-probs) and its gradient by autograd over
+    ``Net.forward_reference`` in eval mode (no dropout; the net's mode is restored afterwards), then
+    ``cw_step_reference`` with the same ``first`` / ``search_end`` / ``last`` flags.  ``x0``: float32 [B, 784]
+    normalised images; same return: ``(x_adv [B, 784], d_best [B], found_search int32 [B], c [B])``.  The images run
+    in chunks of ``_REF_ROWS``.  The CPU / fp32 path of ``Predictor.carlini_wagner`` and the reference of its GPU
+    tests."""
+    search_steps, steps = int(search_steps), int(steps)
+    if search_steps < 1 or steps < 1:
+        raise ValueError("reference_carlini_wagner: search_steps and steps must be at least 1")
+    B, dev = x0.shape[0], x0.device
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(dev)
+    outs = []
+    with _eval_mode(net):
+        for i0 in range(0, B, _REF_ROWS):
+            c0, yc = x0[i0:i0 + _REF_ROWS], y[i0:i0 + _REF_ROWS]
+            m = c0.shape[0]
+            state = (None, None, None, c0.clone(), None, None, None)    # w, m1, v, x, x_best, fstate, istate
+            for k in range(search_steps):
+                final = k == search_steps - 1
+                for j in range(steps + 1):
+                    xg = state[3].clone().requires_grad_()
+                    with torch.enable_grad():
+                        lp = net.forward_reference(xg.view(m, 1, 28, 28))
+                        g, = torch.autograd.grad(margin_loss_reference(lp, yc, "cw").sum(), xg)
+                    margin = margin_loss_reference(lp.detach(), yc, "cw")
+                    end = j == steps
+                    state = cw_step_reference(g, margin, c0, *state, sign, kappa, lr, c_init, min(j + 1, steps), k, lo,
+                                              hi, first=k == 0 and j == 0, search_end=end and not final,
+                                              last=end and final)
+            outs.append((state[4], state[5][:, CW_D_BEST], state[6][:, CW_FOUND_SEARCH], state[5][:, CW_C]))
+    return tuple(torch.cat(q) for q in zip(*outs))
 
 
 def _smooth_generator_seed(seed: int, image_id: int) -> int:
@@ -976,6 +1013,54 @@ class Predictor:
         lp = self._forward(x_adv)[0]
         return x_adv, dist * MNIST_STD, lp, lp.argmax(dim=1) != labels
 
+    def carlini_wagner(self, x: torch.Tensor, labels: torch.Tensor | None = None, search_steps: int = 6,
+                       steps: int = 100, lr: float = 0.05, c_init: float = 1.0, kappa: float = 0.0,
+                       targeted: bool = False):
+        """(x_adv, radii, log_probs, found): minimum-norm adversarial examples of ``x`` by Carlini & Wagner's L2 attack
+        (S&P 2017), in ``fab``'s conventions.  ``x_adv``: float32 [B,1,28,28] in NORMALISED units, inside the valid
+        pixel range; ``radii``: float32 [B], the L2 norm of ``x_adv - x`` in pixel units on the [0, 1] scale, +inf
+        where no iterate was a success (there ``x_adv`` is the clean image); ``log_probs``: the predictor's own
+        float32 [B,10] forward of ``x_adv``; ``found``: bool [B], whether that forward no longer gives ``labels``
+        (``targeted``: gives them).  An image already misclassified on entry keeps ``x_adv = x``, radius 0 and is found.
+
+        ``labels`` ([B] integers): the class each image is to leave, or the class predicted on the clean input when
+        None; ``targeted`` (``labels`` required): the class each image is to reach.  The attack minimises
+        |x_adv - x|^2 (pixel units) + c * max(``kappa`` - margin, 0) with Adam (step ``lr``) over w, x_adv = (tanh(w)
+        + 1) / 2 on the pixel scale, margin = max_{j != y} z_j - z_y on the logits (``targeted``: its negative);
+        ``search_steps`` times ``steps`` updates from the clean image, c starting at ``c_init``, then bisected per
+        image: lowered after a search step with a success (margin > 0 and >= ``kappa``), raised (tenfold until there
+        was one) otherwise.  The nearest success of all iterates is returned.  Differences from Carlini's code: no
+        ``abort_early``, success is read from the margin the attack's own forward computed.  Inference semantics as
+        ``input_gradient``.  GPU with ``dtype="bf16"``: the native loop ``ops.cw.fused_carlini_wagner``; CPU, or
+        ``dtype="fp32"``: ``reference_carlini_wagner``."""
+        B = self._check_input(x)
+        for name, val in (("search_steps", search_steps), ("steps", steps)):
+            if isinstance(val, bool) or val != int(val) or val < 1:
+                raise ValueError(f"carlini_wagner: {name} must be a positive integer, got {val}")
+        if not lr > 0:
+            raise ValueError(f"carlini_wagner: lr must be > 0, got {lr}")
+        if not c_init > 0:
+            raise ValueError(f"carlini_wagner: c_init must be > 0, got {c_init}")
+        if not kappa >= 0:
+            raise ValueError(f"carlini_wagner: kappa must be >= 0, got {kappa}")
+        if targeted and labels is None:
+            raise ValueError("carlini_wagner: a targeted attack needs labels (the target classes)")
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels("carlini_wagner", labels, B, check_range=True)
+        if self.native:
+            from .ops.cw import fused_carlini_wagner as attack
+        else:
+            attack = reference_carlini_wagner
+        x_adv, d_best, _, _ = attack(self.net, x0, labels, int(search_steps), int(steps), float(lr), float(c_init),
+                                     float(kappa), -1 if targeted else 1, PIXEL_LO, PIXEL_HI)
+        x_adv = x_adv.view(B, 1, 28, 28)
+        lp = self._forward(x_adv)[0]
+        hit = lp.argmax(dim=1) == labels
+        return x_adv, d_best.sqrt() * MNIST_STD, lp, hit if targeted else ~hit
+
     # ------------------------------------------------------------------ randomized smoothing
     def smoothed_counts(self, x: torch.Tensor, sigma: float, n: int, seed: int = 0, ids=None,
                         sample_base: int = 0) -> torch.Tensor:
@@ -1283,6 +1368,21 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack the first M images of the split (default: all)')
     ap.add_argument('--fab-radii', type=_radii, default=(), metavar='R1,R2,...',
                     help='radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
+    ap.add_argument('--cw', action='store_true', default=False,
+                    help='also report the minimum-norm adversarial radius of the images against their true labels by '
+                         "Carlini & Wagner's L2 attack (untargeted): how many are found, the median and mean radius "
+                         'in pixel units (default: off)')
+    ap.add_argument('--cw-search-steps', type=int, default=6, metavar='S',
+                    help='bisection steps of the trade-off constant c per image (default: 6)')
+    ap.add_argument('--cw-steps', type=int, default=100, metavar='N', help='Adam updates per search step (default: 100)')
+    ap.add_argument('--cw-lr', type=float, default=0.05, metavar='LR', help="Adam's step size (default: 0.05)")
+    ap.add_argument('--cw-c', type=float, default=1.0, metavar='C', help='the first trade-off constant (default: 1)')
+    ap.add_argument('--cw-kappa', type=float, default=0.0, metavar='K',
+                    help='confidence: the margin a success must reach (default: 0)')
+    ap.add_argument('--cw-count', type=int, default=None, metavar='M',
+                    help='attack the first M images of the split (default: all)')
+    ap.add_argument('--cw-radii', type=_radii, default=(), metavar='R1,R2,...',
+                    help='L2 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
     return ap
 
 
@@ -1368,6 +1468,18 @@ def fab_line(norm: str, steps: int, m: int, found: int, median, mean) -> str:
     fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
     return (f"FAB set ({'L2' if norm == 'l2' else 'Linf'}, steps={steps}): "
             f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
+
+
+def cw_line(search_steps: int, steps: int, m: int, found: int, median, mean) -> str:
+    """The ``CW set`` line of ``mnist_predict.py --cw``, in the number formats of ``minimum_norm_line``."""
+    fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
+    return (f"CW set (L2, search={search_steps}, steps={steps}): "
+            f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
+
+
+def accuracy_at_radius_line(r: float, c: int, m: int) -> str:
+    """The ``Accuracy at radius`` line the minimum-norm reports (``--min-norm``, ``--fab``, ``--cw``) share."""
+    return f"Accuracy at radius {r:g}: {c}/{m} ({100.0 * c / m:.0f}%)"
 
 
 def completeness_gap(predictor: "Predictor", attr: torch.Tensor, lp: torch.Tensor, labels: torch.Tensor,
@@ -1459,7 +1571,7 @@ def predict_main(argv=None) -> int:
         stats = minimum_norm_stats(radii, found, clean, args.min_norm_radii)
         print(minimum_norm_line(args.min_norm_steps, args.min_norm_overshoot, m, *stats[:3]))
         for r, c in zip(args.min_norm_radii, stats[3]):
-            print(f"Accuracy at radius {r:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
+            print(accuracy_at_radius_line(r, c, m))
         record.update(min_norm_steps=args.min_norm_steps, min_norm_overshoot=args.min_norm_overshoot,
                       min_norm_count=m, min_norm_found=stats[0], min_norm_median_radius=stats[1],
                       min_norm_mean_radius=stats[2],
@@ -1478,10 +1590,30 @@ def predict_main(argv=None) -> int:
         stats = minimum_norm_stats(radii, found, clean, args.fab_radii)
         print(fab_line(args.fab_norm, args.fab_steps, m, *stats[:3]))
         for r, c in zip(args.fab_radii, stats[3]):
-            print(f"Accuracy at radius {r:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
+            print(accuracy_at_radius_line(r, c, m))
         record.update(fab_norm=args.fab_norm, fab_steps=args.fab_steps, fab_count=m, fab_found=stats[0],
                       fab_median_radius=stats[1], fab_mean_radius=stats[2],
                       fab_accuracy_at={f"{r:g}": c for r, c in zip(args.fab_radii, stats[3])})
+    if args.cw:
+        m = n if args.cw_count is None else max(1, min(n, args.cw_count))
+        found = torch.empty(m, dtype=torch.bool)
+        clean = torch.empty(m, dtype=torch.bool)
+        radii = torch.empty(m, dtype=torch.float32)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            yb = data.targets[i:j]
+            clean[i:j] = (predictor.predict(images[i:j]).cpu() == yb.long().cpu())
+            _, r, _, fnd = predictor.carlini_wagner(images[i:j], yb, args.cw_search_steps, args.cw_steps, args.cw_lr,
+                                                    args.cw_c, args.cw_kappa)
+            radii[i:j], found[i:j] = r.cpu(), fnd.cpu()
+        stats = minimum_norm_stats(radii, found, clean, args.cw_radii)
+        print(cw_line(args.cw_search_steps, args.cw_steps, m, *stats[:3]))
+        for r, c in zip(args.cw_radii, stats[3]):
+            print(accuracy_at_radius_line(r, c, m))
+        record.update(cw_search_steps=args.cw_search_steps, cw_steps=args.cw_steps, cw_lr=args.cw_lr, cw_c=args.cw_c,
+                      cw_kappa=args.cw_kappa, cw_count=m, cw_found=stats[0], cw_median_radius=stats[1],
+                      cw_mean_radius=stats[2],
+                      cw_accuracy_at={f"{r:g}": c for r, c in zip(args.cw_radii, stats[3])})
     if args.apgd_eps is not None:
         gen = torch.Generator().manual_seed(args.apgd_seed) if args.apgd_restarts > 1 else None
         ap_loss, ap_correct, _ = predictor.robust_evaluate_apgd(images, data.targets, args.apgd_eps, args.apgd_steps,

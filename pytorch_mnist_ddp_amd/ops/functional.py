@@ -1364,8 +1364,178 @@ def apgd_l1_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, x:
                       float(eps), float(lo), float(hi), bool(first), bool(last), int(window), M, _s())
 
 
+CW_SHRINK = 0.999999                # pulls the clean image's tanh-space point inside (-1, 1) (kernels.h CW_SHRINK)
+CW_C_INF, CW_C_BIG = 1e10, 1e9      # c_hi before any success; "c_hi is still unset" is c_hi >= CW_C_BIG (kernels.h)
+CW_BETA1, CW_BETA2, CW_ADAM_EPS = 0.9, 0.999, 1e-8       # Adam's constants, as in Carlini's code (tf.train.AdamOptimizer)
+CW_MAX_M = 1 << 20                  # most images one cw_step launch takes (kernels.h INPUT_GRAD_MAX_B)
+# columns of the per-image records (kernels.h CwStepArgs)
+CW_C, CW_C_LO, CW_C_HI, CW_D_BEST = 0, 1, 2, 3            # fstate, float32 [M, 4]
+CW_SUCC, CW_FOUND_SEARCH, CW_ITERS, CW_SPARE = 0, 1, 2, 3    # istate, int32 [M, 4]
+
+
+def cw_dist_scale() -> float:
+    """MNIST_STD^2: with it the distance term of the CW objective is the squared L2 distance in pixel units."""
+    from ..data.datasets import MNIST_STD
+    return MNIST_STD * MNIST_STD
+
+
+def cw_bias_corrections(t: int, beta1: float = CW_BETA1, beta2: float = CW_BETA2) -> tuple:
+    """``(1 - beta1^t, 1 - beta2^t)`` of Adam's step ``t`` >= 1: computed in float64, rounded to float32 once."""
+    import numpy as np
+    if int(t) < 1:
+        raise ValueError("cw_bias_corrections: t must be at least 1")
+    return float(np.float32(1.0 - float(beta1) ** int(t))), float(np.float32(1.0 - float(beta2) ** int(t)))
+
+
+def cw_w0(x0: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    """atanh((((x0 - lo) / (hi - lo)) * 2 - 1) * CW_SHRINK) in float32: the tanh-space point of the clean image."""
+    import numpy as np
+    lo32 = np.float32(lo)
+    # (a tensor divisor: a true division on every device, never a multiplication by the reciprocal)
+    span = torch.tensor(float(np.float32(hi) - lo32), dtype=torch.float32, device=x0.device)
+    return torch.atanh((((x0.to(torch.float32) - float(lo32)) / span) * 2.0 - 1.0) * float(np.float32(CW_SHRINK)))
+
+
+def cw_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, w: torch.Tensor | None,
+                      m1: torch.Tensor | None, v: torch.Tensor | None, x: torch.Tensor, x_best: torch.Tensor | None,
+                      fstate: torch.Tensor | None, istate: torch.Tensor | None, sign: float, kappa: float, lr: float,
+                      c_init: float, t: int, search: int, lo: float, hi: float, beta1: float = CW_BETA1,
+                      beta2: float = CW_BETA2, adam_eps: float = CW_ADAM_EPS, dist_scale: float | None = None,
+                      first: bool = False, search_end: bool = False, last: bool = False):
+    """``cw_step`` operation by operation in torch float32 on any device (the CPU / fp32 path of
+    ``Predictor.carlini_wagner``, and what the kernel's tests hold it against).  Same operands - ``dx``, ``x0``, ``w``,
+    ``m1``, ``v``, ``x``, ``x_best`` [M, 784], ``loss_rows`` [M], ``fstate`` [M, 4] (c, c_lo, c_hi, d_best), ``istate``
+    integers [M, 4] (succ, found_search, iters, spare) - none of them modified; returns the new ``(w, m1, v, x, x_best,
+    fstate, istate)``.  With ``first`` w, m1, v, x_best and the records are not read (None will do) and ``x`` is the
+    clean image.  Per image, with L = sign * loss, D = sum (x - x0)^2 and w0 = ``cw_w0(x0)``:
+
+        first:       c = c_init; c_lo = 0; c_hi = CW_C_INF; d_best = inf; succ = found_search = iters = 0
+                     w = w0; m1 = v = 0; x_best = x0
+        evaluate:    ok = L > 0 and L >= kappa;  ok: succ = 1, and if D < d_best: d_best = D, x_best = x,
+                     found_search = search + 1
+        last:        stop here
+        search_end:  succ: c_hi = min(c_hi, c), c = (c_lo + c_hi) / 2 if c_hi < CW_C_BIG
+                     else: c_lo = max(c_lo, c), c = (c_lo + c_hi) / 2 if c_hi < CW_C_BIG else 10 c
+                     succ = 0; w = w0; m1 = v = 0; x = x0
+        otherwise:   th = tanh(w); act = L < kappa
+                     gx = (2 dist_scale) (x - x0) - (sign c act) dx;  gw = gx ((0.5 (hi - lo)) (1 - th th))
+                     m1 = beta1 m1 + (1 - beta1) gw;  v = beta2 v + ((1 - beta2) gw) gw
+                     w = w - (lr (m1 / bc1)) / (sqrt(v / bc2) + adam_eps),  (bc1, bc2) = ``cw_bias_corrections(t)``
+                     x = clamp(lo + (hi - lo) (0.5 (tanh(w) + 1)), lo, hi); iters += 1
+
+    Every scalar is rounded to float32 first, as the kernel receives it."""
+    import numpy as np
+    if sign not in (1, -1) or (first and last) or not kappa >= 0 or not lr > 0 or int(search) < 0:
+        raise ValueError("cw_step_reference: sign is +1 or -1, kappa >= 0, lr > 0, search >= 0, and a launch is not "
+                         "first and last")
+    if first and not c_init > 0:
+        raise ValueError("cw_step_reference: c_init must be > 0")
+    f32 = np.float32
+    dt, dev = torch.float32, dx.device
+    M = dx.shape[0]
+    kap, lo32, hi32 = float(f32(kappa)), f32(lo), f32(hi)
+    span = hi32 - lo32
+    big = float(f32(CW_C_BIG))
+    x0, x = x0.reshape(M, 784).to(dt), x.reshape(M, 784).to(dt)
+    L = float(sign) * loss_rows.reshape(M).to(dt)
+    i32 = dict(dtype=torch.int32, device=dev)
+    if first:
+        c = torch.full((M,), float(f32(c_init)), dtype=dt, device=dev)
+        c_lo, c_hi = torch.zeros_like(c), torch.full_like(c, float(f32(CW_C_INF)))
+        d_best = torch.full_like(c, float("inf"))
+        succ, found, iters, spare = (torch.zeros(M, **i32) for _ in range(4))
+        xb = x0
+    else:
+        c, c_lo, c_hi, d_best = fstate.reshape(M, 4).to(dt).unbind(dim=1)
+        succ, found, iters, spare = istate.reshape(M, 4).to(torch.int32).unbind(dim=1)
+        xb = x_best.reshape(M, 784).to(dt)
+    D = (x - x0).square().sum(dim=1)
+    ok = (L > 0) & (L >= kap)
+    improved = ok & (D < d_best)
+    succ = torch.where(ok, torch.ones_like(succ), succ)
+    d_best = torch.where(improved, D, d_best)
+    found = torch.where(improved, torch.full_like(found, int(search) + 1), found)
+    xb = torch.where(improved[:, None], x, xb)
+    pack = lambda: (torch.stack((c, c_lo, c_hi, d_best), dim=1),                              # noqa: E731
+                    torch.stack((succ, found, iters, spare), dim=1))
+    w0 = cw_w0(x0, lo, hi)
+    if last:
+        return (w.reshape(M, 784).clone(), m1.reshape(M, 784).clone(), v.reshape(M, 784).clone(), x.clone(), xb,
+                *pack())
+    if search_end:
+        s = succ > 0
+        hi_s = torch.minimum(c_hi, c)
+        c_s = torch.where(hi_s < big, (c_lo + hi_s) * 0.5, c)
+        lo_f = torch.maximum(c_lo, c)
+        c_f = torch.where(c_hi < big, (lo_f + c_hi) * 0.5, c * 10.0)
+        c, c_lo, c_hi = torch.where(s, c_s, c_f), torch.where(s, c_lo, lo_f), torch.where(s, hi_s, c_hi)
+        succ = torch.zeros_like(succ)
+        return (w0, torch.zeros_like(x0), torch.zeros_like(x0), x0.clone(), xb, *pack())
+    if first:
+        w, m1, v = w0, torch.zeros_like(x0), torch.zeros_like(x0)
+    else:
+        w, m1, v = (q.reshape(M, 784).to(dt) for q in (w, m1, v))
+    b1, b2 = f32(beta1), f32(beta2)
+    bc1, bc2 = (torch.tensor(q, dtype=dt, device=dev) for q in cw_bias_corrections(t, beta1, beta2))   # (as cw_w0)
+    k2 = float(f32(2.0) * f32(cw_dist_scale() if dist_scale is None else dist_scale))
+    s = ((float(sign) * c) * (L < kap).to(dt))[:, None]
+    th = torch.tanh(w)
+    gx = k2 * (x - x0) - s * dx.reshape(M, 784).to(dt)
+    gw = gx * (float(f32(0.5) * span) * (1.0 - th * th))
+    m1 = float(b1) * m1 + float(f32(1.0) - b1) * gw
+    v = float(b2) * v + (float(f32(1.0) - b2) * gw) * gw
+    w = w - (float(f32(lr)) * (m1 / bc1)) / (torch.sqrt(v / bc2) + float(f32(adam_eps)))
+    x_new = (float(lo32) + float(span) * (0.5 * (torch.tanh(w) + 1.0))).clamp(float(lo32), float(hi32))
+    iters = iters + 1
+    return (w, m1, v, x_new, xb, *pack())
+
+
+def cw_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, w: torch.Tensor, m1: torch.Tensor,
+            v: torch.Tensor, x: torch.Tensor, x_best: torch.Tensor, fstate: torch.Tensor, istate: torch.Tensor,
+            sign: float, kappa: float, lr: float, c_init: float, t: int, search: int, lo: float, hi: float,
+            beta1: float = CW_BETA1, beta2: float = CW_BETA2, adam_eps: float = CW_ADAM_EPS,
+            dist_scale: float | None = None, first: bool = False, search_end: bool = False, last: bool = False,
+            M: int | None = None) -> None:
+    """One Carlini-Wagner L2 iteration per image (``csrc/kernels/cw.hip``), one launch, in place: from the gradient
+    rows ``dx`` (float32 [>= M, 784], what ``input_grad`` wrote) and the CW margins ``loss_rows`` (float32 [>= M], what
+    ``head_margin`` stored) at the iterate ``x``, and the clean images ``x0``, the update of ``cw_step_reference`` on
+    ``w``, ``m1``, ``v``, ``x``, ``x_best`` (float32 [>= M, 784]), ``fstate`` (float32 [>= M, 4]) and ``istate``
+    (int32 [>= M, 4]).  float32 throughout, the distance a fixed tree: the same operands give the same bits.
+    ``first``: no state is read, all of it is written, and ``x`` must hold ``x0``; ``search_end``: the bisection of c
+    and the restart from the clean image; ``last``: only the best point and the records are brought up to date.
+    ``t``: Adam's step index inside the search step (>= 1); ``search``: the search step's index.  ``M``: the images
+    of the launch (default ``x.shape[0]``); nothing past M is touched."""
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("cw_step: x must be a float32 [M, 784] tensor on the GPU")
+    dev = x.device
+    M = int(x.shape[0] if M is None else M)
+    if M < 1 or M > CW_MAX_M:
+        raise ValueError(f"cw_step: M = {M} images must be in [1, CW_MAX_M = {CW_MAX_M}] a launch")
+    rows = (("dx", dx), ("x0", x0), ("w", w), ("m1", m1), ("v", v), ("x", x), ("x_best", x_best))
+    for what, q in rows:
+        _f32_rows("cw_step", what, q, M, dev, at_least="M")
+    _df_vec("cw_step", "loss_rows", loss_rows, torch.float32, M, dev, "M")
+    _df_vec("cw_step", "fstate", fstate, torch.float32, 4 * M, dev, "4 M")
+    _df_vec("cw_step", "istate", istate, torch.int32, 4 * M, dev, "4 M")
+    ptrs = [q.data_ptr() for _, q in rows]
+    if len(set(ptrs)) != len(ptrs):
+        raise ValueError("cw_step: dx, x0, w, m1, v, x and x_best must be seven buffers")
+    if sign not in (1, -1) or not kappa >= 0 or not lr > 0 or not lo < hi or int(search) < 0 or (first and last):
+        raise ValueError("cw_step: need sign +1 or -1, kappa >= 0, lr > 0, lo < hi, search >= 0, and not first and last")
+    if first and not c_init > 0:
+        raise ValueError("cw_step: c_init must be > 0")
+    if not (0 <= beta1 < 1 and 0 <= beta2 < 1 and adam_eps > 0):
+        raise ValueError("cw_step: need beta1, beta2 in [0, 1) and adam_eps > 0")
+    bc1, bc2 = cw_bias_corrections(t, beta1, beta2)
+    p = native.ptr
+    _C().cw_step(p(dx), p(loss_rows), p(x0), p(w), p(m1), p(v), p(x), p(x_best), p(fstate), p(istate), float(sign),
+                 float(kappa), float(lr), float(c_init), float(beta1), float(beta2), float(adam_eps), bc1, bc2,
+                 float(cw_dist_scale() if dist_scale is None else dist_scale), float(lo), float(hi), int(search),
+                 bool(first), bool(search_end), bool(last), M, _s())
+
+
 SQUARE_PHILOX_DOMAIN = 0x53515231   # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
-SQUARE_MAX_M = 1 << 20              # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
+SQUARE_MAX_M = 1 << 20             # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
 SQUARE_MAX_SIDE = 27
 # columns of the per-image record, int32 [M, 4] (kernels.h SquareStepArgs); column 0 holds the bits of a float32
 SQUARE_MARGIN, SQUARE_QUERIES, SQUARE_DONE = 0, 1, 2
