@@ -49,6 +49,7 @@ void mnist::preload_all_kernels() {
   preload_fab();
   preload_apgd_l1();
   preload_cw();
+  preload_ibp();
 }
 
 namespace {
@@ -637,6 +638,39 @@ PYBIND11_MODULE(_C, m) {
      "one Carlini-Wagner L2 iteration per image: success test and nearest success, Adam step in tanh space (or, "
      "search_end, the bisection of c and the restart from the clean image); fstate [M][4] = c, c_lo, c_hi, d_best; "
      "istate [M][4] = succ, found_search, iters, spare");
+
+  // ---------------- Interval bound propagation (L-inf certificates) ----------------
+  m.attr("IBP_SPLITS") = IBP_SPLITS;
+  m.attr("IBP_MAX_B") = IBP_MAX_B;
+  m.def("ibp_trunk", [](uintptr_t param, uintptr_t x0, uintptr_t rec, uintptr_t pl, uintptr_t pu, float pix_std,
+                        float lo, float hi, int B, uintptr_t stream) {
+    IbpArgs a{};
+    a.param = P<const float>(param); a.x0 = P<const float>(x0); a.rec = P<float>(rec);
+    a.pl = P<float>(pl); a.pu = P<float>(pu); a.pix_std = pix_std; a.lo = lo; a.hi = hi;
+    launch_ibp_trunk(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("x0"), py::arg("rec"), py::arg("pl"), py::arg("pu"), py::arg("pix_std"), py::arg("lo"),
+     py::arg("hi"), py::arg("B"), py::arg("stream"),
+     "IBP: the input box of radius rec[i][0] / pix_std inside [lo, hi], conv1, conv2 (fp32 MFMA, centre / radius), "
+     "ReLU and the pool: pl, pu fp32 [B][9216] in torch flatten order");
+  m.def("ibp_fc1", [](uintptr_t param, uintptr_t pl, uintptr_t pu, uintptr_t part, int B, uintptr_t stream) {
+    IbpArgs a{};
+    a.param = P<const float>(param); a.pl = P<float>(pl); a.pu = P<float>(pu); a.part = P<float>(part);
+    launch_ibp_fc1(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("pl"), py::arg("pu"), py::arg("part"), py::arg("B"), py::arg("stream"),
+     "IBP: fc1 centre and radius products, split-K partial sums part[IBP_SPLITS][B][2][128]");
+  m.def("ibp_head", [](uintptr_t param, uintptr_t part, uintptr_t labels, uintptr_t lb, uintptr_t rec, bool search,
+                       int B, uintptr_t stream) {
+    IbpArgs a{};
+    a.param = P<const float>(param); a.part = P<float>(part); a.labels = P<const int32_t>(labels);
+    a.lb = P<float>(lb); a.rec = P<float>(rec); a.search = search ? 1 : 0;
+    launch_ibp_head(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("part"), py::arg("labels"), py::arg("lb"), py::arg("rec"), py::arg("search"),
+     py::arg("B"), py::arg("stream"),
+     "IBP: fc1 bias + ReLU bounds and the elided last layer: lb[B][10] lower bounds of z_y - z_j; search: bisect "
+     "rec[i] = {eps, lo, hi, margin}");
 
   // ---------------- Square Attack ----------------
   m.attr("SQUARE_PHILOX_DOMAIN") = SQUARE_PHILOX_DOMAIN;

@@ -578,6 +578,32 @@ struct CwStepArgs {
 // M in [1, INPUT_GRAD_MAX_B], sign +-1, kappa >= 0, lr > 0, c_init > 0 when first, not first and last at once
 void launch_cw_step(const CwStepArgs& a, int M, hipStream_t s);
 
+// ---------------- Interval bound propagation, L-inf (ibp.hip; Gowal et al. 2018, Mirman et al. 2018) ----------------
+// Sound bounds of the fp32 net's logit differences over the box |x - x0|_inf <= eps (pixel units) inside the valid
+// pixel range, in centre / radius form, fp32 on v_mfma_f32_16x16x4_f32: one round is ibp_trunk -> ibp_fc1 -> ibp_head
+// on one stream.  The parameters are the flat fp32 buffer (torch layouts at the OFF_* offsets), never the bf16 shadows.
+// PER-IMAGE RECORD, 16 bytes (array 16-byte aligned): rec[i] = {eps, lo, hi, margin}: ibp_trunk reads eps (pixel
+// units), ibp_head with `search` bisects: margin = min_j lb_j; margin > 0: lo = eps, else hi = eps (a NaN margin is
+// not certified); eps = lo + 0.5 (hi - lo).  It starts at {eps_max, 0, eps_max, 0}.  Rows past B are untouched.
+constexpr int IBP_SPLITS = 36;                           // fc1 split-K: fixed, whatever B is (256 inputs a split)
+constexpr int IBP_MAX_B = 65535;                         // most images a launch takes (ibp_trunk's grid y)
+struct IbpArgs {
+  const float* param;         // the flat fp32 parameter buffer (PARAM_TOTAL floats)
+  const float* x0;            // fp32 [B][784] normalised rows                                   (ibp_trunk)
+  float* rec;                 // [B][4] the records: read by ibp_trunk, read / updated by ibp_head
+  float* pl;                  // fp32 [B][9216] lower / upper bounds after the pool, torch flatten order:
+  float* pu;                  //   written by ibp_trunk, read by ibp_fc1
+  float* part;                // fp32 [IBP_SPLITS][B][2][128] fc1 partial sums (centre, radius): ibp_fc1 -> ibp_head
+  const int32_t* labels;      // [B] in [0, 10)                                                  (ibp_head)
+  float* lb;                  // fp32 [B][10] lower bounds of z_y - z_j, +inf at j = y           (ibp_head)
+  float pix_std, lo, hi;      // the box is x0 -+ eps / pix_std (MNIST_STD) inside [lo, hi]: normalised units (ibp_trunk)
+  int search;                 // ibp_head: update the records
+};
+// B in [1, IBP_MAX_B]; each launcher's own arrays non-null and 16-byte aligned (labels 4-byte); lo < hi, pix_std > 0
+void launch_ibp_trunk(const IbpArgs& a, int B, hipStream_t s);
+void launch_ibp_fc1(const IbpArgs& a, int B, hipStream_t s);
+void launch_ibp_head(const IbpArgs& a, int B, hipStream_t s);
+
 // ---------------- Square Attack (square.hip; Andriushchenko, Croce, Flammarion, Hein 2020), L-inf ----------------
 // A score-based black-box attack: one query is one eval forward of the candidate x_cand, then square_step reads the
 // candidate's margin from head_eval's logp row (untargeted lp[y] - max_{j != y} lp[j]; targeted the negative; < 0:
@@ -737,6 +763,7 @@ void preload_square_l2();
 void preload_fab();
 void preload_apgd_l1();
 void preload_cw();
+void preload_ibp();
 void preload_all_kernels();  // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

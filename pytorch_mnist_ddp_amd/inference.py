@@ -1061,6 +1061,63 @@ class Predictor:
         hit = lp.argmax(dim=1) == labels
         return x_adv, d_best.sqrt() * MNIST_STD, lp, hit if targeted else ~hit
 
+    # ------------------------------------------------------------------ L-inf certificates (IBP)
+    def _ibp_input(self, name: str, x: torch.Tensor, labels):
+        B = self._check_input(x)
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels(name, labels, B, check_range=True)
+        return x0, labels
+
+    def verify_linf(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1):
+        """(certified, margin_lb): a deterministic L-inf certificate by interval bound propagation (Gowal et al. 2018).
+        ``margin_lb``: float32 [B,10], lower bounds of z_labels - z_j over every input within ``eps`` of ``x`` (pixel
+        units on the [0, 1] scale, as every ``eps`` here) inside the valid pixel range, +inf at j = labels;
+        ``certified``: bool [B], whether all of them are positive - no such input leaves ``labels``.  A NaN is not
+        certified.  ``labels``: the class to hold, or the class predicted on the clean input when None.
+
+        The statement is about the fp32 network (the fp32 parameters, inference semantics) in real arithmetic:
+        rounding inside the bound is not propagated outward, and a ``dtype="bf16"`` predictor can disagree with the
+        fp32 net on an exact near-tie.  IBP is loose on a net not trained for it: expect certificates only at small
+        eps.  GPU, either dtype: the native round ``ops.ibp.fused_ibp`` (fp32 kernels); CPU:
+        ``ops.functional.ibp_reference``."""
+        if not eps >= 0:
+            raise ValueError(f"verify_linf: eps must be >= 0, got {eps}")
+        x0, labels = self._ibp_input("verify_linf", x, labels)
+        if self.device.type == "cuda":
+            from .ops.ibp import fused_ibp
+            lb = fused_ibp(self.net, x0, labels, float(eps))
+        else:
+            from .ops.functional import ibp_reference
+            lb = ibp_reference(self.net, x0, labels, float(eps))["lb"]
+        return lb.min(dim=1).values > 0, lb
+
+    def certified_radius_linf(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps_max: float = 0.1,
+                              search_steps: int = 10):
+        """(radii, certified, margin): each image's certified L-inf radius by bisection of ``verify_linf``'s bound over
+        [0, ``eps_max``], ``search_steps`` bisections after the round at ``eps_max``.  ``radii``: float32 [B], pixel
+        units, an eps at which the bound itself was positive, or 0 (an image certified at ``eps_max`` has ``eps_max``);
+        ``certified`` = ``radii > 0``; ``margin``: float32 [B], min_j of the last round's bound.  The caveats of
+        ``verify_linf`` hold.  GPU: ``ops.ibp.fused_ibp_radius`` (the bisection runs in the kernel, no host round trip);
+        CPU: ``ibp_reference`` and ``ibp_search_reference``."""
+        if isinstance(search_steps, bool) or search_steps != int(search_steps) or search_steps < 0:
+            raise ValueError(f"certified_radius_linf: search_steps must be a non-negative integer, got {search_steps}")
+        if not eps_max >= 0:
+            raise ValueError(f"certified_radius_linf: eps_max must be >= 0, got {eps_max}")
+        x0, labels = self._ibp_input("certified_radius_linf", x, labels)
+        if self.device.type == "cuda":
+            from .ops.ibp import fused_ibp_radius
+            rec = fused_ibp_radius(self.net, x0, labels, float(eps_max), int(search_steps))
+        else:
+            from .ops.functional import ibp_reference, ibp_search_reference
+            rec = torch.tensor([eps_max, 0.0, eps_max, 0.0], dtype=torch.float32).repeat(x0.shape[0], 1)
+            for _ in range(int(search_steps) + 1):
+                rec = ibp_search_reference(rec, ibp_reference(self.net, x0, labels, rec[:, 0])["lb"])
+        radii = rec[:, 1].clone()
+        return radii, radii > 0, rec[:, 3].clone()
+
     # ------------------------------------------------------------------ randomized smoothing
     def smoothed_counts(self, x: torch.Tensor, sigma: float, n: int, seed: int = 0, ids=None,
                         sample_base: int = 0) -> torch.Tensor:
@@ -1383,6 +1440,18 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack the first M images of the split (default: all)')
     ap.add_argument('--cw-radii', type=_radii, default=(), metavar='R1,R2,...',
                     help='L2 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
+    ap.add_argument('--ibp-eps', type=float, default=None, metavar='E',
+                    help='also report how many images interval bound propagation certifies to keep their true label '
+                         'within L-inf radius E, in pixel units (default: off)')
+    ap.add_argument('--ibp-radius', action='store_true', default=False,
+                    help='also report the certified L-inf radius of the images by bisection of the IBP bound: how many '
+                         'are certified at all, the median and mean radius in pixel units (default: off)')
+    ap.add_argument('--ibp-eps-max', type=float, default=0.1, metavar='X', help='largest radius tried (default: 0.1)')
+    ap.add_argument('--ibp-search-steps', type=int, default=10, metavar='S', help='bisection steps (default: 10)')
+    ap.add_argument('--ibp-count', type=int, default=None, metavar='M',
+                    help='certify the first M images of the split (default: all)')
+    ap.add_argument('--ibp-radii', type=_radii, default=(), metavar='R1,R2,...',
+                    help='L-inf radii, in pixel units, at which certified accuracy is read off (default: none)')
     return ap
 
 
@@ -1475,6 +1544,18 @@ def cw_line(search_steps: int, steps: int, m: int, found: int, median, mean) -> 
     fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
     return (f"CW set (L2, search={search_steps}, steps={steps}): "
             f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
+
+
+def ibp_verified_line(eps: float, c: int, n: int) -> str:
+    """The ``Verified set`` line of ``mnist_predict.py --ibp-eps``: images certified to keep their true label."""
+    return f"Verified set (Linf eps={eps:g}, IBP): Accuracy: {c}/{n} ({100.0 * c / n:.0f}%)"
+
+
+def ibp_radius_line(eps_max: float, search_steps: int, m: int, certified: int, median, mean) -> str:
+    """The ``IBP set`` line of ``mnist_predict.py --ibp-radius``; the radii over the certified images."""
+    fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
+    return (f"IBP set (Linf, eps_max={eps_max:g}, search={search_steps}): Certified: {certified}/{m} "
+            f"({100.0 * certified / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
 def accuracy_at_radius_line(r: float, c: int, m: int) -> str:
@@ -1659,6 +1740,28 @@ def predict_main(argv=None) -> int:
                       apgd_l1_correct=l1_correct, apgd_l1_median_l0=l1_median)
         if args.apgd_l1_loss != "ce":
             record.update(apgd_l1_loss_name=args.apgd_l1_loss)
+    if args.ibp_eps is not None:
+        ver = sum(int(predictor.verify_linf(images[i:i + args.batch_size], data.targets[i:i + args.batch_size],
+                                            args.ibp_eps)[0].sum()) for i in range(0, n, args.batch_size))
+        print(ibp_verified_line(args.ibp_eps, ver, n))
+        record.update(ibp_eps=args.ibp_eps, ibp_verified=ver)
+    if args.ibp_radius:
+        m = n if args.ibp_count is None else max(1, min(n, args.ibp_count))
+        radii = torch.empty(m, dtype=torch.float32)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            radii[i:j] = predictor.certified_radius_linf(images[i:j], data.targets[i:j], args.ibp_eps_max,
+                                                         args.ibp_search_steps)[0].cpu()
+        cert = radii > 0
+        r = radii[cert].double()
+        median, mean = (float(r.quantile(0.5)), float(r.mean())) if r.numel() else (None, None)
+        at = [int((cert & (radii >= R)).sum()) for R in args.ibp_radii]
+        print(ibp_radius_line(args.ibp_eps_max, args.ibp_search_steps, m, int(cert.sum()), median, mean))
+        for R, c in zip(args.ibp_radii, at):
+            print(f"Certified accuracy at radius {R:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
+        record.update(ibp_eps_max=args.ibp_eps_max, ibp_search_steps=args.ibp_search_steps, ibp_count=m,
+                      ibp_certified=int(cert.sum()), ibp_median_radius=median, ibp_mean_radius=mean,
+                      ibp_accuracy_at={f"{R:g}": c for R, c in zip(args.ibp_radii, at)})
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

@@ -1534,6 +1534,168 @@ def cw_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, w: torc
                  bool(first), bool(search_end), bool(last), M, _s())
 
 
+IBP_SPLITS = 36                     # fc1 split-K of ibp_fc1: fixed, whatever the batch (kernels.h IBP_SPLITS)
+IBP_MAX_B = 65535                   # most images one ibp launch takes (kernels.h IBP_MAX_B)
+IBP_EPS, IBP_LO, IBP_HI, IBP_MARGIN = 0, 1, 2, 3         # columns of the per-image record, float32 [M, 4]
+
+
+def _ibp_setup(net_or_params, dtype, lo, hi):
+    """(parameters as ``dtype`` tensors by torch name, MNIST_STD / lo / hi as the float32 values the kernels get)."""
+    import numpy as np
+    from ..data.datasets import MNIST_STD, PIXEL_HI, PIXEL_LO
+    named = dict(net_or_params.named_parameters()) if hasattr(net_or_params, "named_parameters") else net_or_params
+    f32 = lambda v: float(np.float32(v))                                                       # noqa: E731
+    return ({k: v.detach().to(dtype) for k, v in named.items()}, f32(MNIST_STD),
+            f32(PIXEL_LO if lo is None else lo), f32(PIXEL_HI if hi is None else hi))
+
+
+def ibp_trunk_reference(net_or_params, x: torch.Tensor, eps: torch.Tensor, lo: float | None = None,
+                        hi: float | None = None, dtype=torch.float32):
+    """``ibp_trunk`` in torch ops on any device: ``(pl, pu)`` [M, 9216], the bounds after the pool in torch flatten
+    order, of the box ``[max(x - eps / STD, lo), min(x + eps / STD, hi)]`` (``x`` [M, 784] normalised, ``eps`` [M] in
+    pixel units) through conv1, ReLU, conv2, ReLU and the pool, each affine layer in centre / radius form: mu = (l + u)
+    / 2, r = (u - l) / 2, c = W mu + b, rad = |W| r, l' = c - rad, u' = c + rad.  A NaN passes every clamp."""
+    import torch.nn.functional as F
+    P, std, lo, hi = _ibp_setup(net_or_params, dtype, lo, hi)
+    M = x.shape[0]
+    x = x.reshape(M, 784).to(dtype)
+    e = (eps.reshape(M).to(dtype) / torch.tensor(std, dtype=dtype, device=x.device))[:, None]
+    l, u = torch.clamp(x - e, min=lo).view(M, 1, 28, 28), torch.clamp(x + e, max=hi).view(M, 1, 28, 28)
+    for name in ("conv1", "conv2"):
+        W, b = P[name + ".weight"], P[name + ".bias"]
+        c, rad = F.conv2d((l + u) * 0.5, W, b), F.conv2d((u - l) * 0.5, W.abs())
+        l, u = F.relu(c - rad), F.relu(c + rad)
+    return F.max_pool2d(l, 2).flatten(1), F.max_pool2d(u, 2).flatten(1)
+
+
+def ibp_fc1_reference(net_or_params, pl: torch.Tensor, pu: torch.Tensor, dtype=torch.float32):
+    """``ibp_fc1`` summed over its splits: ``(z1c, z1r)`` [M, 128] = fc1.weight (pl + pu) / 2, |fc1.weight| (pu - pl) / 2
+    (no bias: ``ibp_head`` adds it)."""
+    W = _ibp_setup(net_or_params, dtype, None, None)[0]["fc1.weight"]
+    pl, pu = pl.to(dtype), pu.to(dtype)
+    return ((pl + pu) * 0.5) @ W.t(), ((pu - pl) * 0.5) @ W.abs().t()
+
+
+def ibp_head_reference(net_or_params, part: torch.Tensor, labels: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """``ibp_head`` operation by operation: ``lb`` [M, 10] from the fc1 partial sums ``part`` [S, M, 2, 128] (centre,
+    radius; any S): the splits summed in order, + fc1.bias, l = relu(c - rad), u = relu(c + rad), then for j != y with
+    C = fc2.weight[y] - fc2.weight[j]: lb_j = sum_k (max(C_k, 0) l_k + min(C_k, 0) u_k) + (b_y - b_j), the sum as
+    (t_k + t_{k+64}) then the xor butterfly 32 .. 1 of the kernel's wave; lb_y = +inf."""
+    P = _ibp_setup(net_or_params, dtype, None, None)[0]
+    part = part.to(dtype)
+    M, y = part.shape[1], labels.reshape(-1).long()
+    c, rad = part[0, :, 0], part[0, :, 1]
+    for z in range(1, part.shape[0]):
+        c, rad = c + part[z, :, 0], rad + part[z, :, 1]
+    c = c + P["fc1.bias"]
+    l, u = torch.relu(c - rad)[:, None, :], torch.relu(c + rad)[:, None, :]
+    W2, b2 = P["fc2.weight"], P["fc2.bias"]
+    Cm = W2[y][:, None, :] - W2[None]
+    t = Cm.clamp(min=0) * l + Cm.clamp(max=0) * u
+    s = t[..., :64] + t[..., 64:]
+    idx = torch.arange(64, device=s.device)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[..., idx ^ o]
+    lb = s[..., 0] + (b2[y][:, None] - b2[None, :])
+    lb[torch.arange(M, device=lb.device), y] = float("inf")
+    return lb
+
+
+def ibp_reference(net_or_params, x: torch.Tensor, labels: torch.Tensor, eps, dtype=torch.float32,
+                  lo: float | None = None, hi: float | None = None) -> dict:
+    """Interval bound propagation of the Net (inference semantics) over the L-inf box of radius ``eps`` (pixel units,
+    a number or [M]) around the normalised rows ``x`` [M, 784], clipped to the valid pixel range, in torch ops on any
+    device - the kernels' formulas, stage by stage: ``pl``, ``pu`` [M, 9216] (after the pool), ``z1c``, ``z1r`` [M, 128]
+    (fc1 centre and radius, before the bias), ``lb`` [M, 10] (lower bounds of z_y - z_j, +inf at y), ``margin`` [M]
+    (min_j lb_j, NaN where any is) and ``certified`` (margin > 0).  ``net_or_params``: a Net, or its parameters by
+    torch name."""
+    M = x.shape[0]
+    eps = torch.as_tensor(eps, dtype=dtype, device=x.device).expand(M)
+    pl, pu = ibp_trunk_reference(net_or_params, x, eps, lo, hi, dtype)
+    z1c, z1r = ibp_fc1_reference(net_or_params, pl, pu, dtype)
+    lb = ibp_head_reference(net_or_params, torch.stack((z1c, z1r), dim=1)[None], labels, dtype)
+    margin = lb.min(dim=1).values
+    return {"pl": pl, "pu": pu, "z1c": z1c, "z1r": z1r, "lb": lb, "margin": margin, "certified": margin > 0}
+
+
+def ibp_search_reference(rec: torch.Tensor, lb: torch.Tensor) -> torch.Tensor:
+    """The record update of ``ibp_head`` with ``search``: from ``rec`` [M, 4] = (eps, lo, hi, margin) and ``lb``
+    [M, 10]: margin = min_j lb_j; margin > 0 (a NaN is not): lo = eps, else hi = eps; eps = lo + 0.5 (hi - lo)."""
+    rec = rec.to(torch.float32)
+    margin = lb.to(torch.float32).min(dim=1).values
+    cert = margin > 0
+    lo, hi = torch.where(cert, rec[:, IBP_EPS], rec[:, IBP_LO]), torch.where(cert, rec[:, IBP_HI], rec[:, IBP_EPS])
+    return torch.stack((lo + 0.5 * (hi - lo), lo, hi, margin), dim=1)
+
+
+def _ibp_buf(name: str, what: str, t: torch.Tensor | None, count: int, dev, dtype=torch.float32) -> torch.Tensor:
+    """The float32 array ``t`` of at least ``count`` entries of an ibp launch; a new one when None."""
+    if t is None:
+        return torch.empty(count, dtype=dtype, device=dev)
+    _df_vec(name, what, t, dtype, count, dev, str(count))
+    return t
+
+
+def _ibp_param(name: str, param: torch.Tensor, M: int) -> None:
+    if param.dtype != torch.float32 or param.device.type != "cuda" or not param.is_contiguous() or \
+            param.numel() != _C().PARAM_TOTAL:
+        raise ValueError(f"{name}: param must be the flat float32 parameter buffer on the GPU")
+    if M < 1 or M > IBP_MAX_B:
+        raise ValueError(f"{name}: M = {M} images must be in [1, IBP_MAX_B = {IBP_MAX_B}] a launch")
+
+
+def ibp_trunk(param: torch.Tensor, x: torch.Tensor, rec: torch.Tensor, pl: torch.Tensor | None = None,
+              pu: torch.Tensor | None = None, lo: float | None = None, hi: float | None = None, M: int | None = None):
+    """One launch of ``ibp_trunk`` (csrc/kernels/ibp.hip): ``(pl, pu)`` float32 [>= M, 9216] in torch flatten order
+    from the normalised rows ``x`` (float32 [>= M, 784]) and each image's eps ``rec[i, 0]`` (float32 [>= M, 4], pixel
+    units), through the flat fp32 parameters ``param`` (``ModelState.param``).  Nothing past M is touched."""
+    M = int(x.shape[0] if M is None else M)
+    _ibp_param("ibp_trunk", param, M)
+    dev = param.device
+    _f32_rows("ibp_trunk", "x", x, M, dev, at_least="M")
+    _df_vec("ibp_trunk", "rec", rec, torch.float32, 4 * M, dev, "4 M")
+    pl, pu = (_ibp_buf("ibp_trunk", k, q, M * NFLAT, dev) for k, q in (("pl", pl), ("pu", pu)))
+    _, std, lo, hi = _ibp_setup({}, torch.float32, lo, hi)
+    if not lo < hi or pl.data_ptr() == pu.data_ptr():
+        raise ValueError("ibp_trunk: need lo < hi and two output buffers")
+    p = native.ptr
+    _C().ibp_trunk(p(param), p(x), p(rec), p(pl), p(pu), std, lo, hi, M, _s())
+    return pl.view(-1, NFLAT), pu.view(-1, NFLAT)
+
+
+def ibp_fc1(param: torch.Tensor, pl: torch.Tensor, pu: torch.Tensor, part: torch.Tensor | None = None,
+            M: int | None = None) -> torch.Tensor:
+    """One launch of ``ibp_fc1``: the split-K partial sums ``part`` (float32, ``IBP_SPLITS * M * 256`` entries laid out
+    [IBP_SPLITS, M, 2, 128]: centre, radius) of fc1 over the bounds ``pl``, ``pu`` (float32 [>= M, 9216], torch flatten
+    order).  An image's values do not depend on M or on its row.  Nothing past that many entries is touched."""
+    M = int(pl.shape[0] if M is None else M)
+    _ibp_param("ibp_fc1", param, M)
+    dev = param.device
+    for what, q in (("pl", pl), ("pu", pu)):
+        _df_vec("ibp_fc1", what, q, torch.float32, M * NFLAT, dev, "M * 9216")
+    part = _ibp_buf("ibp_fc1", "part", part, IBP_SPLITS * M * 2 * NH, dev)
+    p = native.ptr
+    _C().ibp_fc1(p(param), p(pl), p(pu), p(part), M, _s())
+    return part
+
+
+def ibp_head(param: torch.Tensor, part: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor,
+             lb: torch.Tensor | None = None, search: bool = False, M: int | None = None) -> torch.Tensor:
+    """One launch of ``ibp_head``: ``lb`` float32 [>= M, 10] (``ibp_head_reference``) from ``part`` ([IBP_SPLITS, M,
+    2, 128] as ``ibp_fc1`` wrote it) and the int32 ``labels`` [>= M] in [0, 10) (not checked).  ``search``: the records
+    ``rec`` (float32 [>= M, 4]) are updated as ``ibp_search_reference`` does from this launch's ``lb``; else only read."""
+    M = int(labels.numel() if M is None else M)
+    _ibp_param("ibp_head", param, M)
+    dev = param.device
+    _df_vec("ibp_head", "part", part, torch.float32, IBP_SPLITS * M * 2 * NH, dev, "IBP_SPLITS * M * 256")
+    _df_vec("ibp_head", "labels", labels, torch.int32, M, dev, "M")
+    _df_vec("ibp_head", "rec", rec, torch.float32, 4 * M, dev, "4 M")
+    lb = _ibp_buf("ibp_head", "lb", lb, M * NCLS, dev)
+    p = native.ptr
+    _C().ibp_head(p(param), p(part), p(labels), p(lb), p(rec), bool(search), M, _s())
+    return lb.view(-1, NCLS)
+
+
 SQUARE_PHILOX_DOMAIN = 0x53515231   # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
 SQUARE_MAX_M = 1 << 20             # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
 SQUARE_MAX_SIDE = 27
