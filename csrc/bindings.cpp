@@ -50,6 +50,7 @@ void mnist::preload_all_kernels() {
   preload_apgd_l1();
   preload_cw();
   preload_ibp();
+  preload_crown();
 }
 
 namespace {
@@ -670,6 +671,64 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("param"), py::arg("part"), py::arg("labels"), py::arg("lb"), py::arg("rec"), py::arg("search"),
      py::arg("B"), py::arg("stream"),
      "IBP: fc1 bias + ReLU bounds and the elided last layer: lb[B][10] lower bounds of z_y - z_j; search: bisect "
+     "rec[i] = {eps, lo, hi, margin}");
+
+  // ---------------- CROWN-IBP (L-inf certificates) ----------------
+  m.attr("CROWN_SPEC") = CROWN_SPEC;
+  m.attr("CROWN_SLICES") = CROWN_SLICES;
+  m.attr("CROWN_STRIPS") = CROWN_STRIPS;
+  m.def("crown_relax", [](uintptr_t param, uintptr_t x0, uintptr_t rec, uintptr_t pl, uintptr_t pu, uintptr_t relax,
+                          float pix_std, float lo, float hi, int B, uintptr_t stream) {
+    CrownArgs a{};
+    a.param = P<const float>(param); a.x0 = P<const float>(x0); a.rec = P<float>(rec); a.pl = P<float>(pl);
+    a.pu = P<float>(pu); a.relax = P<float>(relax); a.pix_std = pix_std; a.lo = lo; a.hi = hi;
+    launch_crown_relax(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("x0"), py::arg("rec"), py::arg("pl"), py::arg("pu"), py::arg("relax"),
+     py::arg("pix_std"), py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
+     "CROWN-IBP: ibp_trunk's pl, pu and, per pooled unit, the relaxation record relax[B][9216][4] = (sL, sU, bU, i*)");
+  m.def("crown_lambda", [](uintptr_t param, uintptr_t part, uintptr_t labels, uintptr_t lam, uintptr_t fcb, int B,
+                           uintptr_t stream) {
+    CrownArgs a{};
+    a.param = P<const float>(param); a.part = P<const float>(part); a.labels = P<const int32_t>(labels);
+    a.lam = P<float>(lam); a.fcb = P<float>(fcb);
+    launch_crown_lambda(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("part"), py::arg("labels"), py::arg("lam"), py::arg("fcb"), py::arg("B"),
+     py::arg("stream"),
+     "CROWN-IBP: from the fc1 slab the relaxed margin rows lam[B][16][128], and fcb[B][2][16] = (bias so far, lb_ibp)");
+  m.def("crown_fc", [](uintptr_t param, uintptr_t relax, uintptr_t lam, uintptr_t v, uintptr_t vb, int B,
+                       uintptr_t stream) {
+    CrownArgs a{};
+    a.param = P<const float>(param); a.relax = P<float>(relax); a.lam = P<float>(lam); a.v = P<float>(v);
+    a.vb = P<float>(vb);
+    launch_crown_fc(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("relax"), py::arg("lam"), py::arg("v"), py::arg("vb"), py::arg("B"), py::arg("stream"),
+     "CROWN-IBP: lam fc1.weight on the fp32 MFMA and the pool relaxation: v[B][10][9216], bias partials "
+     "vb[B][CROWN_SLICES][16]");
+  m.def("crown_bwd", [](uintptr_t param, uintptr_t x0, uintptr_t rec, uintptr_t relax, uintptr_t v, uintptr_t labels,
+                        uintptr_t sp, float pix_std, float lo, float hi, int B, uintptr_t stream) {
+    CrownArgs a{};
+    a.param = P<const float>(param); a.x0 = P<const float>(x0); a.rec = P<float>(rec); a.relax = P<float>(relax);
+    a.v = P<float>(v); a.labels = P<const int32_t>(labels); a.sp = P<float>(sp);
+    a.pix_std = pix_std; a.lo = lo; a.hi = hi;
+    launch_crown_bwd(a, B, S(stream));
+    check_launch();
+  }, py::arg("param"), py::arg("x0"), py::arg("rec"), py::arg("relax"), py::arg("v"), py::arg("labels"),
+     py::arg("sp"), py::arg("pix_std"), py::arg("lo"), py::arg("hi"), py::arg("B"), py::arg("stream"),
+     "CROWN-IBP: the transposed conv2 (fp32 MFMA), the conv1 relaxation, the transposed conv1 and the concretisation "
+     "over the box: sp[B][CROWN_STRIPS][10][2] = (sum, bias) a strip of 4 input rows");
+  m.def("crown_head", [](uintptr_t fcb, uintptr_t vb, uintptr_t sp, uintptr_t labels, uintptr_t lbc, uintptr_t lb,
+                         uintptr_t rec, bool search, int B, uintptr_t stream) {
+    CrownArgs a{};
+    a.fcb = P<float>(fcb); a.vb = P<float>(vb); a.sp = P<float>(sp); a.labels = P<const int32_t>(labels);
+    a.lbc = P<float>(lbc); a.lb = P<float>(lb); a.rec = P<float>(rec); a.search = search ? 1 : 0;
+    launch_crown_head(a, B, S(stream));
+    check_launch();
+  }, py::arg("fcb"), py::arg("vb"), py::arg("sp"), py::arg("labels"), py::arg("lbc"), py::arg("lb"), py::arg("rec"),
+     py::arg("search"), py::arg("B"), py::arg("stream"),
+     "CROWN-IBP: lb[B][10] = max(lb_crown, lb_ibp) from the partials (lbc: lb_crown, or 0 for none); search: bisect "
      "rec[i] = {eps, lo, hi, margin}");
 
   // ---------------- Square Attack ----------------

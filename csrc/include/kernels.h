@@ -604,6 +604,41 @@ void launch_ibp_trunk(const IbpArgs& a, int B, hipStream_t s);
 void launch_ibp_fc1(const IbpArgs& a, int B, hipStream_t s);
 void launch_ibp_head(const IbpArgs& a, int B, hipStream_t s);
 
+// ---------------- CROWN-IBP, L-inf (crown.hip; Zhang et al. 2018 / 2020) ----------------
+// IBP's boxes for every hidden layer, then one backward pass of linear relaxations from the 10 margin rows of an image
+// down to its input box; the result is max(lb_crown, lb_ibp).  fp32 on v_mfma_f32_16x16x4_f32, the same record, the
+// same contract (an image's bits depend on the image alone).  One round on one stream:
+//   crown_relax -> ibp_fc1 -> crown_lambda -> crown_fc -> crown_bwd -> crown_head
+constexpr int CROWN_SPEC = 16;                           // specification slots an image: rows 0 .. 9 = class j, the rest 0
+constexpr int CROWN_SLICES = NFLAT / 16;                 // 576 column slices of crown_fc's bias partials
+constexpr int CROWN_STRIPS = 7;                          // crown_bwd: strips of 4 input rows
+struct CrownArgs {
+  const float* param;         // the flat fp32 parameter buffer
+  const float* x0;            // fp32 [B][784] normalised rows                                  (crown_relax, crown_bwd)
+  float* rec;                 // [B][4] the records of IbpArgs: eps read, updated by crown_head with `search`
+  float* pl;                  // fp32 [B][9216] pooled bounds                                   (crown_relax -> ibp_fc1)
+  float* pu;
+  float* relax;               // fp32 [B][9216][4] per pooled unit (sL, sU, bU, bits of i* in 0 .. 3): crown_relax ->
+                              //   crown_fc (all four), crown_bwd (i*)
+  const float* part;          // the fc1 slab of ibp_fc1                                        (crown_lambda)
+  const int32_t* labels;      // [B]
+  float* lam;                 // fp32 [B][16][128] Lambda = C+ sL + C- sU at fc1                (crown_lambda -> crown_fc)
+  float* fcb;                 // fp32 [B][2][16]: the bias down to fc1's input, lb_ibp          (crown_lambda -> crown_head)
+  float* v;                   // fp32 [B][10][9216] coefficients of the conv2 pixels i*         (crown_fc -> crown_bwd)
+  float* vb;                  // fp32 [B][CROWN_SLICES][16] bias partials of the pool and conv2 (crown_fc -> crown_head)
+  float* sp;                  // fp32 [B][CROWN_STRIPS][10][2] (concretised sum, bias) a strip  (crown_bwd -> crown_head)
+  float* lbc;                 // fp32 [B][10] lb_crown before the max, or null                  (crown_head)
+  float* lb;                  // fp32 [B][10] max(lb_crown, lb_ibp), +inf at j = y              (crown_head)
+  float pix_std, lo, hi;
+  int search;
+};
+// B in [1, IBP_MAX_B]; each launcher's own arrays non-null and 16-byte aligned (labels 4-byte); lo < hi, pix_std > 0
+void launch_crown_relax(const CrownArgs& a, int B, hipStream_t s);
+void launch_crown_lambda(const CrownArgs& a, int B, hipStream_t s);
+void launch_crown_fc(const CrownArgs& a, int B, hipStream_t s);
+void launch_crown_bwd(const CrownArgs& a, int B, hipStream_t s);
+void launch_crown_head(const CrownArgs& a, int B, hipStream_t s);
+
 // ---------------- Square Attack (square.hip; Andriushchenko, Croce, Flammarion, Hein 2020), L-inf ----------------
 // A score-based black-box attack: one query is one eval forward of the candidate x_cand, then square_step reads the
 // candidate's margin from head_eval's logp row (untargeted lp[y] - max_{j != y} lp[j]; targeted the negative; < 0:
@@ -764,6 +799,7 @@ void preload_fab();
 void preload_apgd_l1();
 void preload_cw();
 void preload_ibp();
+void preload_crown();
 void preload_all_kernels();  // every one of the above, in this order (bindings.cpp: the one list)
 
 // ---------------- fp32 step (--dtype fp32; f32_net.hip): f32-input MFMA GEMMs + VALU kernels

@@ -1071,7 +1071,22 @@ class Predictor:
             labels = self._labels(name, labels, B, check_range=True)
         return x0, labels
 
-    def verify_linf(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1):
+    @staticmethod
+    def _ibp_method(name: str, method: str) -> bool:
+        """Whether ``method`` is "crown-ibp" (not "ibp"); anything else raises."""
+        if method not in ("ibp", "crown-ibp"):
+            raise ValueError(f'{name}: method must be "ibp" or "crown-ibp", got {method!r}')
+        return method == "crown-ibp"
+
+    def _crown_cpu(self, x0: torch.Tensor, labels: torch.Tensor, eps) -> torch.Tensor:
+        """``crown_ibp_reference``'s ``lb`` in chunks of 64 images (its coefficient planes are 0.9 MB an image)."""
+        from .ops.functional import crown_ibp_reference
+        eps = torch.as_tensor(eps, dtype=torch.float32).expand(x0.shape[0])
+        return torch.cat([crown_ibp_reference(self.net, x0[i:i + 64], labels[i:i + 64], eps[i:i + 64])["lb"]
+                          for i in range(0, x0.shape[0], 64)])
+
+    def verify_linf(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps: float = 0.1,
+                    method: str = "ibp"):
         """(certified, margin_lb): a deterministic L-inf certificate by interval bound propagation (Gowal et al. 2018).
         ``margin_lb``: float32 [B,10], lower bounds of z_labels - z_j over every input within ``eps`` of ``x`` (pixel
         units on the [0, 1] scale, as every ``eps`` here) inside the valid pixel range, +inf at j = labels;
@@ -1082,11 +1097,24 @@ class Predictor:
         rounding inside the bound is not propagated outward, and a ``dtype="bf16"`` predictor can disagree with the
         fp32 net on an exact near-tie.  IBP is loose on a net not trained for it: expect certificates only at small
         eps.  GPU, either dtype: the native round ``ops.ibp.fused_ibp`` (fp32 kernels); CPU:
-        ``ops.functional.ibp_reference``."""
+        ``ops.functional.ibp_reference``.
+
+        ``method="crown-ibp"`` (Zhang et al. 2020): IBP's boxes for the hidden layers, then one backward pass of
+        linear relaxations from the margin rows to the input box; the result is the larger of that bound and IBP's,
+        so it is never below ``method="ibp"``'s and certifies several times larger radii on a standard-trained net,
+        at roughly ten times the cost.  The same statement and caveats.  GPU: ``ops.crown.fused_crown_ibp``; CPU:
+        ``ops.functional.crown_ibp_reference``."""
+        crown = self._ibp_method("verify_linf", method)
         if not eps >= 0:
             raise ValueError(f"verify_linf: eps must be >= 0, got {eps}")
         x0, labels = self._ibp_input("verify_linf", x, labels)
-        if self.device.type == "cuda":
+        if crown:
+            if self.device.type == "cuda":
+                from .ops.crown import fused_crown_ibp
+                lb = fused_crown_ibp(self.net, x0, labels, float(eps))
+            else:
+                lb = self._crown_cpu(x0, labels, float(eps))
+        elif self.device.type == "cuda":
             from .ops.ibp import fused_ibp
             lb = fused_ibp(self.net, x0, labels, float(eps))
         else:
@@ -1095,19 +1123,29 @@ class Predictor:
         return lb.min(dim=1).values > 0, lb
 
     def certified_radius_linf(self, x: torch.Tensor, labels: torch.Tensor | None = None, eps_max: float = 0.1,
-                              search_steps: int = 10):
+                              search_steps: int = 10, method: str = "ibp"):
         """(radii, certified, margin): each image's certified L-inf radius by bisection of ``verify_linf``'s bound over
         [0, ``eps_max``], ``search_steps`` bisections after the round at ``eps_max``.  ``radii``: float32 [B], pixel
         units, an eps at which the bound itself was positive, or 0 (an image certified at ``eps_max`` has ``eps_max``);
         ``certified`` = ``radii > 0``; ``margin``: float32 [B], min_j of the last round's bound.  The caveats of
         ``verify_linf`` hold.  GPU: ``ops.ibp.fused_ibp_radius`` (the bisection runs in the kernel, no host round trip);
-        CPU: ``ibp_reference`` and ``ibp_search_reference``."""
+        CPU: ``ibp_reference`` and ``ibp_search_reference``.  ``method``: as ``verify_linf`` ("crown-ibp" on the GPU:
+        ``ops.crown.fused_crown_ibp_radius``)."""
+        crown = self._ibp_method("certified_radius_linf", method)
         if isinstance(search_steps, bool) or search_steps != int(search_steps) or search_steps < 0:
             raise ValueError(f"certified_radius_linf: search_steps must be a non-negative integer, got {search_steps}")
         if not eps_max >= 0:
             raise ValueError(f"certified_radius_linf: eps_max must be >= 0, got {eps_max}")
         x0, labels = self._ibp_input("certified_radius_linf", x, labels)
-        if self.device.type == "cuda":
+        if crown and self.device.type == "cuda":
+            from .ops.crown import fused_crown_ibp_radius
+            rec = fused_crown_ibp_radius(self.net, x0, labels, float(eps_max), int(search_steps))
+        elif crown:
+            from .ops.functional import ibp_search_reference
+            rec = torch.tensor([eps_max, 0.0, eps_max, 0.0], dtype=torch.float32).repeat(x0.shape[0], 1)
+            for _ in range(int(search_steps) + 1):
+                rec = ibp_search_reference(rec, self._crown_cpu(x0, labels, rec[:, 0]))
+        elif self.device.type == "cuda":
             from .ops.ibp import fused_ibp_radius
             rec = fused_ibp_radius(self.net, x0, labels, float(eps_max), int(search_steps))
         else:
@@ -1443,6 +1481,9 @@ def build_predict_parser() -> argparse.ArgumentParser:
     ap.add_argument('--ibp-eps', type=float, default=None, metavar='E',
                     help='also report how many images interval bound propagation certifies to keep their true label '
                          'within L-inf radius E, in pixel units (default: off)')
+    ap.add_argument('--ibp-method', choices=('ibp', 'crown-ibp'), default='ibp',
+                    help='the bound behind --ibp-eps and --ibp-radius: interval bound propagation, or CROWN-IBP '
+                         '(tighter, about ten times the cost; default: ibp)')
     ap.add_argument('--ibp-radius', action='store_true', default=False,
                     help='also report the certified L-inf radius of the images by bisection of the IBP bound: how many '
                          'are certified at all, the median and mean radius in pixel units (default: off)')
@@ -1546,15 +1587,20 @@ def cw_line(search_steps: int, steps: int, m: int, found: int, median, mean) -> 
             f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
-def ibp_verified_line(eps: float, c: int, n: int) -> str:
+def _ibp_method_name(method: str) -> str:
+    return "CROWN-IBP" if method == "crown-ibp" else "IBP"
+
+
+def ibp_verified_line(eps: float, c: int, n: int, method: str = "ibp") -> str:
     """The ``Verified set`` line of ``mnist_predict.py --ibp-eps``: images certified to keep their true label."""
-    return f"Verified set (Linf eps={eps:g}, IBP): Accuracy: {c}/{n} ({100.0 * c / n:.0f}%)"
+    return f"Verified set (Linf eps={eps:g}, {_ibp_method_name(method)}): Accuracy: {c}/{n} ({100.0 * c / n:.0f}%)"
 
 
-def ibp_radius_line(eps_max: float, search_steps: int, m: int, certified: int, median, mean) -> str:
+def ibp_radius_line(eps_max: float, search_steps: int, m: int, certified: int, median, mean,
+                    method: str = "ibp") -> str:
     """The ``IBP set`` line of ``mnist_predict.py --ibp-radius``; the radii over the certified images."""
     fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
-    return (f"IBP set (Linf, eps_max={eps_max:g}, search={search_steps}): Certified: {certified}/{m} "
+    return (f"{_ibp_method_name(method)} set (Linf, eps_max={eps_max:g}, search={search_steps}): Certified: {certified}/{m} "
             f"({100.0 * certified / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
@@ -1742,8 +1788,9 @@ def predict_main(argv=None) -> int:
             record.update(apgd_l1_loss_name=args.apgd_l1_loss)
     if args.ibp_eps is not None:
         ver = sum(int(predictor.verify_linf(images[i:i + args.batch_size], data.targets[i:i + args.batch_size],
-                                            args.ibp_eps)[0].sum()) for i in range(0, n, args.batch_size))
-        print(ibp_verified_line(args.ibp_eps, ver, n))
+                                            args.ibp_eps, args.ibp_method)[0].sum())
+                  for i in range(0, n, args.batch_size))
+        print(ibp_verified_line(args.ibp_eps, ver, n, args.ibp_method))
         record.update(ibp_eps=args.ibp_eps, ibp_verified=ver)
     if args.ibp_radius:
         m = n if args.ibp_count is None else max(1, min(n, args.ibp_count))
@@ -1751,17 +1798,20 @@ def predict_main(argv=None) -> int:
         for i in range(0, m, args.batch_size):
             j = min(m, i + args.batch_size)
             radii[i:j] = predictor.certified_radius_linf(images[i:j], data.targets[i:j], args.ibp_eps_max,
-                                                         args.ibp_search_steps)[0].cpu()
+                                                         args.ibp_search_steps, args.ibp_method)[0].cpu()
         cert = radii > 0
         r = radii[cert].double()
         median, mean = (float(r.quantile(0.5)), float(r.mean())) if r.numel() else (None, None)
         at = [int((cert & (radii >= R)).sum()) for R in args.ibp_radii]
-        print(ibp_radius_line(args.ibp_eps_max, args.ibp_search_steps, m, int(cert.sum()), median, mean))
+        print(ibp_radius_line(args.ibp_eps_max, args.ibp_search_steps, m, int(cert.sum()), median, mean,
+                              args.ibp_method))
         for R, c in zip(args.ibp_radii, at):
             print(f"Certified accuracy at radius {R:g}: {c}/{m} ({100.0 * c / m:.0f}%)")
         record.update(ibp_eps_max=args.ibp_eps_max, ibp_search_steps=args.ibp_search_steps, ibp_count=m,
                       ibp_certified=int(cert.sum()), ibp_median_radius=median, ibp_mean_radius=mean,
                       ibp_accuracy_at={f"{R:g}": c for R, c in zip(args.ibp_radii, at)})
+    if args.ibp_method != "ibp" and (args.ibp_eps is not None or args.ibp_radius):
+        record.update(ibp_method=args.ibp_method)
     if args.json_log:
         with open(args.json_log, "a") as f:
             f.write(json.dumps(record) + "\n")

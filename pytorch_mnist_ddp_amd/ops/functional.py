@@ -1696,7 +1696,259 @@ def ibp_head(param: torch.Tensor, part: torch.Tensor, labels: torch.Tensor, rec:
     return lb.view(-1, NCLS)
 
 
-SQUARE_PHILOX_DOMAIN = 0x53515231   # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
+CROWN_SPEC = 16                     # specification slots an image in crown_lambda / crown_fc (kernels.h CROWN_SPEC)
+CROWN_SLICES = 576                  # 16-column slices of crown_fc's bias partials (kernels.h CROWN_SLICES)
+CROWN_STRIPS = 7                    # strips of 4 input rows of crown_bwd (kernels.h CROWN_STRIPS)
+
+
+def relu_relax_reference(l: torch.Tensor, u: torch.Tensor):
+    """``(sL, sU, bU)`` of relu over [l, u]: sL z <= relu(z) <= sU z + bU.  l >= 0: (1, 1, 0); u <= 0: zeros; else
+    sU = u / (u - l), bU = -l u / (u - l) and sL = 1 where u > -l, else 0."""
+    pos = l >= 0
+    un = ~pos & ~(u <= 0)
+    one, zero, d = torch.ones_like(l), torch.zeros_like(l), u - l
+    return (torch.where(pos | (un & (u > -l)), one, zero), torch.where(pos, one, torch.where(un, u / d, zero)),
+            torch.where(un, (-l * u) / d, zero))
+
+
+def _windows(t: torch.Tensor) -> torch.Tensor:
+    """[M, 64, 24, 24] -> [M, 9216, 4]: each pool window's pixels in row-major order, windows in torch flatten order."""
+    M = t.shape[0]
+    return t.view(M, 64, 12, 2, 12, 2).permute(0, 1, 2, 4, 3, 5).reshape(M, NFLAT, 4)
+
+
+def _relaxed(A, sL, sU):
+    return torch.where(A > 0, A * sL, A * sU)
+
+
+def _relax_bias(A, bU):
+    return torch.where(A < 0, A * bU, torch.zeros_like(A))
+
+
+def crown_ibp_reference(net_or_params, x: torch.Tensor, labels: torch.Tensor, eps, dtype=torch.float32,
+                        lo: float | None = None, hi: float | None = None, record: dict | None = None) -> dict:
+    """CROWN-IBP (Zhang et al. 2020) of the Net over the box of ``ibp_reference``, in torch ops on any device - the
+    formulas of csrc/kernels/crown.hip stage by stage.  IBP bounds every hidden pre-activation; the ten margin rows
+    C_j = fc2.weight[y] - fc2.weight[j] then go backward through one linear relaxation a layer: outgoing coefficients
+    A+ sL + A- sU, the bias gains sum A- bU, an affine layer adds A b and gives A W, and at the input
+    lb_j = sum(A0+ xl + A0- xu) + bias.  The ReLU and the pool behind it are one relaxation a pooled unit, on the
+    window's pixel i* (first argmax of the lower bounds): below sL z_i*; above sU z_i* + bU when pixel i* dominates the
+    window (l2[i*] >= every other u2), else the constant U = max u2.
+
+    Stages: ``pl``, ``pu``, ``z1c``, ``z1r``, ``lb_ibp`` as ``ibp_reference``; the record ``sL``, ``sU``, ``bU`` [M, 9216]
+    and ``istar`` (int64 [M, 9216], 0 .. 3 row-major in the window); ``lam`` [M, 16, 128] (rows y and 10 .. 15 zero) and
+    ``fcb`` [M, 16] (the bias down to fc1's input); ``v`` [M, 10, 9216] and ``vb`` [M, 576, 10] (the pool's and conv2's
+    bias terms by 16-column slice); ``sp`` [M, 7, 10, 2] ((concretised sum, bias) of each strip of 4 input rows);
+    ``lb_crown``; ``lb`` = max(lb_crown, lb_ibp) (+inf at y); ``margin`` and ``certified``.  ``record``: the backward
+    pass runs from these ``sL``, ``sU``, ``bU``, ``istar`` instead of the ones computed here."""
+    import torch.nn.functional as F
+    M, dev = x.shape[0], x.device
+    y = labels.reshape(-1).long().to(dev)
+    P, xl, xu, pre1 = crown_box_reference(net_or_params, x, eps, dtype, lo, hi)
+    l, u = F.relu(pre1[0]), F.relu(pre1[1])
+    c, rad = F.conv2d((l + u) * 0.5, P["conv2.weight"], P["conv2.bias"]), F.conv2d((u - l) * 0.5, P["conv2.weight"].abs())
+    pl, pu = F.max_pool2d(F.relu(c - rad), 2).flatten(1), F.max_pool2d(F.relu(c + rad), 2).flatten(1)
+    l2w, u2w = _windows(c - rad), _windows(c + rad)
+    istar = l2w.argmax(dim=2)
+    ls, us, U = l2w.gather(2, istar[..., None])[..., 0], u2w.gather(2, istar[..., None])[..., 0], u2w.max(dim=2).values
+    dom = ((ls[..., None] >= u2w) | F.one_hot(istar, 4).bool()).all(dim=2)
+    sL, sU, bU = relu_relax_reference(ls, us)
+    zero = torch.zeros_like(sL)
+    sU, bU = torch.where(dom, sU, zero), torch.where(dom, bU, U)
+    sL, sU, bU = (torch.where(U <= 0, zero, t) for t in (sL, sU, bU))
+    out = {"pl": pl, "pu": pu, "sL": sL, "sU": sU, "bU": bU, "istar": istar}
+    if record is not None:
+        sL, sU, bU = (record[k].to(dev, dtype) for k in ("sL", "sU", "bU"))
+        istar = record["istar"].to(dev).long()
+    z1c, z1r = ibp_fc1_reference(net_or_params, pl, pu, dtype)
+    lb_ibp = ibp_head_reference(net_or_params, torch.stack((z1c, z1r), dim=1)[None], y, dtype)
+    lam, fcb = crown_lambda_reference(P, z1c, z1r, y)
+    v, vb = crown_fc_reference(P, lam, sL, sU, bU)
+    sp = crown_bwd_reference(P, xl, xu, pre1, v, istar)
+    lbc, lb = crown_head_reference(fcb, vb, sp, lb_ibp, y)
+    margin = lb.min(dim=1).values
+    out.update(z1c=z1c, z1r=z1r, lb_ibp=lb_ibp, lam=lam, fcb=fcb, v=v, vb=vb, sp=sp, lb_crown=lbc, lb=lb, margin=margin,
+               certified=margin > 0)
+    return out
+
+
+def _wave_sum128(t: torch.Tensor) -> torch.Tensor:
+    """The sum over the last axis (128) in a wave's order: (t_k + t_{k+64}), then the xor butterfly 32 .. 1."""
+    s = t[..., :64] + t[..., 64:]
+    idx = torch.arange(64, device=s.device)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[..., idx ^ o]
+    return s[..., 0]
+
+
+def crown_lambda_reference(P: dict, z1c, z1r, y):
+    """``crown_lambda``: ``(lam [M, 16, 128], fcb [M, 10])`` from the fc1 sums (before the bias) and the labels."""
+    M, dev = z1c.shape[0], z1c.device
+    W2f, b2f, b1f = P["fc2.weight"], P["fc2.bias"], P["fc1.bias"]
+    c3 = z1c + b1f
+    s3L, s3U, b3U = (t[:, None, :] for t in relu_relax_reference(c3 - z1r, c3 + z1r))
+    Cm = W2f[y][:, None, :] - W2f[None]
+    keep = torch.ones(M, NCLS, dtype=torch.bool, device=dev)
+    keep[torch.arange(M, device=dev), y] = False
+    lam = _relaxed(Cm, s3L, s3U) * keep[..., None]
+    fcb = (_wave_sum128(_relax_bias(Cm, b3U) + lam * b1f) + (b2f[y][:, None] - b2f[None, :])) * keep
+    return torch.cat([lam, torch.zeros(M, CROWN_SPEC - NCLS, NH, dtype=lam.dtype, device=dev)], dim=1), fcb
+
+
+def crown_fc_reference(P: dict, lam, sL, sU, bU):
+    """``crown_fc``: ``(v [M, 10, 9216], vb [M, 576, 10])`` from ``lam`` and the pooled record."""
+    M = lam.shape[0]
+    Ap = lam[:, :NCLS] @ P["fc1.weight"]
+    v = _relaxed(Ap, sL[:, None], sU[:, None])
+    tb = _relax_bias(Ap, bU[:, None]) + v * P["conv2.bias"].repeat_interleave(144)
+    return v, tb.view(M, NCLS, CROWN_SLICES, 16).sum(dim=3).transpose(1, 2)
+
+
+def crown_bwd_reference(P: dict, xl, xu, pre1, v, istar):
+    """``crown_bwd``: ``sp`` [M, 7, 10, 2] from the box ``xl``, ``xu`` [M, 1, 28, 28], the conv1 pre-activation bounds
+    ``pre1`` = (l1, u1), the rows ``v`` and each window's ``istar``, in gather form as the kernel runs it."""
+    import torch.nn.functional as F
+    M = xl.shape[0]
+    Vd = (v[..., None] * F.one_hot(istar, 4)[:, None]).view(M * NCLS, 64, 12, 12, 2, 2)
+    Vd = Vd.permute(0, 1, 2, 4, 3, 5).reshape(M * NCLS, 64, 24, 24)
+    A1 = F.conv2d(F.pad(Vd, (2, 2, 2, 2)), P["conv2.weight"].transpose(0, 1).flip(2, 3)).view(M, NCLS, 32, 26, 26)
+    s1L, s1U, b1U = (t[:, None] for t in relu_relax_reference(*pre1))
+    A1r = _relaxed(A1, s1L, s1U)
+    t1 = _relax_bias(A1, b1U) + A1r * P["conv1.bias"].view(1, 1, 32, 1, 1)
+    A0 = F.conv2d(F.pad(A1r.view(M * NCLS, 32, 26, 26), (2, 2, 2, 2)),
+                  P["conv1.weight"].transpose(0, 1).flip(2, 3)).view(M, NCLS, 28, 28)
+    t0 = torch.where(A0 > 0, A0 * xl, A0 * xu)
+    rows1 = F.pad(t1.sum(dim=(2, 4)), (0, 2))                                    # [M, 10, 28]: conv1 rows, by owner
+    return torch.stack((t0.sum(dim=3).view(M, NCLS, CROWN_STRIPS, 4).sum(dim=3),
+                        rows1.view(M, NCLS, CROWN_STRIPS, 4).sum(dim=3)), dim=3).transpose(1, 2).contiguous()
+
+
+def crown_head_reference(fcb, vb, sp, lb_ibp, y):
+    """``crown_head``: ``(lb_crown, lb)`` [M, 10] from the partials; +inf at the label."""
+    lbc = fcb + sp.sum(dim=(1, 3)) + vb.sum(dim=1)
+    lbc[torch.arange(lbc.shape[0], device=lbc.device), y] = float("inf")
+    return lbc, torch.maximum(lbc, lb_ibp)
+
+
+def crown_box_reference(net_or_params, x, eps, dtype=torch.float32, lo=None, hi=None):
+    """``(P, xl, xu, (l1, u1))``: the parameters, the clipped box [M, 1, 28, 28] and conv1's pre-activation bounds, as
+    ``crown_bwd`` recomputes them."""
+    import torch.nn.functional as F
+    P, std, lo, hi = _ibp_setup(net_or_params, dtype, lo, hi)
+    M = x.shape[0]
+    x = x.reshape(M, 784).to(dtype)
+    e = (torch.as_tensor(eps, dtype=dtype, device=x.device).expand(M) / torch.tensor(std, dtype=dtype, device=x.device))[:, None]
+    xl, xu = torch.clamp(x - e, min=lo).view(M, 1, 28, 28), torch.clamp(x + e, max=hi).view(M, 1, 28, 28)
+    c = F.conv2d((xl + xu) * 0.5, P["conv1.weight"], P["conv1.bias"])
+    rad = F.conv2d((xu - xl) * 0.5, P["conv1.weight"].abs())
+    return P, xl, xu, (c - rad, c + rad)
+
+
+def _crown_rec(rec4: torch.Tensor) -> dict:
+    """The kernels' record [M, 9216, 4] (sL, sU, bU, bits of i*) as the reference's fields."""
+    return {"sL": rec4[..., 0], "sU": rec4[..., 1], "bU": rec4[..., 2],
+            "istar": rec4[..., 3].contiguous().view(torch.int32).long()}
+
+
+def crown_relax(param: torch.Tensor, x: torch.Tensor, rec: torch.Tensor, pl: torch.Tensor | None = None,
+                pu: torch.Tensor | None = None, relax: torch.Tensor | None = None, lo: float | None = None,
+                hi: float | None = None, M: int | None = None):
+    """One launch of ``crown_relax`` (csrc/kernels/crown.hip): ``(pl, pu, relax)``: ``ibp_trunk``'s bounds and the
+    relaxation record float32 [>= M, 9216, 4] = (sL, sU, bU, bits of i*) of every pooled unit.  Arguments as
+    ``ibp_trunk``.  Nothing past M is touched."""
+    M = int(x.shape[0] if M is None else M)
+    _ibp_param("crown_relax", param, M)
+    dev = param.device
+    _f32_rows("crown_relax", "x", x, M, dev, at_least="M")
+    _df_vec("crown_relax", "rec", rec, torch.float32, 4 * M, dev, "4 M")
+    pl, pu = (_ibp_buf("crown_relax", k, q, M * NFLAT, dev) for k, q in (("pl", pl), ("pu", pu)))
+    relax = _ibp_buf("crown_relax", "relax", relax, M * NFLAT * 4, dev)
+    _, std, lo, hi = _ibp_setup({}, torch.float32, lo, hi)
+    if not lo < hi or pl.data_ptr() == pu.data_ptr():
+        raise ValueError("crown_relax: need lo < hi and two bound buffers")
+    p = native.ptr
+    _C().crown_relax(p(param), p(x), p(rec), p(pl), p(pu), p(relax), std, lo, hi, M, _s())
+    return pl.view(-1, NFLAT), pu.view(-1, NFLAT), relax.view(-1, NFLAT, 4)
+
+
+def crown_lambda(param: torch.Tensor, part: torch.Tensor, labels: torch.Tensor, lam: torch.Tensor | None = None,
+                 fcb: torch.Tensor | None = None, M: int | None = None):
+    """One launch of ``crown_lambda``: ``(lam, fcb)`` from the slab ``part`` of ``ibp_fc1`` and the int32 ``labels``:
+    the relaxed margin rows float32 [>= M, 16, 128] and [>= M, 2, 16] = (the bias down to fc1's input, lb_ibp)."""
+    M = int(labels.numel() if M is None else M)
+    _ibp_param("crown_lambda", param, M)
+    dev = param.device
+    _df_vec("crown_lambda", "part", part, torch.float32, IBP_SPLITS * M * 2 * NH, dev, "IBP_SPLITS * M * 256")
+    _df_vec("crown_lambda", "labels", labels, torch.int32, M, dev, "M")
+    lam = _ibp_buf("crown_lambda", "lam", lam, M * CROWN_SPEC * NH, dev)
+    fcb = _ibp_buf("crown_lambda", "fcb", fcb, M * 2 * CROWN_SPEC, dev)
+    p = native.ptr
+    _C().crown_lambda(p(param), p(part), p(labels), p(lam), p(fcb), M, _s())
+    return lam.view(-1, CROWN_SPEC, NH), fcb.view(-1, 2, CROWN_SPEC)
+
+
+def crown_fc(param: torch.Tensor, relax: torch.Tensor, lam: torch.Tensor, v: torch.Tensor | None = None,
+             vb: torch.Tensor | None = None, M: int | None = None):
+    """One launch of ``crown_fc``: ``(v, vb)`` = lam fc1.weight through the pool relaxation ``relax``: float32
+    [>= M, 10, 9216] and the bias partials [>= M, 576, 16] (slots 10 .. 15 are not written)."""
+    M = int(lam.shape[0] if M is None else M)
+    _ibp_param("crown_fc", param, M)
+    dev = param.device
+    _df_vec("crown_fc", "relax", relax, torch.float32, M * NFLAT * 4, dev, "M * 9216 * 4")
+    _df_vec("crown_fc", "lam", lam, torch.float32, M * CROWN_SPEC * NH, dev, "M * 2048")
+    v = _ibp_buf("crown_fc", "v", v, M * NCLS * NFLAT, dev)
+    vb = _ibp_buf("crown_fc", "vb", vb, M * CROWN_SLICES * CROWN_SPEC, dev)
+    p = native.ptr
+    _C().crown_fc(p(param), p(relax), p(lam), p(v), p(vb), M, _s())
+    return v.view(-1, NCLS, NFLAT), vb.view(-1, CROWN_SLICES, CROWN_SPEC)
+
+
+def crown_bwd(param: torch.Tensor, x: torch.Tensor, rec: torch.Tensor, relax: torch.Tensor, v: torch.Tensor,
+              labels: torch.Tensor, sp: torch.Tensor | None = None, lo: float | None = None, hi: float | None = None,
+              M: int | None = None) -> torch.Tensor:
+    """One launch of ``crown_bwd``: ``sp`` float32 [>= M, 7, 10, 2], each strip's (concretised sum, bias) of the rows
+    ``v`` taken back through conv2, the conv1 relaxation (from the box of ``x`` and ``rec[i, 0]``) and conv1."""
+    M = int(x.shape[0] if M is None else M)
+    _ibp_param("crown_bwd", param, M)
+    dev = param.device
+    _f32_rows("crown_bwd", "x", x, M, dev, at_least="M")
+    _df_vec("crown_bwd", "rec", rec, torch.float32, 4 * M, dev, "4 M")
+    _df_vec("crown_bwd", "relax", relax, torch.float32, M * NFLAT * 4, dev, "M * 9216 * 4")
+    _df_vec("crown_bwd", "v", v, torch.float32, M * NCLS * NFLAT, dev, "M * 92160")
+    _df_vec("crown_bwd", "labels", labels, torch.int32, M, dev, "M")
+    sp = _ibp_buf("crown_bwd", "sp", sp, M * CROWN_STRIPS * NCLS * 2, dev)
+    _, std, lo, hi = _ibp_setup({}, torch.float32, lo, hi)
+    if not lo < hi:
+        raise ValueError("crown_bwd: need lo < hi")
+    p = native.ptr
+    _C().crown_bwd(p(param), p(x), p(rec), p(relax), p(v), p(labels), p(sp), std, lo, hi, M, _s())
+    return sp.view(-1, CROWN_STRIPS, NCLS, 2)
+
+
+def crown_head(fcb: torch.Tensor, vb: torch.Tensor, sp: torch.Tensor, labels: torch.Tensor, rec: torch.Tensor,
+               lb: torch.Tensor | None = None, lbc: torch.Tensor | None = None, search: bool = False,
+               M: int | None = None) -> torch.Tensor:
+    """One launch of ``crown_head``: ``lb`` float32 [>= M, 10] = max(lb_crown, lb_ibp) from the partials of the other
+    kernels, +inf at the label (``lbc``, when given: lb_crown).  ``search``: the records are bisected as
+    ``ibp_search_reference`` does from this launch's ``lb``."""
+    M = int(labels.numel() if M is None else M)
+    dev = fcb.device
+    if dev.type != "cuda" or M < 1 or M > IBP_MAX_B:
+        raise ValueError(f"crown_head: needs GPU buffers and M in [1, {IBP_MAX_B}]")
+    _df_vec("crown_head", "fcb", fcb, torch.float32, M * 2 * CROWN_SPEC, dev, "32 M")
+    _df_vec("crown_head", "vb", vb, torch.float32, M * CROWN_SLICES * CROWN_SPEC, dev, "M * 9216")
+    _df_vec("crown_head", "sp", sp, torch.float32, M * CROWN_STRIPS * NCLS * 2, dev, "140 M")
+    _df_vec("crown_head", "labels", labels, torch.int32, M, dev, "M")
+    _df_vec("crown_head", "rec", rec, torch.float32, 4 * M, dev, "4 M")
+    lb = _ibp_buf("crown_head", "lb", lb, M * NCLS, dev)
+    if lbc is not None:
+        _df_vec("crown_head", "lbc", lbc, torch.float32, M * NCLS, dev, "10 M")
+    p = native.ptr
+    _C().crown_head(p(fcb), p(vb), p(sp), p(labels), 0 if lbc is None else p(lbc), p(lb), p(rec), bool(search), M, _s())
+    return lb.view(-1, NCLS)
+
+
+SQUARE_PHILOX_DOMAIN = 0x53515231  # Philox counter word 1 of square_init / square_step (csrc/include/kernels.h)
 SQUARE_MAX_M = 1 << 20             # most images one square_init / square_step launch takes (kernels.h INPUT_GRAD_MAX_B)
 SQUARE_MAX_SIDE = 27
 # columns of the per-image record, int32 [M, 4] (kernels.h SquareStepArgs); column 0 holds the bits of a float32
