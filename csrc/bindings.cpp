@@ -49,6 +49,7 @@ void mnist::preload_all_kernels() {
   preload_fab();
   preload_apgd_l1();
   preload_cw();
+  preload_ead();
   preload_ibp();
   preload_crown();
 }
@@ -638,6 +639,28 @@ PYBIND11_MODULE(_C, m) {
      py::arg("last"), py::arg("M"), py::arg("stream"),
      "one Carlini-Wagner L2 iteration per image: success test and nearest success, Adam step in tanh space (or, "
      "search_end, the bisection of c and the restart from the clean image); fstate [M][4] = c, c_lo, c_hi, d_best; "
+     "istate [M][4] = succ, found_search, iters, spare");
+
+  // ---------------- EAD (elastic-net L1 attack) ----------------
+  m.attr("EAD_RULE_EN") = (int)EAD_RULE_EN;
+  m.attr("EAD_RULE_L1") = (int)EAD_RULE_L1;
+  m.def("ead_step", [](uintptr_t dx, uintptr_t loss_rows, uintptr_t x0, uintptr_t y, uintptr_t x, uintptr_t x_best,
+                       uintptr_t fstate, uintptr_t istate, float sign, float kappa, float c_init, float lr_k,
+                       float zeta_k, float beta, float beta_n, float std, float dist_scale, float lo, float hi,
+                       int search, int rule, bool first, bool search_end, bool last, int M, uintptr_t stream) {
+    EadStepArgs a{P<const float>(dx), P<const float>(loss_rows), P<const float>(x0), P<float>(y), P<float>(x),
+                  P<float>(x_best), P<float>(fstate), P<int32_t>(istate), sign, kappa, c_init, lr_k, zeta_k, beta,
+                  beta_n, std, dist_scale, lo, hi, search, rule, first ? 1 : 0, search_end ? 1 : 0, last ? 1 : 0};
+    launch_ead_step(a, M, S(stream));
+    check_launch();
+  }, py::arg("dx"), py::arg("loss_rows"), py::arg("x0"), py::arg("y"), py::arg("x"), py::arg("x_best"),
+     py::arg("fstate"), py::arg("istate"), py::arg("sign"), py::arg("kappa"), py::arg("c_init"), py::arg("lr_k"),
+     py::arg("zeta_k"), py::arg("beta"), py::arg("beta_n"), py::arg("std"), py::arg("dist_scale"), py::arg("lo"),
+     py::arg("hi"), py::arg("search"), py::arg("rule"), py::arg("first"), py::arg("search_end"), py::arg("last"),
+     py::arg("M"), py::arg("stream"),
+     "one EAD (elastic-net) iteration per image: success test and nearest success at the shrunk point x, ISTA step "
+     "with shrinkage around x0 and FISTA momentum from the slack point y (or, search_end, the bisection of c and the "
+     "restart from the clean image); loss_rows [2 M] = margins at y then at x; fstate [M][4] = c, c_lo, c_hi, d_best; "
      "istate [M][4] = succ, found_search, iters, spare");
 
   // ---------------- Interval bound propagation (L-inf certificates) ----------------

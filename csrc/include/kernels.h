@@ -578,6 +578,42 @@ struct CwStepArgs {
 // M in [1, INPUT_GRAD_MAX_B], sign +-1, kappa >= 0, lr > 0, c_init > 0 when first, not first and last at once
 void launch_cw_step(const CwStepArgs& a, int M, hipStream_t s);
 
+// ---------------- EAD, the elastic-net L1 attack (ead.hip; Chen, Sharma, Zhang, Yi & Hsieh 2018) ----------------
+// One iteration's per-image update in one launch, one workgroup per image, fp32, no atomics.  Each image has two
+// points: the slack point y, where the gradient is taken, and the shrunk point x, the candidate adversarial example.
+// The gradient chain (GradChain loss "cw") ran over 2 M rows - [0, M) the y rows, [M, 2 M) the x rows - so
+// loss_rows[i] is the margin at y, loss_rows[M + i] the margin at x, and dx[i] the gradient at y.  The launch judges
+// x (success when sign * margin > 0 and >= kappa; the nearest success by the decision rule's distance is kept in
+// d_best, x_best, found_search), then takes the ISTA step from y with the three-way shrinkage around x0 and the FISTA
+// momentum; a `search_end` launch instead bisects c as cw_step does and puts x = y = x0.  The exact form and the NaN
+// rules are in ead.hip.  The records are cw_step's: fstate[i] = {c, c_lo, c_hi, d_best}, istate[i] = {succ,
+// found_search, iters, spare}; d_best is the rule's distance in pixel units (EN: |d|_2^2 + beta |d|_1; L1: |d|_1).
+// first: reads no record and no x_best, writes all of them; the caller has set x = y = x0.  last: only the best point
+// and the records are brought up to date.  Rows and records past M are untouched.
+enum EadRule : int { EAD_RULE_EN = 0, EAD_RULE_L1 = 1 };
+struct EadStepArgs {
+  const float* dx;            // fp32 [M][784] d margin / d input at the slack point y
+  const float* loss_rows;     // [2 M] the CW margin at y ([i]) and at x ([M + i])
+  const float* x0;            // fp32 [M][784] the clean normalised image, inside [lo, hi]
+  float* y;                   // fp32 [M][784] the slack point (rows [0, M) of the next chain run)
+  float* x;                   // fp32 [M][784] the shrunk point (rows [M, 2 M) of the next chain run)
+  float* x_best;              // fp32 [M][784] the nearest success so far (the clean image until there is one)
+  float* fstate;              // [M][4]
+  int32_t* istate;            // [M][4]
+  float sign;                 // +1 untargeted (leave labels), -1 targeted (reach labels)
+  float kappa, c_init;        // confidence >= 0, the first c > 0 (read by a first launch)
+  float lr_k, zeta_k;         // lr sqrt(1 - k / steps) and k / (k + 3) of this launch's update index k
+  float beta, beta_n;         // the L1 weight in pixel units, and beta / std: the shrinkage threshold
+  float std, dist_scale;      // MNIST_STD and its square: pixel units of |d|_1 and |d|_2^2
+  float lo, hi;               // valid range, normalised units
+  int search;                 // the index of the current search step
+  int rule;                   // EadRule: the distance the best point is chosen by
+  int first, search_end, last;   // flags: launch 0 / the launch after a search step's last update / the very last
+};
+// M in [1, INPUT_GRAD_MAX_B / 2], sign +-1, kappa >= 0, lr_k >= 0, zeta_k in [0, 1), beta >= 0, c_init > 0 when
+// first, not first and last at once
+void launch_ead_step(const EadStepArgs& a, int M, hipStream_t s);
+
 // ---------------- Interval bound propagation, L-inf (ibp.hip; Gowal et al. 2018, Mirman et al. 2018) ----------------
 // Sound bounds of the fp32 net's logit differences over the box |x - x0|_inf <= eps (pixel units) inside the valid
 // pixel range, in centre / radius form, fp32 on v_mfma_f32_16x16x4_f32: one round is ibp_trunk -> ibp_fc1 -> ibp_head
@@ -798,6 +834,7 @@ void preload_square_l2();
 void preload_fab();
 void preload_apgd_l1();
 void preload_cw();
+void preload_ead();
 void preload_ibp();
 void preload_crown();
 void preload_all_kernels();  // every one of the above, in this order (bindings.cpp: the one list)

@@ -30,11 +30,11 @@ OUTPUT = os.path.join(PKG_DIR, "_C" + EXT_SUFFIX)
 #   "rw": race-window widening, 0..RACE_WIDEN_US us random sleeps before every kernel's first global
 #         read and every stream hand-off signal (device_utils.h; MNIST_AMD_RACE_WIDEN=1 loads it)
 RACE_WIDEN_US = 20
-# per-file compiler flags.  fab.hip, square.hip (the L2 kernels), apgd_l1.hip, cw.hip: no packed fp32 instructions -
+# per-file compiler flags.  fab.hip, square.hip (the L2 kernels), apgd_l1.hip, cw.hip, ead.hip: no packed fp32 instructions -
 # every operation of their fixed-order sums is a scalar one, rounded on its own, whatever the vectorizer would pair up
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"fab.hip": _NO_PACKED_FP32, "square.hip": _NO_PACKED_FP32, "apgd_l1.hip": _NO_PACKED_FP32,
-              "cw.hip": _NO_PACKED_FP32}
+              "cw.hip": _NO_PACKED_FP32, "ead.hip": _NO_PACKED_FP32}
 VARIANTS = {
     "": (os.path.join(ROOT, "build", "obj"), OUTPUT, []),
     "tl": (os.path.join(ROOT, "build", "obj_tl"), os.path.join(PKG_DIR, "_C_tl" + EXT_SUFFIX), ["-DMNIST_TIMELINE"]),

@@ -65,6 +65,7 @@ from .ops.chain import chain_loss
 from .ops.functional import (APGD_L1_LOSS_BEST, APGD_LOSS_BEST, CW_C, CW_D_BEST, CW_FOUND_SEARCH, DF_CLASSES, FAB_NORMS, PGD_L2_TINY, SQUARE_DONE,
                              SQUARE_QUERIES, apgd_checkpoints, apgd_l1_checkpoints, apgd_l1_step_reference,
                              apgd_step_reference, attr_path_reference, attr_reduce_reference, cw_step_reference,
+                             ead_step_reference,
                              deepfool_step_reference, fab_step_reference, margin_loss_reference, pgd_l2_step_reference, square_init_reference, square_l2_init_reference,
                              square_l2_step_reference, square_norm, square_sides, square_sides_l2, square_state_margin,
                              square_step_reference)
@@ -344,6 +345,44 @@ def reference_carlini_wagner(net: Net, x0: torch.Tensor, labels: torch.Tensor, s
                                               hi, first=k == 0 and j == 0, search_end=end and not final,
                                               last=end and final)
             outs.append((state[4], state[5][:, CW_D_BEST], state[6][:, CW_FOUND_SEARCH], state[5][:, CW_C]))
+    return tuple(torch.cat(q) for q in zip(*outs))
+
+
+def reference_elastic_net(net: Net, x0: torch.Tensor, labels: torch.Tensor, search_steps: int, steps: int, lr: float,
+                          c_init: float, beta: float, kappa: float, rule: str, sign: float, lo: float, hi: float):
+    """``ops.ead.fused_elastic_net`` in torch float32 on any device: the same ``search_steps * (steps + 1)`` rounds -
+    the CW margin of ``labels`` at the slack rows y and at the shrunk rows x in one forward (``margin_loss_reference``
+    on the log-probs), its gradient at the y rows by autograd over ``Net.forward_reference`` in eval mode (no dropout;
+    the net's mode is restored afterwards), then ``ead_step_reference`` with the same ``first`` / ``search_end`` /
+    ``last`` flags.  ``x0``: float32 [B, 784] normalised images; same return: ``(x_adv [B, 784], d_best [B],
+    found_search int32 [B], c [B])``.  The images run in chunks of ``_REF_ROWS`` / 2.  The CPU / fp32 path of
+    ``Predictor.elastic_net`` and the reference of its GPU tests."""
+    search_steps, steps = int(search_steps), int(steps)
+    if search_steps < 1 or steps < 1:
+        raise ValueError("reference_elastic_net: search_steps and steps must be at least 1")
+    B, dev = x0.shape[0], x0.device
+    x0 = x0.detach().reshape(B, 784).to(torch.float32)
+    y = labels.reshape(B).long().to(dev)
+    outs, mc = [], _REF_ROWS // 2
+    with _eval_mode(net):
+        for i0 in range(0, B, mc):
+            c0, yc = x0[i0:i0 + mc], y[i0:i0 + mc]
+            m = c0.shape[0]
+            y2 = torch.cat((yc, yc))
+            state = (c0.clone(), c0.clone(), None, None, None)         # y, x, x_best, fstate, istate
+            for k in range(search_steps):
+                final = k == search_steps - 1
+                for j in range(steps + 1):
+                    rows = torch.cat((state[0], state[1])).requires_grad_()
+                    with torch.enable_grad():
+                        lp = net.forward_reference(rows.view(2 * m, 1, 28, 28))
+                        g, = torch.autograd.grad(margin_loss_reference(lp[:m], yc, "cw").sum(), rows)
+                    margin = margin_loss_reference(lp.detach(), y2, "cw")
+                    end = j == steps
+                    state = ead_step_reference(g[:m], margin, c0, *state, sign, kappa, lr, c_init, beta,
+                                               min(j, steps - 1), steps, k, lo, hi, rule, first=k == 0 and j == 0,
+                                               search_end=end and not final, last=end and final)
+            outs.append((state[2], state[3][:, CW_D_BEST], state[4][:, CW_FOUND_SEARCH], state[3][:, CW_C]))
     return tuple(torch.cat(q) for q in zip(*outs))
 
 
@@ -1061,6 +1100,64 @@ class Predictor:
         hit = lp.argmax(dim=1) == labels
         return x_adv, d_best.sqrt() * MNIST_STD, lp, hit if targeted else ~hit
 
+    def elastic_net(self, x: torch.Tensor, labels: torch.Tensor | None = None, search_steps: int = 6,
+                    steps: int = 100, lr: float = 0.01, c_init: float = 1.0, beta: float = 0.01, kappa: float = 0.0,
+                    decision_rule: str = "en", targeted: bool = False):
+        """(x_adv, radii, log_probs, found): minimum-L1 adversarial examples of ``x`` by EAD, the elastic-net attack of
+        Chen, Sharma, Zhang, Yi & Hsieh (AAAI 2018), in ``fab``'s conventions.  ``x_adv``: float32 [B,1,28,28] in
+        NORMALISED units, inside the valid pixel range; ``radii``: float32 [B], the L1 norm of ``x_adv - x`` in pixel
+        units on the [0, 1] scale (whatever ``decision_rule``), +inf where no iterate was a success (there ``x_adv``
+        is the clean image); ``log_probs``: the predictor's own float32 [B,10] forward of ``x_adv``; ``found``: bool
+        [B], whether that forward no longer gives ``labels`` (``targeted``: gives them).  An image already
+        misclassified on entry keeps ``x_adv = x``, radius 0 and is found.
+
+        ``labels`` ([B] integers): the class each image is to leave, or the class predicted on the clean input when
+        None; ``targeted`` (``labels`` required): the class each image is to reach.  The attack minimises c *
+        max(``kappa`` - margin, 0) + |x_adv - x|_2^2 + ``beta`` |x_adv - x|_1 (pixel units) by ISTA - a gradient step
+        of size ``lr`` sqrt(1 - k / ``steps``) on the smooth part from the slack point, then the shrinkage that puts
+        every pixel within ``beta`` of the clean one back on it and pulls the others ``beta`` closer - with FISTA
+        momentum k / (k + 3); margin = max_{j != y} z_j - z_y on the logits (``targeted``: its negative).
+        ``search_steps`` times ``steps`` updates from the clean image, c starting at ``c_init``, then bisected per
+        image as ``carlini_wagner`` does.  Of all shrunk points that were a success the one nearest by
+        ``decision_rule`` is returned: "en", the elastic-net distance |d|_2^2 + ``beta`` |d|_1, or "l1".  Differences
+        from the authors' code: no ``abort_early``, success is read from the margin the attack's own forward
+        computed.  Inference semantics as ``input_gradient``.  GPU with ``dtype="bf16"``: the native loop
+        ``ops.ead.fused_elastic_net``; CPU, or ``dtype="fp32"``: ``reference_elastic_net``."""
+        B = self._check_input(x)
+        for name, val in (("search_steps", search_steps), ("steps", steps)):
+            if isinstance(val, bool) or val != int(val) or val < 1:
+                raise ValueError(f"elastic_net: {name} must be a positive integer, got {val}")
+        if not lr > 0:
+            raise ValueError(f"elastic_net: lr must be > 0, got {lr}")
+        if not c_init > 0:
+            raise ValueError(f"elastic_net: c_init must be > 0, got {c_init}")
+        if not beta >= 0:
+            raise ValueError(f"elastic_net: beta must be >= 0, got {beta}")
+        if not kappa >= 0:
+            raise ValueError(f"elastic_net: kappa must be >= 0, got {kappa}")
+        if decision_rule not in ("en", "l1"):
+            raise ValueError(f'elastic_net: decision_rule must be "en" or "l1", got {decision_rule!r}')
+        if targeted and labels is None:
+            raise ValueError("elastic_net: a targeted attack needs labels (the target classes)")
+        x0 = _rows_f32(x, B, self.device)
+        if labels is None:
+            labels = self._forward(x0.view(B, 1, 28, 28))[1]
+        else:
+            labels = self._labels("elastic_net", labels, B, check_range=True)
+        if self.native:
+            from .ops.ead import fused_elastic_net as attack
+        else:
+            attack = reference_elastic_net
+        x_adv, _, found_search, _ = attack(self.net, x0, labels, int(search_steps), int(steps), float(lr),
+                                           float(c_init), float(beta), float(kappa), decision_rule,
+                                           -1 if targeted else 1, PIXEL_LO, PIXEL_HI)
+        radii = (x_adv - x0).abs().sum(dim=1) * MNIST_STD
+        radii = torch.where(found_search > 0, radii, torch.full_like(radii, float("inf")))
+        x_adv = x_adv.view(B, 1, 28, 28)
+        lp = self._forward(x_adv)[0]
+        hit = lp.argmax(dim=1) == labels
+        return x_adv, radii, lp, hit if targeted else ~hit
+
     # ------------------------------------------------------------------ L-inf certificates (IBP)
     def _ibp_input(self, name: str, x: torch.Tensor, labels):
         B = self._check_input(x)
@@ -1478,6 +1575,25 @@ def build_predict_parser() -> argparse.ArgumentParser:
                     help='attack the first M images of the split (default: all)')
     ap.add_argument('--cw-radii', type=_radii, default=(), metavar='R1,R2,...',
                     help='L2 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
+    ap.add_argument('--ead', action='store_true', default=False,
+                    help='also report the minimum L1 adversarial radius of the images against their true labels by '
+                         'EAD, the elastic-net attack (untargeted): how many are found, the median and mean L1 radius '
+                         'in pixel units (default: off)')
+    ap.add_argument('--ead-search-steps', type=int, default=6, metavar='S',
+                    help='bisection steps of the trade-off constant c per image (default: 6)')
+    ap.add_argument('--ead-steps', type=int, default=100, metavar='N', help='ISTA updates per search step (default: 100)')
+    ap.add_argument('--ead-lr', type=float, default=0.01, metavar='LR', help='the first step size (default: 0.01)')
+    ap.add_argument('--ead-c', type=float, default=1.0, metavar='C', help='the first trade-off constant (default: 1)')
+    ap.add_argument('--ead-beta', type=float, default=0.01, metavar='B',
+                    help='weight of the L1 term and shrinkage threshold, pixel units (default: 0.01)')
+    ap.add_argument('--ead-kappa', type=float, default=0.0, metavar='K',
+                    help='confidence: the margin a success must reach (default: 0)')
+    ap.add_argument('--ead-rule', choices=('en', 'l1'), default='en',
+                    help='the distance the best point is chosen by: elastic net or L1 (default: en)')
+    ap.add_argument('--ead-count', type=int, default=None, metavar='M',
+                    help='attack the first M images of the split (default: all)')
+    ap.add_argument('--ead-radii', type=_radii, default=(), metavar='R1,R2,...',
+                    help='L1 radii, in pixel units, at which accuracy is read off the per-image radii (default: none)')
     ap.add_argument('--ibp-eps', type=float, default=None, metavar='E',
                     help='also report how many images interval bound propagation certifies to keep their true label '
                          'within L-inf radius E, in pixel units (default: off)')
@@ -1584,6 +1700,13 @@ def cw_line(search_steps: int, steps: int, m: int, found: int, median, mean) -> 
     """The ``CW set`` line of ``mnist_predict.py --cw``, in the number formats of ``minimum_norm_line``."""
     fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
     return (f"CW set (L2, search={search_steps}, steps={steps}): "
+            f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
+
+
+def ead_line(rule: str, search_steps: int, steps: int, m: int, found: int, median, mean) -> str:
+    """The ``EAD set`` line of ``mnist_predict.py --ead``, in the number formats of ``minimum_norm_line``."""
+    fmt = lambda v: "n/a" if v is None else f"{v:.4f}"   # noqa: E731
+    return (f"EAD set (L1, rule={rule}, search={search_steps}, steps={steps}): "
             f"Found: {found}/{m} ({100.0 * found / m:.0f}%), median radius: {fmt(median)}, mean radius: {fmt(mean)}")
 
 
@@ -1741,6 +1864,26 @@ def predict_main(argv=None) -> int:
                       cw_kappa=args.cw_kappa, cw_count=m, cw_found=stats[0], cw_median_radius=stats[1],
                       cw_mean_radius=stats[2],
                       cw_accuracy_at={f"{r:g}": c for r, c in zip(args.cw_radii, stats[3])})
+    if args.ead:
+        m = n if args.ead_count is None else max(1, min(n, args.ead_count))
+        found = torch.empty(m, dtype=torch.bool)
+        clean = torch.empty(m, dtype=torch.bool)
+        radii = torch.empty(m, dtype=torch.float32)
+        for i in range(0, m, args.batch_size):
+            j = min(m, i + args.batch_size)
+            yb = data.targets[i:j]
+            clean[i:j] = (predictor.predict(images[i:j]).cpu() == yb.long().cpu())
+            _, r, _, fnd = predictor.elastic_net(images[i:j], yb, args.ead_search_steps, args.ead_steps, args.ead_lr,
+                                                 args.ead_c, args.ead_beta, args.ead_kappa, args.ead_rule)
+            radii[i:j], found[i:j] = r.cpu(), fnd.cpu()
+        stats = minimum_norm_stats(radii, found, clean, args.ead_radii)
+        print(ead_line(args.ead_rule, args.ead_search_steps, args.ead_steps, m, *stats[:3]))
+        for r, c in zip(args.ead_radii, stats[3]):
+            print(accuracy_at_radius_line(r, c, m))
+        record.update(ead_search_steps=args.ead_search_steps, ead_steps=args.ead_steps, ead_lr=args.ead_lr,
+                      ead_c=args.ead_c, ead_beta=args.ead_beta, ead_kappa=args.ead_kappa, ead_rule=args.ead_rule,
+                      ead_count=m, ead_found=stats[0], ead_median_radius=stats[1], ead_mean_radius=stats[2],
+                      ead_accuracy_at={f"{r:g}": c for r, c in zip(args.ead_radii, stats[3])})
     if args.apgd_eps is not None:
         gen = torch.Generator().manual_seed(args.apgd_seed) if args.apgd_restarts > 1 else None
         ap_loss, ap_correct, _ = predictor.robust_evaluate_apgd(images, data.targets, args.apgd_eps, args.apgd_steps,

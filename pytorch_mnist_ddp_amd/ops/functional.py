@@ -1534,6 +1534,173 @@ def cw_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, w: torc
                  bool(first), bool(search_end), bool(last), M, _s())
 
 
+EAD_RULES = {"en": 0, "l1": 1}      # the distance the best point is chosen by (kernels.h EadRule)
+EAD_MAX_M = CW_MAX_M // 2           # most images one ead_step launch takes: the chain runs two rows an image
+
+
+def ead_schedule(k: int, steps: int, lr: float) -> tuple:
+    """``(lr_k, zeta_k)`` of update ``k`` in [0, steps) of an EAD search step: lr sqrt(1 - k / steps), the authors'
+    square-root decay, and the FISTA momentum k / (k + 3); computed in float64, rounded to float32 once."""
+    import numpy as np
+    k, steps = int(k), int(steps)
+    if steps < 1 or not 0 <= k < steps:
+        raise ValueError("ead_schedule: need steps >= 1 and k in [0, steps)")
+    return float(np.float32(float(lr) * (1.0 - k / steps) ** 0.5)), float(np.float32(k / (k + 3.0)))
+
+
+def ead_beta_n(beta: float) -> float:
+    """beta / MNIST_STD: the shrinkage threshold in normalised units; float64, rounded to float32 once."""
+    import numpy as np
+    from ..data.datasets import MNIST_STD
+    return float(np.float32(float(beta) / MNIST_STD))
+
+
+def _row_tree_sum(t: torch.Tensor) -> torch.Tensor:
+    """The sum over a [M, 784] row in the row kernels' order (row_ops.h): each thread's (t0 + t1) + (t2 + t3) of its
+    float4, the xor butterfly 32 .. 1 over the wave's 64 lanes (60 idle threads add zeros), then (w0 + w1) + (w2 + w3)."""
+    M = t.shape[0]
+    q = t.reshape(M, 196, 4)
+    s = torch.zeros(M, 256, dtype=t.dtype, device=t.device)
+    s[:, :196] = (q[..., 0] + q[..., 1]) + (q[..., 2] + q[..., 3])
+    s = s.view(M, 4, 64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s[..., :o] + s[..., o:]
+    s = s[..., 0]
+    return (s[:, 0] + s[:, 1]) + (s[:, 2] + s[:, 3])
+
+
+def ead_step_reference(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, y: torch.Tensor, x: torch.Tensor,
+                       x_best: torch.Tensor | None, fstate: torch.Tensor | None, istate: torch.Tensor | None,
+                       sign: float, kappa: float, lr: float, c_init: float, beta: float, k: int, steps: int,
+                       search: int, lo: float, hi: float, rule: str = "en", first: bool = False,
+                       search_end: bool = False, last: bool = False):
+    """``ead_step`` operation by operation in torch float32 on any device, the two distance sums in the kernel's own
+    tree (the CPU / fp32 path of ``Predictor.elastic_net``, and what the kernel's tests hold it against).  Same
+    operands - ``dx``, ``x0``, ``y``, ``x``, ``x_best`` [M, 784], ``loss_rows`` [2 M] (the margins at the y rows, then
+    at the x rows), ``fstate`` [M, 4] (c, c_lo, c_hi, d_best), ``istate`` integers [M, 4] (succ, found_search, iters,
+    spare) - none of them modified; returns the new ``(y, x, x_best, fstate, istate)``.  With ``first`` x_best and the
+    records are not read (None will do) and ``x`` = ``y`` = the clean image.  Per image, with L_y, L_x = sign * the
+    two margins, s2 = MNIST_STD^2, D1 = sum |x - x0|, D2 = sum (x - x0)^2:
+
+        first:       c = c_init; c_lo = 0; c_hi = CW_C_INF; d_best = inf; succ = found_search = iters = 0; x_best = x0
+        evaluate:    dist = STD D1 ("l1") or s2 D2 + beta (STD D1) ("en");  ok = L_x > 0 and L_x >= kappa
+                     ok: succ = 1, and if dist < d_best: d_best = dist, x_best = x, found_search = search + 1
+        last:        stop here
+        search_end:  ``cw_step_reference``'s bisection of c;  succ = 0;  x = y = x0
+        otherwise:   act = L_y < kappa;  (lr_k, zeta_k) = ``ead_schedule(k, steps, lr)``
+                     z = y - (lr_k / s2) ((2 s2) (y - x0) - (sign c act) dx);  d = z - x0
+                     x+ = min(z - beta_n, hi) where d > beta_n, max(z + beta_n, lo) where d < -beta_n, else x0
+                     y+ = x+ + zeta_k (x+ - x);  iters += 1
+
+    Every scalar is rounded to float32 first, as the kernel receives it."""
+    import numpy as np
+    from ..data.datasets import MNIST_STD
+    if sign not in (1, -1) or (first and last) or not kappa >= 0 or not lr > 0 or not beta >= 0 or int(search) < 0:
+        raise ValueError("ead_step_reference: sign is +1 or -1, kappa >= 0, lr > 0, beta >= 0, search >= 0, and a "
+                         "launch is not first and last")
+    if rule not in EAD_RULES:
+        raise ValueError(f"ead_step_reference: rule must be 'en' or 'l1', got {rule!r}")
+    if first and not c_init > 0:
+        raise ValueError("ead_step_reference: c_init must be > 0")
+    f32 = np.float32
+    dt, dev = torch.float32, dx.device
+    M = x0.shape[0]
+    kap, lo32, hi32 = float(f32(kappa)), float(f32(lo)), float(f32(hi))
+    std, s2, b32, bn = f32(MNIST_STD), f32(cw_dist_scale()), f32(beta), f32(ead_beta_n(beta))
+    big = float(f32(CW_C_BIG))
+    x0, x, y = (q.reshape(M, 784).to(dt) for q in (x0, x, y))
+    L = float(sign) * loss_rows.reshape(-1)[:2 * M].to(dt)
+    Ly, Lx = L[:M], L[M:]
+    i32 = dict(dtype=torch.int32, device=dev)
+    if first:
+        c = torch.full((M,), float(f32(c_init)), dtype=dt, device=dev)
+        c_lo, c_hi = torch.zeros_like(c), torch.full_like(c, float(f32(CW_C_INF)))
+        d_best = torch.full_like(c, float("inf"))
+        succ, found, iters, spare = (torch.zeros(M, **i32) for _ in range(4))
+        xb = x0
+    else:
+        c, c_lo, c_hi, d_best = fstate.reshape(M, 4).to(dt).unbind(dim=1)
+        succ, found, iters, spare = istate.reshape(M, 4).to(torch.int32).unbind(dim=1)
+        xb = x_best.reshape(M, 784).to(dt)
+    d = x - x0
+    dist = float(std) * _row_tree_sum(d.abs())
+    if rule == "en":
+        dist = float(s2) * _row_tree_sum(d * d) + float(b32) * dist
+    ok = (Lx > 0) & (Lx >= kap)
+    improved = ok & (dist < d_best)
+    succ = torch.where(ok, torch.ones_like(succ), succ)
+    d_best = torch.where(improved, dist, d_best)
+    found = torch.where(improved, torch.full_like(found, int(search) + 1), found)
+    xb = torch.where(improved[:, None], x, xb)
+    pack = lambda: (torch.stack((c, c_lo, c_hi, d_best), dim=1),                              # noqa: E731
+                    torch.stack((succ, found, iters, spare), dim=1))
+    if last:
+        return (y.clone(), x.clone(), xb, *pack())
+    if search_end:
+        s = succ > 0
+        hi_s = torch.minimum(c_hi, c)
+        c_s = torch.where(hi_s < big, (c_lo + hi_s) * 0.5, c)
+        lo_f = torch.maximum(c_lo, c)
+        c_f = torch.where(c_hi < big, (lo_f + c_hi) * 0.5, c * 10.0)
+        c, c_lo, c_hi = torch.where(s, c_s, c_f), torch.where(s, c_lo, lo_f), torch.where(s, hi_s, c_hi)
+        succ = torch.zeros_like(succ)
+        return (x0.clone(), x0.clone(), xb, *pack())
+    lr_k, zeta_k = ead_schedule(k, steps, lr)
+    lrs, k2, bnf = float(f32(lr_k) / s2), float(f32(2.0) * s2), float(bn)
+    sc = ((float(sign) * c) * (Ly < kap).to(dt))[:, None]
+    z = y - lrs * (k2 * (y - x0) - sc * dx.reshape(-1, 784)[:M].to(dt))
+    d = z - x0
+    x_new = torch.where(d > bnf, (z - bnf).clamp(max=hi32), torch.where(d < -bnf, (z + bnf).clamp(min=lo32), x0))
+    y_new = x_new + zeta_k * (x_new - x)
+    iters = iters + 1
+    return (y_new, x_new, xb, *pack())
+
+
+def ead_step(dx: torch.Tensor, loss_rows: torch.Tensor, x0: torch.Tensor, y: torch.Tensor, x: torch.Tensor,
+             x_best: torch.Tensor, fstate: torch.Tensor, istate: torch.Tensor, sign: float, kappa: float, lr: float,
+             c_init: float, beta: float, k: int, steps: int, search: int, lo: float, hi: float, rule: str = "en",
+             first: bool = False, search_end: bool = False, last: bool = False, M: int | None = None) -> None:
+    """One EAD (elastic-net) iteration per image (``csrc/kernels/ead.hip``), one launch, in place: from the gradient
+    rows ``dx`` (float32 [>= M, 784], what ``input_grad`` wrote for the y rows) and the CW margins ``loss_rows``
+    (float32 [>= 2 M]: entry i at the slack point ``y[i]``, entry M + i at the shrunk point ``x[i]``, what
+    ``head_margin`` stored for a chain over the y rows followed by the x rows), and the clean images ``x0``, the update
+    of ``ead_step_reference`` on ``y``, ``x``, ``x_best`` (float32 [>= M, 784]), ``fstate`` (float32 [>= M, 4]) and
+    ``istate`` (int32 [>= M, 4]).  float32 throughout, the distances a fixed tree: the same operands give the same
+    bits.  ``first``: no state is read, all of it is written, and ``x`` and ``y`` must hold ``x0``; ``search_end``:
+    the bisection of c and the restart from the clean image; ``last``: only the best point and the records are brought
+    up to date.  ``k``: the update's index inside the search step, in [0, ``steps``) (not read by a ``search_end`` or
+    ``last`` launch); ``search``: the search step's index.  ``M``: the images of the launch (default ``x.shape[0]``);
+    nothing past M is touched."""
+    from ..data.datasets import MNIST_STD
+    if x.dim() != 2 or x.device.type != "cuda":
+        raise ValueError("ead_step: x must be a float32 [M, 784] tensor on the GPU")
+    dev = x.device
+    M = int(x.shape[0] if M is None else M)
+    if M < 1 or M > EAD_MAX_M:
+        raise ValueError(f"ead_step: M = {M} images must be in [1, EAD_MAX_M = {EAD_MAX_M}] a launch")
+    rows = (("dx", dx), ("x0", x0), ("y", y), ("x", x), ("x_best", x_best))
+    for what, q in rows:
+        _f32_rows("ead_step", what, q, M, dev, at_least="M")
+    _df_vec("ead_step", "loss_rows", loss_rows, torch.float32, 2 * M, dev, "2 M")
+    _df_vec("ead_step", "fstate", fstate, torch.float32, 4 * M, dev, "4 M")
+    _df_vec("ead_step", "istate", istate, torch.int32, 4 * M, dev, "4 M")
+    ptrs = [q.data_ptr() for _, q in rows]
+    if len(set(ptrs)) != len(ptrs):
+        raise ValueError("ead_step: dx, x0, y, x and x_best must be five buffers")
+    if sign not in (1, -1) or not kappa >= 0 or not lr > 0 or not lo < hi or int(search) < 0 or (first and last):
+        raise ValueError("ead_step: need sign +1 or -1, kappa >= 0, lr > 0, lo < hi, search >= 0, and not first and last")
+    if first and not c_init > 0:
+        raise ValueError("ead_step: c_init must be > 0")
+    if not beta >= 0 or rule not in EAD_RULES:
+        raise ValueError("ead_step: need beta >= 0 and rule 'en' or 'l1'")
+    lr_k, zeta_k = (float(lr), 0.0) if (search_end or last) else ead_schedule(k, steps, lr)
+    p = native.ptr
+    _C().ead_step(p(dx), p(loss_rows), p(x0), p(y), p(x), p(x_best), p(fstate), p(istate), float(sign), float(kappa),
+                  float(c_init), lr_k, zeta_k, float(beta), ead_beta_n(beta), float(MNIST_STD), cw_dist_scale(),
+                  float(lo), float(hi), int(search), EAD_RULES[rule], bool(first), bool(search_end), bool(last), M,
+                  _s())
+
+
 IBP_SPLITS = 36                     # fc1 split-K of ibp_fc1: fixed, whatever the batch (kernels.h IBP_SPLITS)
 IBP_MAX_B = 65535                   # most images one ibp launch takes (kernels.h IBP_MAX_B)
 IBP_EPS, IBP_LO, IBP_HI, IBP_MARGIN = 0, 1, 2, 3         # columns of the per-image record, float32 [M, 4]
